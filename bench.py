@@ -50,6 +50,34 @@ def mvm_bytes(rows: int, cols: int) -> int:
     return rows * cols // 2 + 4 * (rows // 64) * (cols // 64) + (cols // 2 + cols // 16) + (rows // 2 + rows // 16)
 
 
+SIDE_STEPS = 20                      # timed steps of every side measurement (cold pass, c5, product loops): min(--steps, this)
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: total size of the written arrays
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as out_dir/<name>.npy (float32 or float64 only), all of them within DUMP_LIMIT_BYTES."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} B exceeds {DUMP_LIMIT_BYTES} B"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
+def decode_v4(nib, scales) -> dict:
+    """A packed CloverVector4 (32 bytes of nibbles per 64-element block, high nibble first, + one fp32 scale per block) as the
+    caller receives it: the restored values (nibble * (scale / 7), the reference's restore order), the nibbles and the scales."""
+    import numpy as np
+    b = np.asarray(nib, dtype=np.uint8)
+    q = np.empty(2 * b.size, dtype=np.int8)
+    q[0::2] = ((b >> 4) ^ 8).astype(np.int8) - 8
+    q[1::2] = ((b & 15) ^ 8).astype(np.int8) - 8
+    s = np.asarray(scales, dtype=np.float32)
+    vals = (q.astype(np.float32).reshape(-1, 64) * (s / np.float32(7.0))[:, None]).reshape(-1)
+    return {"values": vals, "nibbles": q.astype(np.float32), "scales": s}
+
+
 # ----------------------------------------------------------------------------------------------------
 # CPU baseline leg (runs in a child process so OpenMP binding env vars take effect)
 # ----------------------------------------------------------------------------------------------------
@@ -221,7 +249,9 @@ def run_cpu_baseline(hip, A, sA, x, sx, r, sr, rows_total: int, cols: int, sampl
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=500)
+    ap.add_argument("--steps", type=int, default=500,
+                    help=f"timed steps of the headline (ms_per_step = their wall time / K); the side measurements behind it -- the cold pass, "
+                         f"the c5 object, the product's loops -- time min(K, {SIDE_STEPS}) steps each, so that K alone sets the run's length")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps before the timed ones (default 20; 80 for --workload gemm: the matrix "
                                                                "pipe's clocks settle after about 50 calls)")
     ap.add_argument("--rows-per-gpu", type=int, default=65536)
@@ -256,10 +286,16 @@ def main() -> None:
     ap.add_argument("--no-one-process", action="store_true",
                     help="leave out the `one_process` and `gemm_sharded` objects (the product's clm4_sharded_* loops over the same N devices, "
                          "driven by rank 0 behind the ranks' timed regions)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES >> 20} MB in all; a fixed, seeded sample of a larger output).  The inputs are seeded: the "
+                         "same arguments give the same inputs on every run, so two builds can be compared output for output")
     ap.add_argument("--cpu-baseline-child", type=str, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--gemm-probe-child", type=str, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--product-loops-child", type=int, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.dump_outputs and args.mode == "one-process":
+        raise SystemExit("bench.py --dump-outputs: supported for the mvm path in --mode ranks and for --workload gemm")
     if args.warmup is None:
         args.warmup = 80 if args.workload == "gemm" else 20
     if args.event_every <= 0:
@@ -285,7 +321,7 @@ def main() -> None:
     import torch.distributed as dist
 
     from clover_amd.lib_binding import DOT_EXACT, DOT_FAST, CloverHip
-    from clover_amd.sharding import gather_packed, gather_packed_async, packed_bytes, partition_rows
+    from clover_amd.sharding import gather_packed, gather_packed_async, packed_bytes, partition_rows, unpack_gathered
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -379,10 +415,10 @@ def main() -> None:
     hip.check(lib.clv_fill_random_nibbles(x.data_ptr(), x.numel(), seed + 2, 0, stream))
     hip.check(lib.clv_fill_random_scales(sx.data_ptr(), sx.numel(), seed + 3, 0, stream))
 
-    def time_config(rows: int, cold_first: bool) -> dict:
+    def time_config(rows: int, cold_first: bool, steps: int) -> dict:
         """One row-sharded mvm configuration: this rank's `rows` rows of a (rows * world) x cols matrix, generated in HBM, then
-        [cold_first: W warm-up + K timed steps straight away], the clock settle, W warm-up steps and the K timed steps.  Both timed regions
-        are bracketed by barrier + synchronize, their wall time is the max over ranks."""
+        [cold_first: W warm-up + min(K, SIDE_STEPS) timed steps straight away], the clock settle, W warm-up steps and the K = `steps`
+        timed steps.  Both timed regions are bracketed by barrier + synchronize, their wall time is the max over ranks."""
         assert rows % 64 == 0
         rows_total = rows * world
         # ---- synthetic operands, resident in HBM (quantised domain: nibbles U[-7,7], scales U[0.5,2)) ----
@@ -396,7 +432,7 @@ def main() -> None:
         res_bufs = [torch.empty(packed_bytes(rows), dtype=torch.uint8, device=dev) for _ in range(2)]
         res = res_bufs[0]
         pending = [None, None]
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
 
         def step(i: int | None, n: int) -> None:
             buf = res_bufs[n & 1]
@@ -419,8 +455,8 @@ def main() -> None:
                     pending[j].wait()
                     pending[j] = None
 
-        def timed_region() -> tuple[float, float]:
-            """W untimed + K timed steps -> (wall seconds of the K steps, max over ranks; kernel ms from the sampled event pairs, this rank)"""
+        def timed_region(k: int) -> tuple[float, float]:
+            """W untimed + k timed steps -> (wall seconds of the k steps, max over ranks; kernel ms from the sampled event pairs, this rank)"""
             for w_ in range(args.warmup):
                 step(None, w_)
             drain()
@@ -428,7 +464,7 @@ def main() -> None:
             if dist_on:
                 dist.barrier()
             t0 = time.perf_counter()
-            for i in range(args.steps):
+            for i in range(k):
                 step(i, i)
             drain()
             torch.cuda.synchronize()
@@ -438,11 +474,12 @@ def main() -> None:
             t = torch.tensor([el], dtype=torch.float64, device=red_dev)
             if dist_on:
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            km = [a.elapsed_time(b) for i, (a, b) in enumerate(ev) if i % args.event_every == 0]
+            km = [a.elapsed_time(b) for i, (a, b) in enumerate(ev[:k]) if i % args.event_every == 0]
             return float(t.item()), sum(km) / len(km)
 
         torch.cuda.synchronize()
-        cold = timed_region() if cold_first else None
+        cold_steps = min(steps, SIDE_STEPS)
+        cold = timed_region(cold_steps) if cold_first else None
         # clock settle (untimed, reported): the same step, back to back, until --settle-ms of work have been issued
         # (a launch COUNT derived from the shape, not a wall-clock loop: with N > 1 every step carries a collective, so all ranks must issue
         #  the same number of them)
@@ -456,13 +493,13 @@ def main() -> None:
                     settle_launches += 1
                 drain()
                 torch.cuda.synchronize()
-        elapsed, kern_mine = timed_region()
+        elapsed, kern_mine = timed_region(steps)
         kt = torch.tensor([kern_mine], dtype=torch.float64, device=red_dev)
         if dist_on:
             dist.all_reduce(kt, op=dist.ReduceOp.MAX)
-        r = {"rows": rows, "rows_total": rows_total, "elapsed": elapsed, "kern_avg_ms": float(kt.item()), "kern_samples": len(range(0, args.steps, args.event_every)),
-             "settle_launches": settle_launches, "cold": cold, "per_rank_kernel_ms": None, "gather_us": None, "gather_ok": None,
-             "A": A, "sA": sA, "res": res}
+        r = {"rows": rows, "rows_total": rows_total, "elapsed": elapsed, "kern_avg_ms": float(kt.item()), "kern_samples": len(range(0, steps, args.event_every)),
+             "settle_launches": settle_launches, "cold": cold, "cold_steps": cold_steps, "per_rank_kernel_ms": None, "gather_us": None, "gather_ok": None,
+             "A": A, "sA": sA, "res": res, "last": res_bufs[(steps - 1) & 1]}
         if dist_on:
             pr = [torch.zeros(1, dtype=torch.float64, device=red_dev) for _ in range(world)]
             dist.all_gather(pr, torch.tensor([kern_mine], dtype=torch.float64, device=red_dev))
@@ -479,7 +516,6 @@ def main() -> None:
             dist.all_reduce(gt, op=dist.ReduceOp.MAX)
             r["gather_us"] = round(float(gt.item()), 1)
             # outside the timed region: every rank finds its own shard, bit for bit, at its place in the gathered vector
-            from clover_amd.sharding import unpack_gathered
             g = gather_packed(res.cpu() if host_exchange else res, rows_total, group=data_group)
             nib, sc = unpack_gathered(g, rows_total, world)
             mine = res.cpu() if host_exchange else res
@@ -491,8 +527,28 @@ def main() -> None:
         return r
 
     rows = args.rows_per_gpu
-    head = time_config(rows, cold_first=True)
+    head = time_config(rows, cold_first=True, steps=args.steps)
     rows_total = head["rows_total"]
+    if args.dump_outputs:
+        # the result vector of the last timed step as the caller receives it: with N > 1 the all-gathered whole (untimed, every rank takes part)
+        last = head.pop("last")
+        if dist_on:
+            nib, sc = unpack_gathered(gather_packed(last.cpu() if host_exchange else last, rows_total, group=data_group), rows_total, world)
+        else:
+            nib, sc = last[: rows // 2], last[rows // 2:].view(torch.float32)
+        if rank == 0:
+            nib, sc = nib.cpu().numpy(), sc.cpu().numpy()
+            blocks = rows_total // 64
+            keep = blocks if blocks * (64 * 8 + 4) <= DUMP_LIMIT_BYTES // 2 else (DUMP_LIMIT_BYTES // 2) // (64 * 8 + 4 + 8)
+            dump = {}
+            if keep < blocks:                                    # a fixed, seeded sample of whole 64-row blocks
+                idx = np.sort(np.random.default_rng(0xD0).choice(blocks, keep, replace=False))
+                nib = nib.reshape(blocks, 32)[idx].reshape(-1)
+                sc = sc[idx]
+                dump["mvm_result_block_index"] = idx.astype(np.float64)
+            dump.update({f"mvm_result_{k}": v for k, v in decode_v4(nib, sc).items()})
+            write_outputs(args.dump_outputs, dump)
+    head.pop("last", None)
     rccl_ranks = (dist.get_world_size(data_group) if data_backend == "nccl" else 0) if dist_on else None
 
     # BASELINE configs[4] in the same line: the 2^20 x 2^16 matrix row-sharded over the N ranks (2^20 / N rows each: strong scaling; 32 GiB
@@ -508,19 +564,20 @@ def main() -> None:
             if not keep_for_cpu:
                 del head_A, head_sA
             torch.cuda.empty_cache()
-            c5r = time_config(c5_total // world, cold_first=False)
-            c5r.pop("A"), c5r.pop("sA"), c5r.pop("res")
+            c5_steps = min(args.steps, SIDE_STEPS)
+            c5r = time_config(c5_total // world, cold_first=False, steps=c5_steps)
+            c5r.pop("A"), c5r.pop("sA"), c5r.pop("res"), c5r.pop("last")
             torch.cuda.empty_cache()
             if keep_for_cpu:
                 head["A"], head["sA"] = head_A, head_sA
             head["res"] = head_res
             b_tot, b_gpu = mvm_bytes(c5_total, cols), mvm_bytes(c5_total // world, cols)
-            ms5 = c5r["elapsed"] / args.steps * 1e3
+            ms5 = c5r["elapsed"] / c5_steps * 1e3
             ach5 = b_gpu / (c5r["kern_avg_ms"] * 1e-3) / 1e9
             c5 = {
                 "workload": f"CloverMatrix4::mvm {c5_total}x{cols} int4 row-sharded {world} way(s), {c5_total // world} rows per GPU"
                             + (" = BASELINE configs[4]" if (c5_total, cols) == (1 << 20, 65536) else " (NOT configs[4]: shrunk by CLOVER_BENCH_C5_ROWS / --cols)"),
-                "scaling": "strong", "n_gpus": world, "rows_per_gpu": c5_total // world, "cols": cols, "steps": args.steps, "warmup": args.warmup,
+                "scaling": "strong", "n_gpus": world, "rows_per_gpu": c5_total // world, "cols": cols, "steps": c5_steps, "warmup": args.warmup,
                 "settle_launches": c5r["settle_launches"],
                 "ms_per_step": round(ms5, 5), "value": round(b_tot / (ms5 * 1e-3) / 1e9, 2), "unit": "GB/s",
                 "frac": round(b_tot / (ms5 * 1e-3) / 1e9 / (world * HBM_PEAK_GBS), 4), "frac_of": f"{world} x {HBM_PEAK_GBS:g} GB/s",
@@ -541,7 +598,7 @@ def main() -> None:
     elapsed, kern_avg_ms, settle_launches = head["elapsed"], head["kern_avg_ms"], head["settle_launches"]
     per_rank_kernel_ms, gather_us, gather_ok = head["per_rank_kernel_ms"], head["gather_us"], head["gather_ok"]
     ms_per_step = elapsed / args.steps * 1e3
-    ms_cold = head["cold"][0] / args.steps * 1e3
+    ms_cold = head["cold"][0] / head["cold_steps"] * 1e3
     bytes_total = mvm_bytes(rows_total, cols)
     bytes_gpu = mvm_bytes(rows, cols)
     value = bytes_total / (ms_per_step * 1e-3) / 1e9
@@ -576,7 +633,7 @@ def main() -> None:
             "algorithmic_bytes_per_step": bytes_total,
             "clock_settle": f"{settle_launches} untimed launches of the same step ({args.settle_ms:g} ms) before the {args.warmup} warm-up steps "
                             "(steady clocks need 20-30 ms of work after idle); the K timed steps and their barriers are unchanged; "
-                            "ms_per_step_cold = the same K steps measured before any of that",
+                            f"ms_per_step_cold = the first min(K, {SIDE_STEPS}) = {head['cold_steps']} of the same steps, measured before any of that",
             "arithmetic": "int4 x int4 products summed exactly per 32-bit word (v_dot8_i32_i4), fp32 per-block scale + fma chains in reference order",
         },
         "roofline": {
@@ -689,7 +746,7 @@ def one_process_measure(args, torch, hip, n: int) -> dict:
     hip.check(lib.clv_fill_random_scales(sx.data_ptr(), sx.numel(), 0xC10FE4 + 3, 0, None))
     torch.cuda.synchronize()
 
-    def time_config(rows: int) -> dict:
+    def time_config(rows: int, steps: int) -> dict:
         rows_total = rows * n
         devs = (C.c_int * n)(*([0] * n if debug else range(n)))
         ctx = C.c_void_p()
@@ -697,7 +754,7 @@ def one_process_measure(args, torch, hip, n: int) -> dict:
         try:
             hip.check(lib.clm4_sharded_fill_random(ctx, 0xC10FE4))
             hip.check(lib.clm4_sharded_set_x(ctx, x.data_ptr(), sx.data_ptr(), 0))
-            hip.check(lib.clm4_sharded_loop_begin(ctx, args.steps))
+            hip.check(lib.clm4_sharded_loop_begin(ctx, steps))
             settle = 0
             if args.settle_ms > 0:                        # clock settle, as in ranks mode (untimed)
                 settle_target = min(256, max(8, int(args.settle_ms / (mvm_bytes(rows, cols) / 6.0e12 * 1e3) + 7) // 8 * 8))
@@ -710,8 +767,8 @@ def one_process_measure(args, torch, hip, n: int) -> dict:
                 hip.check(lib.clm4_sharded_mvm_enqueue(ctx, w_, 0))
             hip.check(lib.clm4_sharded_sync(ctx))
             t0 = time.perf_counter()
-            sampled = list(range(0, args.steps, args.event_every))       # event triples around every Nth step only (see --event-every)
-            for i in range(args.steps):
+            sampled = list(range(0, steps, args.event_every))       # event triples around every Nth step only (see --event-every)
+            for i in range(steps):
                 hip.check(lib.clm4_sharded_mvm_enqueue(ctx, i, 1 if i % args.event_every == 0 else 0))
             hip.check(lib.clm4_sharded_sync(ctx))
             elapsed = time.perf_counter() - t0
@@ -726,7 +783,7 @@ def one_process_measure(args, torch, hip, n: int) -> dict:
                 per_k.append(ks / len(sampled))
                 per_g.append(gs / len(sampled))
             # every device holds the full result, and it equals the unsharded call's (n * 72 KiB: compared on the host)
-            last = (args.steps - 1) & 1
+            last = (steps - 1) & 1
             full = []
             for d in range(n):
                 rp, sp = C.c_void_p(), C.c_void_p()
@@ -761,7 +818,7 @@ def one_process_measure(args, torch, hip, n: int) -> dict:
                 "rccl_ranks": ranks.value, "settle_launches": settle}
 
     rows = args.rows_per_gpu
-    h = time_config(rows)
+    h = time_config(rows, args.steps)
     rows_total = h["rows_total"]
     backend = lambda r: "rccl (dlopen, ncclCommInitAll)" if r["rccl_ranks"] else "device copies"       # noqa: E731
     ms_per_step = h["elapsed"] / args.steps * 1e3
@@ -797,14 +854,15 @@ def one_process_measure(args, torch, hip, n: int) -> dict:
         if c5_total % (64 * n) != 0:
             out["c5"] = {"skipped": f"{c5_total} rows do not split into {n} equal shards of whole 64-row blocks"}
         else:
-            c = time_config(c5_total // n)
-            ms5, k5 = c["elapsed"] / args.steps * 1e3, max(c["per_k"])
+            c5_steps = min(args.steps, SIDE_STEPS)
+            c = time_config(c5_total // n, c5_steps)
+            ms5, k5 = c["elapsed"] / c5_steps * 1e3, max(c["per_k"])
             b_tot, b_gpu = mvm_bytes(c5_total, cols), mvm_bytes(c5_total // n, cols)
             ach5 = b_gpu / (k5 * 1e-3) / 1e9
             out["c5"] = {
                 "workload": f"CloverMatrix4::mvm {c5_total}x{cols} int4 row-sharded {n} way(s), {c5_total // n} rows per GPU"
                             + (" = BASELINE configs[4]" if (c5_total, cols) == (1 << 20, 65536) else " (NOT configs[4]: shrunk by CLOVER_BENCH_C5_ROWS / --cols)"),
-                "scaling": "strong", "n_gpus": n, "rows_per_gpu": c5_total // n, "cols": cols, "steps": args.steps, "warmup": args.warmup,
+                "scaling": "strong", "n_gpus": n, "rows_per_gpu": c5_total // n, "cols": cols, "steps": c5_steps, "warmup": args.warmup,
                 "settle_launches": c["settle_launches"], "mode": "one-process",
                 "ms_per_step": round(ms5, 5), "value": round(b_tot / (ms5 * 1e-3) / 1e9, 2), "unit": "GB/s",
                 "frac": round(b_tot / (ms5 * 1e-3) / 1e9 / (n * HBM_PEAK_GBS), 4), "frac_of": f"{n} x {HBM_PEAK_GBS:g} GB/s",
@@ -842,7 +900,7 @@ def run_product_loops(args, n: int) -> dict:
     """The product's own loops over the same N devices (`one_process`, `gemm_sharded`) in a CHILD process with a time limit: a side
     measurement -- RCCL through dlopen, ncclCommInitAll over N devices, paths no one-GPU box can rehearse with more than one rank --
     must never cost the headline line, whether it raises, crashes or hangs."""
-    cmd = [sys.executable, str(Path(__file__).resolve()), "--product-loops-child", str(n), "--gpus", str(n), "--steps", str(args.steps), "--warmup", str(args.warmup),
+    cmd = [sys.executable, str(Path(__file__).resolve()), "--product-loops-child", str(n), "--gpus", str(n), "--steps", str(min(args.steps, SIDE_STEPS)), "--warmup", str(args.warmup),
            "--rows-per-gpu", str(args.rows_per_gpu), "--cols", str(args.cols), "--settle-ms", str(args.settle_ms), "--event-every", str(args.event_every),
            "--gemm-size", str(args.gemm_size), *(["--preset", args.preset] if args.preset else []), *(["--no-c5"] if args.no_c5 else [])]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",
@@ -1060,6 +1118,16 @@ def gemm_main(args) -> None:
     elapsed = time.perf_counter() - t0
     ms = elapsed / args.steps * 1e3
     call_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
+    if args.dump_outputs:
+        # C of the last timed call (fp32, G x G): whole when it fits, else a fixed, seeded sample of its elements with their flat indices
+        import numpy as np
+        keep = G * G if G * G * 4 <= DUMP_LIMIT_BYTES else 1 << 20
+        if keep < G * G:
+            idx = np.sort(np.random.default_rng(0xD1).choice(G * G, keep, replace=False))
+            c = Cm[torch.from_numpy(idx).to(dev)].cpu().numpy()
+            write_outputs(args.dump_outputs, {"gemm_C_index": idx.astype(np.float64), "gemm_C": c})
+        else:
+            write_outputs(args.dump_outputs, {"gemm_C": Cm.cpu().numpy()})
     ops = 2.0 * G ** 3
     tops = ops / (ms * 1e-3) / 1e12
     ach = ops / (call_ms * 1e-3) / 1e12

@@ -73,3 +73,45 @@ def test_gemm_line():
     for k in CONTRACT:
         assert k in d, k
     assert d["unit"] == "TOP/s" and d["roofline"]["bound"] == "mfma" and d["value"] > 0
+
+
+def test_dump_decode_matches_oracle_restore(oracle):
+    """--dump-outputs writes the mvm result as the caller receives it: bench.decode_v4 == the oracle's CloverVector4 restore, bit for bit"""
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+    x = np.random.default_rng(3).normal(size=64 * 37).astype(np.float32)
+    q, s = oracle.v4_quantize(x)
+    d = bench.decode_v4(q, s)
+    assert np.array_equal(d["values"].view(np.uint32), oracle.v4_restore(q, s).view(np.uint32))
+    assert d["nibbles"].dtype == np.float32 and d["nibbles"].size == x.size and np.array_equal(d["scales"], s)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_mvm_same_inputs_same_outputs(tmp_path):
+    """--dump-outputs: the last timed step's result vector, float32, identical over two runs of the same arguments"""
+    import numpy as np
+
+    args = ["--gpus", "1", "--warmup", "1", "--rows-per-gpu", "8192", "--cols", "8192", "--no-c5", "--no-extras", "--no-cpu-baseline",
+            "--no-one-process"]
+    got = []
+    for k, steps in enumerate(("3", "5")):
+        d = _run([*args, "--steps", steps, "--dump-outputs", str(tmp_path / str(k))])
+        assert d["steps"] == int(steps) and d["ms_per_step"] > 0
+        got.append({n: np.load(tmp_path / str(k) / f"mvm_result_{n}.npy") for n in ("values", "nibbles", "scales")})
+    for g in got:
+        assert g["values"].dtype == np.float32 and g["values"].shape == (8192,) and g["scales"].shape == (8192 // 64,)
+        assert np.all(np.abs(g["nibbles"]) <= 7) and np.any(g["nibbles"] != 0)
+    for n in got[0]:
+        assert np.array_equal(got[0][n].view(np.uint32), got[1][n].view(np.uint32)), n
+
+
+@pytest.mark.gpu
+def test_dump_outputs_gemm(tmp_path):
+    import numpy as np
+
+    d = _run(["--workload", "gemm", "--gemm-size", "1024", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 2
+    c = np.load(tmp_path / "gemm_C.npy")
+    assert c.dtype == np.float32 and c.shape == (1024 * 1024,) and np.all(np.isfinite(c)) and np.any(c != 0)

@@ -269,3 +269,15 @@ def test_default_line_carries_baseline_config_4():
     assert out["ms_per_step_cold"] >= out["ms_per_step"] * 0.9 and out["value_cold"] > 0
     c5 = check_c5(out, 1, 1 << 20, 65536)
     assert c5["algorithmic_bytes_per_step"] == 34427473920 and c5["kernel_frac"] > 0.6
+
+
+@pytest.mark.gpu
+def test_steps_sets_the_headline_and_caps_the_side_measurements():
+    """--steps K times K headline steps; the cold pass, the c5 object and the product's loops behind it time min(K, 20) each, so that
+    the run's length follows K and ms_per_step alone"""
+    out = json_line(run_bench(["--gpus", "1", "--steps", "48", "--warmup", "2", "--rows-per-gpu", "4096", "--cols", "8192", "--no-cpu-baseline",
+                               "--no-extras"], {"CLOVER_BENCH_C5_ROWS": "16384", "CLOVER_BENCH_GEMM_SIZE": "1024"}))
+    assert out["steps"] == 48 and out["ms_per_step"] > 0 and out["ms_per_step_cold"] > 0
+    assert "min(K, 20) = 20 " in out["config"]["clock_settle"]
+    assert out["c5"]["steps"] == 20 and out["c5"]["ms_per_step"] > 0
+    assert out["one_process"]["steps"] == 20 and out["one_process"]["c5"]["steps"] == 20

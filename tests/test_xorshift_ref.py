@@ -7,17 +7,21 @@ seed pair (test/random/00_random.cpp:42): the four lanes after avx_xorshift128pl
 avx_xorshift128plus (:97-109), the state after them, a digest of the next 2^20 draws, and the state after
 avx_xorshift128plus_jump (:115-127).
 
-CPU tests: the oracle's restatement == fixture (and == the live reference build when oracle/_ref is present).
+CPU tests: the oracle's restatement == fixture, and == golden/xorshift_ref_keys.json (the reference's answers for 16 more
+keys); both fixtures and the oracle == the live reference build when oracle/_ref is present.
 GPU tests: clv_rng_seed == fixture lanes; the state a stochastic kernel leaves behind after consuming 256 (then 2^20 more)
 draws == the fixture's states, i.e. the device jump-ahead walks the reference's stream.
 """
+import hashlib
 import json
+import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 FIX = json.loads((Path(__file__).parent / "golden" / "xorshift_ref.json").read_text())
+KEYS_PATH = Path(__file__).parent / "golden" / "xorshift_ref_keys.json"
 STREAMS = FIX["streams"]
 IDS = [s["key1"] for s in STREAMS]
 
@@ -51,31 +55,56 @@ def test_oracle_init_draws_digest_jump_equal_reference_fixture(oracle, s):
     assert np.array_equal(k0, _u64s(s["after_jump_s0"])) and np.array_equal(k1, _u64s(s["after_jump_s1"]))
 
 
+def _key_cases():
+    """16 more key pairs and draw counts, seeded"""
+    rs = np.random.default_rng(7)
+    for _ in range(16):
+        k1, k2 = (int(v) for v in rs.integers(1, 2**63, size=2))
+        yield k1, k2, int(rs.integers(1, 2000))
+
+
+def _hexs(a):
+    return [f"{int(v):016x}" for v in a]
+
+
+def _record(k1, k2, n, init, draw, digest, jump, keys):
+    """one key pair through a generator: init lanes, SHA-256 of n draws, digest of the next 50000, state after the jump"""
+    st = init(k1, k2)
+    s0, s1 = keys(st)
+    rec = {"key1": str(k1), "key2": str(k2), "init_s0": _hexs(s0), "init_s1": _hexs(s1), "draws": n,
+           "draws_sha256": hashlib.sha256(np.ascontiguousarray(draw(st, n), dtype="<u4").tobytes()).hexdigest()}
+    x, a = digest(st, 50000)
+    jump(st)
+    s0, s1 = keys(st)
+    rec.update({"digest_xor_fold": f"{x:016x}", "digest_sum": f"{a:016x}", "after_jump_s0": _hexs(s0), "after_jump_s1": _hexs(s1)})
+    return rec
+
+
+def _oracle_records(oracle):
+    return [_record(k1, k2, n, oracle.rng, lambda r, m: np.stack([oracle.rng_draw(r) for _ in range(m)]), oracle.rng_digest, oracle.rng_jump,
+                    oracle.rng_keys) for k1, k2, n in _key_cases()]
+
+
+def _reference_records(ref):
+    return [_record(k1, k2, n, lambda a, b: ref.init(a, b), lambda st, m: ref.draw(*st, m), lambda st, m: ref.digest(*st, m),
+                    lambda st: ref.jump(*st), lambda st: st) for k1, k2, n in _key_cases()]
+
+
 def test_fixture_matches_live_reference_build_when_present(oracle):
-    """Where oracle/_ref/libxorshift_ref.so exists (builder container: compiled from /root/reference; GPU box: the prebuilt
-    file), the committed fixture and the oracle are re-checked against the reference code itself, on other keys too."""
+    """The reference's answers for 16 more keys (golden/xorshift_ref_keys.json, written from oracle/_ref by `python
+    tests/test_xorshift_ref.py`) are the oracle's, everywhere.  Where oracle/_ref/libxorshift_ref.so exists (built by `make -C oracle
+    ref` where the reference tree is), the committed fixtures and the oracle are re-checked against the reference code itself too."""
     from oracle.binding import RefXorshift
+    want = json.loads(KEYS_PATH.read_text())["cases"]
+    assert len(want) == 16 and _oracle_records(oracle) == want
     if not RefXorshift.available():
-        pytest.skip("no oracle/_ref build and no /root/reference here: the committed fixture is the pin")
+        return
     ref = RefXorshift()
     for s in STREAMS:
         s0, s1 = ref.init(int(s["key1"]), int(s["key2"]))
         assert np.array_equal(s0, _u64s(s["init_s0"])) and np.array_equal(s1, _u64s(s["init_s1"]))
         assert np.array_equal(ref.draw(s0, s1, FIX["draws"]), _words(s))
-    rs = np.random.default_rng(7)
-    for _ in range(16):
-        k1, k2 = (int(v) for v in rs.integers(1, 2**63, size=2))
-        s0, s1 = ref.init(k1, k2)
-        r = oracle.rng(k1, k2)
-        o0, o1 = oracle.rng_keys(r)
-        assert np.array_equal(o0, s0) and np.array_equal(o1, s1)
-        n = int(rs.integers(1, 2000))
-        assert np.array_equal(ref.draw(s0, s1, n), np.stack([oracle.rng_draw(r) for _ in range(n)]))
-        assert ref.digest(s0, s1, 50000) == oracle.rng_digest(r, 50000)
-        ref.jump(s0, s1)
-        oracle.rng_jump(r)
-        o0, o1 = oracle.rng_keys(r)
-        assert np.array_equal(o0, s0) and np.array_equal(o1, s1)
+    assert _reference_records(ref) == want
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -127,3 +156,11 @@ def test_gpu_other_stochastic_kernels_walk_the_same_reference_stream(hip, oracle
     k0, k1 = hip.rng_get(st)
     o0, o1 = oracle.rng_keys(r)
     assert np.array_equal(k0, o0) and np.array_equal(k1, o1)
+
+
+if __name__ == "__main__":
+    # regenerate golden/xorshift_ref_keys.json from the reference's generator (oracle/_ref, `make -C oracle ref`)
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+    from oracle.binding import RefXorshift
+    KEYS_PATH.write_text(json.dumps({"generator": "oracle/_ref/libxorshift_ref.so (python tests/test_xorshift_ref.py)",
+                                     "cases": _reference_records(RefXorshift())}, indent=1) + "\n")
