@@ -80,10 +80,13 @@ def probe_library_path() -> Path:
 def build_probe_library(force: bool = False) -> Path:
     """libclover_hip_probe.so = the product's objects with gemm6.hip compiled a second time under -DCLV_GEMM_EXPERIMENTS: the GEMM main
     loop's timing-only variants with parts left out (tools/gen_gemm6_loop256.py ... experiments; results wrong by construction), selected
-    by CLV_GEMM_LOOP=vN -- and matrix4.hip under -DCLV_EXPERIMENTS: the mvm kernel variants and the plain read-bandwidth kernel behind
-    tools/microbench.py (clvx_mvm_variant, clvx_read_bw).  It lives under tools/_build/, and clv_version() of it reads "clover_hip_probe ..." (load_library refuses that unless
+    by CLV_GEMM_LOOP=vN -- and matrix4.hip, iht_persist.hip and threshold4.hip under -DCLV_EXPERIMENTS: the mvm kernel variants and the
+    plain read-bandwidth kernel behind tools/microbench.py (clvx_mvm_variant, clvx_read_bw); the phase stamps of the persistent IHT and
+    threshold kernels, written to the device buffer whose address CLV_IHT_DEBUG_STAMPS / CLV_THRESHOLD_DEBUG_STAMPS hold, and the IHT
+    kernels' spin-wait sleeps from CLV_IHT_NAP0 / CLV_IHT_NAP (tools/iht_persist_probe.py, tools/thresh3_probe.py).  It lives under tools/_build/, and clv_version() of it reads "clover_hip_probe ..." (load_library refuses that unless
     allow_probe=True).  BENCH INFRASTRUCTURE: bench.py's `gemm.ceiling` and tools/gemm_bench.py load it explicitly to measure what the
-    arithmetic alone costs on the box the bench runs on; nothing else ever loads it and the product library has no such switch."""
+    arithmetic alone costs on the box the bench runs on; beyond those only the probe tools load it, and the product library has none of these
+    switches."""
     import sys
     root = repo_root()
     src_dir = root / "clover_amd" / "csrc"
@@ -95,18 +98,22 @@ def build_probe_library(force: bool = False) -> Path:
     build_hip_library(force=force)
     obj_dir = hip_library_path().parent / "obj"
     gen = root / "tools" / "gen_gemm6_loop256.py"
-    deps = [src_dir / "gemm6.hip", src_dir / "matrix4.hip", gen, hip_library_path()] + list(src_dir.glob("*.h")) + list(src_dir.glob("*.inc"))
+    exp_srcs = ["matrix4.hip", "iht_persist.hip", "threshold4.hip"]      # compiled again under -DCLV_EXPERIMENTS
+    deps = [src_dir / "gemm6.hip", *[src_dir / s for s in exp_srcs], gen, hip_library_path()] + list(src_dir.glob("*.h")) + list(src_dir.glob("*.inc"))
     if force or _stale(out, deps):
         subprocess.run([sys.executable, str(gen), str(obj_dir / "gemm6_loop256_exp.inc"), "experiments"], check=True, stdout=subprocess.DEVNULL)
         obj = obj_dir / "gemm6_probe.o"
         subprocess.run([_hipcc(), *HIP_FLAGS, "-DCLV_GEMM_EXPERIMENTS", f"-I{root / 'include'}", f"-I{src_dir}", f"-I{obj_dir}", "-c", "-o", str(obj),
                         str(src_dir / "gemm6.hip")], check=True)
-        # matrix4.hip with its experiment entry points (clvx_read_bw, clvx_mvm_variant: tools/microbench.py, pmc_probe.py) -- the product
-        # library is compiled without them
-        obj_m = obj_dir / "matrix4_probe.o"
-        subprocess.run([_hipcc(), *HIP_FLAGS, "-DCLV_EXPERIMENTS", f"-I{root / 'include'}", f"-I{src_dir}", "-c", "-o", str(obj_m),
-                        str(src_dir / "matrix4.hip")], check=True)
-        objs = [str(obj_dir / (Path(s).stem + ".o")) for s in HIP_SOURCES if s not in ("gemm6.hip", "matrix4.hip")] + [str(obj), str(obj_m)]
+        # the CLV_EXPERIMENTS sources with their probe-only parts (the product library is compiled without them), in parallel
+        exp_objs = [obj_dir / (Path(s).stem + "_probe.o") for s in exp_srcs]
+        jobs = [(cmd, subprocess.Popen(cmd)) for cmd in
+                ([_hipcc(), *HIP_FLAGS, "-DCLV_EXPERIMENTS", f"-I{root / 'include'}", f"-I{src_dir}", "-c", "-o", str(o), str(src_dir / s)]
+                 for s, o in zip(exp_srcs, exp_objs))]
+        for cmd, proc in jobs:
+            if proc.wait() != 0:
+                raise subprocess.CalledProcessError(proc.returncode, cmd)
+        objs = [str(obj_dir / (Path(s).stem + ".o")) for s in HIP_SOURCES if s not in ("gemm6.hip", *exp_srcs)] + [str(obj), *map(str, exp_objs)]
         subprocess.run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(out), *objs, "-ldl"], check=True)
     return out
 

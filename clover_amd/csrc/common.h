@@ -42,6 +42,19 @@ static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream
 
 // number of compute units of the current device (cached per device)
 int clv_cu_count();
+// the library's switches: clv_env is getenv, clv_env_int its base-10 value (atoi's parse) or `dflt` when unset.  Switches read ONCE per
+// process keep the value in a function-local static at the call site (CLV_GEMM_*, CLV_DOT_FAST_TWO_LAUNCHES, CLV_SAA8_BLK_MIN_BLOCKS,
+// CLV_ST_SEGMENTS); CLV_IHT_PERSISTENT, CLV_THRESHOLD_THREE_LAUNCH and CLV_THRESHOLD_FORCE_CAND are read on EVERY call: bench.py and the
+// tests flip them through os.environ inside one process.
+const char *clv_env(const char *name);
+long long clv_env_int(const char *name, long long dflt);
+// CLV_PROBE(...): its arguments in the probe library (-DCLV_EXPERIMENTS, tools/_build/libclover_hip_probe.so), nothing in the product --
+// the phase stamps of the persistent kernels, their debug pointers and the spin-wait overrides
+#ifdef CLV_EXPERIMENTS
+#define CLV_PROBE(...) __VA_ARGS__
+#else
+#define CLV_PROBE(...)
+#endif
 // grow-only per-device scratch buffer used when the caller passes workspace == NULL
 int clv_internal_workspace(void **ptr, uint64_t bytes, hipStream_t stream);      // grow-only scratch per (device, stream)
 void clv_internal_workspace_forget(hipStream_t stream);

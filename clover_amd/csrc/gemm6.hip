@@ -436,7 +436,7 @@ static inline uint64_t image_bytes(uint64_t rows, uint64_t K, uint32_t tile) { r
 // CLV_GEMM_TILE=128|256 forces one (A/B runs, tests).
 static uint32_t pick_tile(uint64_t M, uint64_t N)
 {
-    static const int forced = [] { const char *e = getenv("CLV_GEMM_TILE"); return e ? atoi(e) : 0; }();
+    static const int forced = (int)clv_env_int("CLV_GEMM_TILE", 0);
     if (forced == 128 || forced == 256) return (uint32_t)forced;
     const uint64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
     return tiles >= (uint64_t)clv_cu_count() ? 256u : 128u;
@@ -512,7 +512,7 @@ static int gemm_fp6_run(const clm4_gemm_operand *opA, const int8_t *A, const flo
         const uint32_t s0 = i32 ? (uint32_t)(kb_begin / 2) : 0u, ns = i32 ? (uint32_t)(kb_count / 2) : (uint32_t)(K / 128);
         int variant = 0;
 #ifdef G6T_LOOP_EXPERIMENTS
-        static const int env_variant = [] { const char *e = getenv("CLV_GEMM_LOOP"); return e && e[0] == 'v' ? atoi(e + 1) : 0; }();
+        static const int env_variant = [] { const char *e = clv_env("CLV_GEMM_LOOP"); return e && e[0] == 'v' ? atoi(e + 1) : 0; }();
         variant = env_variant;
 #endif
 #define G6T_LAUNCH(I, V)                                                                                                                   \
@@ -561,13 +561,13 @@ static int gemm_fp6_run(const clm4_gemm_operand *opA, const int8_t *A, const flo
         return CLV_OK;
     }
     // CLV_GEMM_LOOP=hipcc: the compiler-scheduled main loop (A/B runs); default: the hand-scheduled one
-    static const bool hipcc_loop = [] { const char *e = getenv("CLV_GEMM_LOOP"); return e && !strcmp(e, "hipcc"); }();
+    static const bool hipcc_loop = [] { const char *e = clv_env("CLV_GEMM_LOOP"); return e && !strcmp(e, "hipcc"); }();
     if (hipcc_loop) {
         hipLaunchKernelGGL(k_m4_gemm_fp6, grid, block, G6_LDS_BYTES, st, A6, sA, B6, sB, M, N, K, (float *)C, tiles_m, tiles_n);
     } else {
 #define G6_LAUNCH(V) hipLaunchKernelGGL(k_m4_gemm_fp6_asm<V>, grid, block, G6_LDS_BYTES, st, A6, sA, B6, sB, 0u, N, K, (float *)C, tiles_m, tiles_n, (uint32_t)(K / 128))
 #ifdef G6_LOOP_EXPERIMENTS
-        static const int variant = [] { const char *e = getenv("CLV_GEMM_LOOP"); return e && e[0] == 'v' ? atoi(e + 1) : 0; }();
+        static const int variant = [] { const char *e = clv_env("CLV_GEMM_LOOP"); return e && e[0] == 'v' ? atoi(e + 1) : 0; }();
         switch (variant) {
         case 1: G6_LAUNCH(1); break;
         case 2: G6_LAUNCH(2); break;
@@ -636,7 +636,7 @@ static int gemm_i32_checked(const char *who, const clm4_gemm_operand *opA, const
     CLV_REQUIRE(!opB || (opB->rows == N && opB->K == K), "%s: operand B was prepared as %llu x %llu", who, opB ? (unsigned long long)opB->rows : 0ull,
                 opB ? (unsigned long long)opB->K : 0ull);
     hipStream_t st = as_stream(stream);
-    static const bool simple = [] { const char *e = getenv("CLV_GEMM_KERNEL"); return e && !strcmp(e, "simple"); }();
+    static const bool simple = [] { const char *e = clv_env("CLV_GEMM_KERNEL"); return e && !strcmp(e, "simple"); }();
     if (((kb_begin | kb_count) & 1) || simple) {
         // odd ranges run on the nibbles themselves
         CLV_REQUIRE(A && B, "%s: an odd K-block range needs the nibbles of both operands (A, B), not only their prepared images", who);

@@ -59,9 +59,11 @@ struct IhtpArgs {
     const u64 *seg_rows;
     u64 jump[64], jump1[64];
     uint32_t nap0, nap;           // s_sleep(1) units before the first poll round of a gather / between two rounds
-    u64 *dbg;                     // NULL, or 16 wall-clock stamps (100 MHz) per iteration and workgroup for tools/iht_persist_probe.py
+    CLV_PROBE(u64 *dbg;)          // probe build: NULL, or 16 wall-clock stamps (100 MHz) per iteration and workgroup for tools/iht_persist_probe.py
 };
-#define IHTP_STAMP(k) do { if (A.dbg && (threadIdx.x == 0 || threadIdx.x == IHTP_THREADS - 1) && it < 16) A.dbg[((size_t)g * 16 + it) * 32 + (threadIdx.x ? 16 : 0) + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define IHTP_STAMP(k) CLV_PROBE(do { if (A.dbg && (threadIdx.x == 0 || threadIdx.x == IHTP_THREADS - 1) && it < 16) A.dbg[((size_t)g * 16 + it) * 32 + (threadIdx.x ? 16 : 0) + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0))
+// probe build: the threshold's own stamps go to words 10-15 of the iteration's row
+#define IHTP_THR_DBG CLV_PROBE(, A.dbg && it < 16 ? A.dbg + ((size_t)g * 16 + it) * 32 : nullptr)
 
 // ---- who owns which rows ------------------------------------------------------------------------------------------------------------
 // A consumer thread owns ONE WORD of a vector (elements 8 w .. 8 w + 7) and wants its 8 dots with coalesced 16-byte loads (two granules
@@ -376,9 +378,9 @@ __device__ __forceinline__ u64 ihtp_lut_entry(uint32_t b)
 // bins in 4 copies (3 levels instead of 4, but a level's scan + clear by one wave costs 0.68 us against 0.42).
 // LDS: hist[4 * 256] zero on entry and again on exit; wtot[16], sel[8], lut[256].  9 workgroup barriers.
 __device__ __forceinline__ uint32_t ihtp_threshold(uint32_t w, float s, uint32_t tid_, uint32_t n, uint32_t k, uint32_t *hist, uint32_t *wtot,
-                                                   uint32_t *sel, const u64 *lut, u64 *dbg)
+                                                   uint32_t *sel, const u64 *lut CLV_PROBE(, u64 *dbg))
 {
-#define THR_STAMP(k_) do { if (dbg && threadIdx.x == 0) dbg[k_] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define THR_STAMP(k_) CLV_PROBE(do { if (dbg && threadIdx.x == 0) dbg[k_] = __builtin_amdgcn_s_memrealtime(); } while (0))
     const int tid = (int)tid_, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t first = 8u * tid;
     const uint32_t valid = first >= n ? 0u : (n - first < 8u ? n - first : 8u);
@@ -517,7 +519,7 @@ __global__ __launch_bounds__(IHTP_THREADS) void k_iht4_persist(const IhtpArgs A)
     }
     __syncthreads();
 
-    if (A.dbg && tid0 == 0) { A.dbg[((size_t)g * 16 + 15) * 32 + 28] = __builtin_readcyclecounter(); A.dbg[((size_t)g * 16 + 15) * 32 + 29] = __builtin_amdgcn_s_memrealtime(); }
+    CLV_PROBE(if (A.dbg && tid0 == 0) { A.dbg[((size_t)g * 16 + 15) * 32 + 28] = __builtin_readcyclecounter(); A.dbg[((size_t)g * 16 + 15) * 32 + 29] = __builtin_amdgcn_s_memrealtime(); })
     for (uint32_t it = 0; it < A.iterations; it++) {
         const uint32_t epoch = it + 1;
         // the thread index, opaque to the optimiser once per iteration: everything derived from it (LDS addresses, granule addresses,
@@ -604,8 +606,7 @@ __global__ __launch_bounds__(IHTP_THREADS) void k_iht4_persist(const IhtpArgs A)
             }
         }
         IHTP_STAMP(7);
-        if (A.threshold && A.K < A.x_len) xw = ihtp_threshold(xw, xs, tid, A.x_len, A.K, hist, wtot, sel, lut,
-                                                                       A.dbg && it < 16 ? A.dbg + ((size_t)g * 16 + it) * 32 : nullptr);       // all threads: barriers inside
+        if (A.threshold && A.K < A.x_len) xw = ihtp_threshold(xw, xs, tid, A.x_len, A.K, hist, wtot, sel, lut IHTP_THR_DBG);      // all threads: barriers inside
         IHTP_STAMP(8);
         if (tid < n / 8) {
             xv[dealt_word(tid)] = xw;
@@ -619,7 +620,7 @@ __global__ __launch_bounds__(IHTP_THREADS) void k_iht4_persist(const IhtpArgs A)
         __syncthreads();
         IHTP_STAMP(9);
     }
-    if (A.dbg && tid0 == 0) { A.dbg[((size_t)g * 16 + 15) * 32 + 30] = __builtin_readcyclecounter(); A.dbg[((size_t)g * 16 + 15) * 32 + 31] = __builtin_amdgcn_s_memrealtime(); }
+    CLV_PROBE(if (A.dbg && tid0 == 0) { A.dbg[((size_t)g * 16 + 15) * 32 + 30] = __builtin_readcyclecounter(); A.dbg[((size_t)g * 16 + 15) * 32 + 31] = __builtin_amdgcn_s_memrealtime(); })
     if (ST && g == 0) {                                                  // stamp the slot written in the last iteration (rng_device.h: rng_commit)
         __syncthreads();
         if (tid0 == IHTP_THREADS - 4 * segs1) {
@@ -841,10 +842,10 @@ __device__ __forceinline__ uint32_t pack4_i8(const int q[4]) { return ((uint32_t
 // two levels (a dozen) and ranking them in one wave instead of levels 2 and 3: 1.4 against 1.6 us, not kept; levels 1-3 on ONE copy of the bins
 // with one barrier each (no adding up): 0.63 against 0.79 us per level by the stamps, 13.4 against 13.4 us per iteration -- a level is
 // its ~100 instructions in each of 16 waves, whatever the barriers.)
-__device__ __forceinline__ void ihtp8_threshold(int q[8], float s, uint32_t tid_, uint32_t n, uint32_t k, uint32_t *hist, uint32_t *hsum, uint32_t *wtot,
-                                                u64 *dbg = nullptr)
+__device__ __forceinline__ void ihtp8_threshold(int q[8], float s, uint32_t tid_, uint32_t n, uint32_t k, uint32_t *hist, uint32_t *hsum, uint32_t *wtot
+                                                CLV_PROBE(, u64 *dbg))
 {
-#define THR8_STAMP(k_) do { if (dbg && threadIdx.x == 0) dbg[k_] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define THR8_STAMP(k_) CLV_PROBE(do { if (dbg && threadIdx.x == 0) dbg[k_] = __builtin_amdgcn_s_memrealtime(); } while (0))
     const int tid = (int)tid_, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     uint32_t keys[8], valid = 0;
 #pragma unroll
@@ -932,7 +933,7 @@ struct Ihtp8Args {
     int threshold;
     u64 *g1, *g2;
     uint32_t nap0, nap;
-    u64 *dbg;                     // probe only: phase stamps, as IhtpArgs
+    CLV_PROBE(u64 *dbg;)          // probe build: phase stamps, as IhtpArgs
     u64 *rng;                     // stochastic rounding (k_iht8_persist<true>): as IhtpArgs
     u64 seq;
     const u64 *seg_rows;
@@ -1107,7 +1108,7 @@ __global__ __launch_bounds__(IHTP_THREADS) void k_iht8_persist(const Ihtp8Args A
             __syncthreads();
         }
         if (A.threshold && A.K < A.x_len)
-            ihtp8_threshold(qx, xs, tid, A.x_len, A.K, hist, hsum, wtot, A.dbg && it < 16 ? A.dbg + ((size_t)g * 16 + it) * 32 : nullptr);
+            ihtp8_threshold(qx, xs, tid, A.x_len, A.K, hist, hsum, wtot IHTP_THR_DBG);
         IHTP_STAMP(8);
         if (tid < n / 8) {
             xw[0] = pack4_i8(qx);
@@ -1214,12 +1215,23 @@ int clv_internal_persist_enter(hipStream_t stream)
 }
 void clv_internal_persist_leave(void) { g_persist_mutex.unlock(); }
 
+#ifdef CLV_EXPERIMENTS
+// probe build only (tools/iht_persist_probe.py): other spin-wait sleeps, and a device buffer of grid * 16 * 32 words for the phase stamps
+template <class Args> static void ihtp_probe_overrides(Args &a)
+{
+    a.nap0 = (uint32_t)clv_env_int("CLV_IHT_NAP0", a.nap0);
+    a.nap = (uint32_t)clv_env_int("CLV_IHT_NAP", a.nap);
+    const char *e = clv_env("CLV_IHT_DEBUG_STAMPS");
+    a.dbg = e ? (u64 *)strtoull(e, nullptr, 0) : nullptr;
+}
+#endif
+
 // returns 1 if the persistent kernel was launched, 0 if the problem does not qualify (the caller runs the launch-per-step loop), < 0 on error
 int clm4_iht_persistent(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, int8_t *x,
                         float *sx, uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3,
                         float *st3, uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng, hipStream_t st)
 {
-    const int mode = [] { const char *e = getenv("CLV_IHT_PERSISTENT"); return e ? atoi(e) : 1; }();      // read per call: A/B runs flip it
+    const int mode = (int)clv_env_int("CLV_IHT_PERSISTENT", 1);      // read per call: A/B runs flip it
     if (!mode || threshold < 0 || threshold > 1 || !iterations || iterations >= 0x7FFFFFFFull) return 0;
     if (rng && (m + n) / 64 * 4 < 32) return 0;                             // stochastic: the per-iteration jumps T^(D - 16), T^(D - 17) want D >= 32
     if (m > IHTP_MAXLEN || n > IHTP_MAXLEN || m % 128 || n % 128 || !m || !n) return 0;
@@ -1272,10 +1284,7 @@ int clm4_iht_persistent(const int8_t *Phi, const float *sPhi, const int8_t *PhiT
     }
     a.nap0 = 14;         // ~0.4 us: measured best of 0 / 6 / 10 / 14 / 18 / 22 / 26 ... 40 at N = 8192 (profiles/r06_iht_persist_notes.txt)
     a.nap = 2;
-    if (const char *e = getenv("CLV_IHT_NAP0")) a.nap0 = (uint32_t)atoi(e);                             // probe only
-    if (const char *e = getenv("CLV_IHT_NAP")) a.nap = (uint32_t)atoi(e);                               // probe only
-    a.dbg = nullptr;
-    if (const char *e = getenv("CLV_IHT_DEBUG_STAMPS")) a.dbg = (u64 *)strtoull(e, nullptr, 0);      // probe only: a device buffer of grid * 16 * 32 words
+    CLV_PROBE(ihtp_probe_overrides(a);)
     PersistChain chain(st);
     if (chain.rc) return -1;
     if (rng) {
@@ -1298,7 +1307,7 @@ int clm4_iht_v8_persistent(const int8_t *Phi, const float *sPhi, const int8_t *P
                            uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3, float *st3,
                            uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng, hipStream_t st)
 {
-    const int mode = [] { const char *e = getenv("CLV_IHT_PERSISTENT"); return e ? atoi(e) : 1; }();
+    const int mode = (int)clv_env_int("CLV_IHT_PERSISTENT", 1);
     if (!mode || threshold < 0 || threshold > 1 || !iterations || iterations >= 0x7FFFFFFFull) return 0;
     if (rng && (m + n) / 64 * 4 < 32) return 0;
     if (m > IHTP_MAXLEN || n > IHTP_MAXLEN || m % 128 || n % 128 || !m || !n) return 0;
@@ -1345,9 +1354,7 @@ int clm4_iht_v8_persistent(const int8_t *Phi, const float *sPhi, const int8_t *P
     a.g1 = (u64 *)ws; a.g2 = (u64 *)ws + m;
     a.nap0 = 16;         // best of 6 ... 26 for this kernel at N = 8192
     a.nap = 2;
-    if (const char *e = getenv("CLV_IHT_NAP0")) a.nap0 = (uint32_t)atoi(e);                             // probe only
-    a.dbg = nullptr;
-    if (const char *e = getenv("CLV_IHT_DEBUG_STAMPS")) a.dbg = (u64 *)strtoull(e, nullptr, 0);      // probe only: a device buffer of grid * 16 * 32 words
+    CLV_PROBE(ihtp_probe_overrides(a);)
     a.rng = rng;
     a.seq = 0;
     a.seg_rows = nullptr;

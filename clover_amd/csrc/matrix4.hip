@@ -232,7 +232,7 @@ __global__ __launch_bounds__(64 * L) void k_m4_mvm64(const uint8_t *__restrict__
 // ================================================================================================
 // quantize  (CloverMatrix4.h:512-766, rounding disabled)
 // ================================================================================================
-// k_m4_quantize_strip (the one in use): workgroup = 64 rows x 256 columns = 4 tiles side by side (256 threads, 64 floats each).  A wave-instruction reads
+// k_m4_quantize_strip: workgroup = 64 rows x 256 columns = 4 tiles side by side (256 threads, 64 floats each).  A wave-instruction reads
 // one contiguous KiB of a row (lane = float4); lanes 16t..16t+15 -- one DPP row -- belong to tile t, so the tile maximum
 // is a per-lane maximum over the wave's 16 rows, a row rotation reduce and a 4-wave combine in LDS.  A lane quantises
 // half a dword; lane pairs swap halves between two consecutive rows so that every lane stores a whole dword and a row
@@ -271,46 +271,6 @@ __global__ __launch_bounds__(256) void k_m4_quantize_strip(const float *__restri
         const uint32_t word = odd ? (recv | (h1 << 16)) : (h0 | (recv << 16));
         // even lanes hold the dword of row r, odd lanes that of row r+1; dword index inside the row = (col of the pair) / 8
         if (live) __builtin_nontemporal_store(word, &q[((row0 + r + odd) * cols + (col & ~7ull)) / 8]);
-    }
-}
-
-// k_m4_quantize (the first kernel of the round, kept behind CLV_M4Q_TILE=1 for A/B): workgroup = one 64x64 tile (256 threads);
-// thread = (row r = tid>>3 [+32 on the second pass], octet o = tid&7) holds 8 consecutive values = one output dword.  Pass 1
-// reduces the tile maximum (registers -> wave shuffle -> LDS); pass 2 quantises from the registers, nothing is re-read.
-__global__ __launch_bounds__(256) void k_m4_quantize(const float *__restrict__ A, uint64_t cols, uint32_t *__restrict__ q,
-                                                     float *__restrict__ s, uint32_t tiles_x)
-{
-    __shared__ float sh[4];
-    const uint32_t bj = blockIdx.x % tiles_x;
-    const uint64_t bi = blockIdx.x / tiles_x;
-    const int tid = threadIdx.x;
-    const int o = tid & 7;
-    const int r0 = tid >> 3;
-
-    float v[2][8];
-    float m = 0.0f;
-#pragma unroll
-    for (int p = 0; p < 2; p++) {
-        const uint64_t row = bi * 64 + r0 + 32 * p;
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(A + row * cols + bj * 64 + o * 8);
-        const f32x4 lo = __builtin_nontemporal_load(&src[0]);
-        const f32x4 hi = __builtin_nontemporal_load(&src[1]);
-        v[p][0] = lo.x; v[p][1] = lo.y; v[p][2] = lo.z; v[p][3] = lo.w;
-        v[p][4] = hi.x; v[p][5] = hi.y; v[p][6] = hi.z; v[p][7] = hi.w;
-#pragma unroll
-        for (int e = 0; e < 8; e++) m = fmaxf(m, __builtin_fabsf(v[p][e]));
-    }
-    m = wave_max(m);
-    if ((tid & 63) == 0) sh[tid >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-    m = fix_zero_max(m);
-    const float k = 7.0f / m;
-    if (tid == 0) s[bi * tiles_x + bj] = m;
-#pragma unroll
-    for (int p = 0; p < 2; p++) {
-        const uint64_t row = bi * 64 + r0 + 32 * p;
-        q[(row * cols + bj * 64) / 8 + o] = quant_pack8(v[p], k, nullptr);
     }
 }
 
@@ -566,16 +526,9 @@ extern "C" int clm4_quantize(const float *A, uint64_t rows, uint64_t cols, int8_
     const uint64_t tiles = (rows / 64) * (cols / 64);
     CLV_REQUIRE(tiles <= 0x7FFFFFFFull, "clm4_quantize: too many tiles");
     if (rng_state_dev) return clm4_quantize_stochastic(A, rows, cols, q, s, rng_state_dev, as_stream(stream));
-    static const bool tile_kernel = getenv("CLV_M4Q_TILE") != nullptr;       // A/B switch: the older one-tile-per-workgroup kernel
-    if (!tile_kernel) {
-        const uint32_t strips_x = (uint32_t)((cols + 255) / 256);
-        hipLaunchKernelGGL(k_m4_quantize_strip, dim3((unsigned)((rows / 64) * strips_x)), dim3(256), 0, as_stream(stream), A, cols,
-                           (uint32_t *)q, s, strips_x, (uint32_t)(cols / 64));
-        CLV_LAUNCH_CHECK();
-        return CLV_OK;
-    }
-    hipLaunchKernelGGL(k_m4_quantize, dim3((unsigned)tiles), dim3(256), 0, as_stream(stream), A, cols, (uint32_t *)q, s,
-                       (uint32_t)(cols / 64));
+    const uint32_t strips_x = (uint32_t)((cols + 255) / 256);
+    hipLaunchKernelGGL(k_m4_quantize_strip, dim3((unsigned)((rows / 64) * strips_x)), dim3(256), 0, as_stream(stream), A, cols,
+                       (uint32_t *)q, s, strips_x, (uint32_t)(cols / 64));
     CLV_LAUNCH_CHECK();
     return CLV_OK;
 }
@@ -588,7 +541,7 @@ extern "C" int clm4_gemm(const int8_t *A, const float *sA, uint64_t M, uint64_t 
                 (unsigned long long)M, (unsigned long long)N, (unsigned long long)K);
     if (!M || !N) return CLV_OK;
     // CLV_GEMM_KERNEL (A/B runs): "i8" = the int8 MFMA kernel of gemm4.hip, "simple" = the scalar check kernel
-    static const int which = [] { const char *e = getenv("CLV_GEMM_KERNEL"); return !e ? 0 : !strcmp(e, "simple") ? 2 : !strcmp(e, "i8") ? 1 : 0; }();
+    static const int which = [] { const char *e = clv_env("CLV_GEMM_KERNEL"); return !e ? 0 : !strcmp(e, "simple") ? 2 : !strcmp(e, "i8") ? 1 : 0; }();
     if (which == 0 && K > 0) return clm4_gemm_fp6(A, sA, M, K, B, sB, N, C, as_stream(stream));
     if (which == 1 && K > 0) return clm4_gemm_mfma(A, sA, M, K, B, sB, N, C, as_stream(stream));
     hipLaunchKernelGGL(k_m4_gemm_simple, dim3((unsigned)(N / 16), (unsigned)(M / 16)), dim3(256), 0, as_stream(stream),

@@ -746,7 +746,7 @@ extern "C" int clv8_scale_and_add(const int8_t *qu, const float *su, const int8_
     if (!n_pad) return CLV_OK;
     hipStream_t st = as_stream(stream);
     const uint64_t nb = n_pad / 64;
-    static const uint64_t blk_min = [] { const char *e = getenv("CLV_SAA8_BLK_MIN_BLOCKS"); return e ? strtoull(e, nullptr, 10) : (uint64_t)SAA8_BLK_MIN_BLOCKS; }();      // A/B runs
+    static const uint64_t blk_min = (uint64_t)clv_env_int("CLV_SAA8_BLK_MIN_BLOCKS", SAA8_BLK_MIN_BLOCKS);      // A/B runs
     if (!rng_state_dev && nb >= blk_min) {                                // once-per-block arithmetic (k_v8_scale_and_add_blk)
         const uint64_t want = (nb + 255) / 256, cap = (uint64_t)clv_cu_count() * 8;
         const dim3 grid((unsigned)(want < cap ? want : cap));

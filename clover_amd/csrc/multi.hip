@@ -210,7 +210,7 @@ extern "C" int clm4_sharded_create(clm4_shard_ctx **out, int ndev, const int *de
         }
     }
     c->equal = (rows / 64) % (uint64_t)ndev == 0;
-    const char *selftest = getenv("CLV_SHARDED_RCCL_SELFTEST");
+    const char *selftest = clv_env("CLV_SHARDED_RCCL_SELFTEST");
     c->use_rccl = !c->loopback && (ndev > 1 || (selftest && selftest[0] && selftest[0] != '0'));
     if (c->use_rccl && ndev == 1 && !strcmp(selftest, "ragged")) c->equal = false;
     if (rc == CLV_OK && c->use_rccl) {

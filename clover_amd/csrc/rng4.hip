@@ -180,63 +180,7 @@ __global__ __launch_bounds__(256) void k_v4_quantize_st(const f32x4 *__restrict_
 
 // ---- matrix quantize, stochastic (CloverMatrix4.h:512-766) ----------------------------------------------
 // stream order: tile t = bj * (rows/64) + bi (column-block outer), then the tile's 64 rows, two draws each.
-__global__ __launch_bounds__(256) void k_m4_quantize_st(const float *__restrict__ A, uint64_t cols, uint32_t *__restrict__ q,
-                                                        float *__restrict__ s, uint32_t tiles_x, uint64_t tiles_y, uint64_t *state,
-                                                        uint64_t seq, RngTables T)
-{
-    __shared__ __attribute__((aligned(16))) uint64_t raw[64 * 2 * 4];
-    __shared__ float sh[4];
-    __shared__ uint64_t base[4];
-    const uint32_t bj = blockIdx.x % tiles_x;
-    const uint64_t bi = blockIdx.x / tiles_x;
-    const uint64_t t = (uint64_t)bj * tiles_y + bi;                 // position of this tile in the stream
-    const int tid = threadIdx.x;
-    const int o = tid & 7;
-    const int r0 = tid >> 3;
-
-    SegRows<8> segs;
-    if (tid < 64) segs.load(T.seg_rows, 0);
-    rng_workgroup_begin(state, seq, T.pow_rows, t, 7, (uint64_t)tiles_x * tiles_y * 128, base);   // tile = 64 rows = 2^7 draws
-    if (tid < 64) {                                                  // wave 0: 8 segments x 4 generator lanes
-        const uint64_t a = segs.starts(base);
-        if (tid < 32) gen_blocks(a, 8, raw + (size_t)(8 * (tid >> 2)) * 8, tid & 3);
-    }
-
-    float v[2][8];
-    float m = 0.0f;
-#pragma unroll
-    for (int p = 0; p < 2; p++) {
-        const uint64_t row = bi * 64 + r0 + 32 * p;
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(A + row * cols + bj * 64 + o * 8);
-        const f32x4 lo = __builtin_nontemporal_load(&src[0]);
-        const f32x4 hi = __builtin_nontemporal_load(&src[1]);
-        v[p][0] = lo.x; v[p][1] = lo.y; v[p][2] = lo.z; v[p][3] = lo.w;
-        v[p][4] = hi.x; v[p][5] = hi.y; v[p][6] = hi.z; v[p][7] = hi.w;
-#pragma unroll
-        for (int e = 0; e < 8; e++) m = fmaxf(m, __builtin_fabsf(v[p][e]));
-    }
-    m = wave_max(m);
-    if ((tid & 63) == 0) sh[tid >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-    m = fix_zero_max(m);
-    const float kq = 7.0f / m;
-    if (tid == 0) s[bi * tiles_x + bj] = m;
-#pragma unroll
-    for (int p = 0; p < 2; p++) {
-        const int rl = r0 + 32 * p;                                  // tile row = stream block within the tile
-        const u32x4 *Wp = reinterpret_cast<const u32x4 *>(raw + (size_t)(rl * 2 + (o >> 2)) * 4);
-        const u32x4 W0 = Wp[0], W1 = Wp[1];
-        const uint32_t W[8] = {W0.x, W0.y, W0.z, W0.w, W1.x, W1.y, W1.z, W1.w};
-        float nz[8];
-#pragma unroll
-        for (int e = 0; e < 8; e++) nz[e] = noise_of(W[e], o & 3);
-        const uint64_t row = bi * 64 + rl;
-        q[(row * cols + bj * 64) / 8 + o] = quant_pack8(v[p], kq, nz);
-    }
-}
-
-// strip form of the same (see k_m4_quantize_strip, matrix4.hip): workgroup = 64 rows x 4 tiles side by side.  Wave w
+// strip form (as k_m4_quantize_strip, matrix4.hip): workgroup = 64 rows x 4 tiles side by side.  Wave w
 // generates the draws of tile bj = 4 sj + w -- stream position t = bj * tiles_y + bi, all four generator lanes -- and
 // every lane then reads the 16 bytes of noise words its four elements of a row need.
 //
@@ -320,7 +264,7 @@ __global__ __launch_bounds__(256) void k_m4_quantize_strip_st(const float *__res
 // segments (of 8 blocks) per wave for the vector kernels.  The choice never changes results, only speed;
 // clv_rng_set_segments (clover_hip.h: a tuning knob, and how the tests reach every kernel shape at small sizes) or
 // CLV_ST_SEGMENTS=1|4|16|64 force one shape.
-static int g_st_forced = [] { const char *e = getenv("CLV_ST_SEGMENTS"); return e ? atoi(e) : 0; }();
+static int g_st_forced = 0;
 
 extern "C" int clv_rng_set_segments(int s)
 {
@@ -333,7 +277,7 @@ extern "C" int clv_rng_set_segments(int s)
 // quantize kernels stream 8x the bytes per element and lose 15 % with it (more rounds, each with its barrier)
 int clv_st_segments(uint64_t nblocks, bool long_ok)
 {
-    static const int env_forced = [] { const char *e = getenv("CLV_ST_SEGMENTS"); return e ? atoi(e) : 0; }();      // A/B runs
+    static const int env_forced = (int)clv_env_int("CLV_ST_SEGMENTS", 0);      // A/B runs; it wins over clv_rng_set_segments
     if (env_forced == 1 || env_forced == 4 || env_forced == 16 || env_forced == 64) return env_forced;
     if (g_st_forced == 1 || g_st_forced == 4 || g_st_forced == 16 || g_st_forced == 64) return g_st_forced;
     return nblocks <= 8192 ? 1 : nblocks <= (1u << 18) ? 4 : (nblocks <= (1u << 21) || !long_ok) ? 16 : 64;
@@ -365,22 +309,13 @@ int clm4_quantize_stochastic(const float *A, uint64_t rows, uint64_t cols, int8_
     RngTables T;
     int rc = clv_rng_tables(&T);
     if (rc) return rc;
-    const uint64_t tiles = (rows / 64) * (cols / 64);
-    static const bool tile_kernel = getenv("CLV_M4Q_TILE") != nullptr;       // A/B switch: the older one-tile-per-workgroup kernel
-    if (!tile_kernel) {
-        const uint32_t strips_x = (uint32_t)((cols + 255) / 256);
-        static const bool one_tile = getenv("CLV_M4Q_NV1") != nullptr;       // A/B switch: one tile row per workgroup
-        if (one_tile || rows / 64 < 2)
-            hipLaunchKernelGGL(k_m4_quantize_strip_st<1>, dim3((unsigned)((rows / 64) * strips_x)), dim3(256), 0, st, A, cols, (uint32_t *)q, s,
-                               strips_x, (uint32_t)(cols / 64), rows / 64, rng, clv_rng_seq_for(rng, st), T);
-        else
-            hipLaunchKernelGGL(k_m4_quantize_strip_st<2>, dim3((unsigned)(((rows / 64 + 1) / 2) * strips_x)), dim3(256), 0, st, A, cols, (uint32_t *)q,
-                               s, strips_x, (uint32_t)(cols / 64), rows / 64, rng, clv_rng_seq_for(rng, st), T);
-        CLV_LAUNCH_CHECK();
-        return CLV_OK;
-    }
-    hipLaunchKernelGGL(k_m4_quantize_st, dim3((unsigned)tiles), dim3(256), 0, st, A, cols, (uint32_t *)q, s, (uint32_t)(cols / 64),
-                       rows / 64, rng, clv_rng_seq_for(rng, st), T);
+    const uint32_t strips_x = (uint32_t)((cols + 255) / 256);
+    if (rows / 64 < 2)
+        hipLaunchKernelGGL(k_m4_quantize_strip_st<1>, dim3((unsigned)((rows / 64) * strips_x)), dim3(256), 0, st, A, cols, (uint32_t *)q, s,
+                           strips_x, (uint32_t)(cols / 64), rows / 64, rng, clv_rng_seq_for(rng, st), T);
+    else
+        hipLaunchKernelGGL(k_m4_quantize_strip_st<2>, dim3((unsigned)(((rows / 64 + 1) / 2) * strips_x)), dim3(256), 0, st, A, cols, (uint32_t *)q,
+                           s, strips_x, (uint32_t)(cols / 64), rows / 64, rng, clv_rng_seq_for(rng, st), T);
     CLV_LAUNCH_CHECK();
     return CLV_OK;
 }

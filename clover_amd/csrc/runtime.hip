@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include <stdarg.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <mutex>
@@ -74,6 +75,13 @@ int clv_cu_count()
         g_cu[dev] = n;
     }
     return g_cu[dev];
+}
+
+const char *clv_env(const char *name) { return getenv(name); }
+long long clv_env_int(const char *name, long long dflt)
+{
+    const char *e = clv_env(name);
+    return e ? strtoll(e, nullptr, 10) : dflt;
 }
 
 // Grow-only scratch, one buffer per (device, stream): used when a caller passes workspace == NULL (clv4_dot, threshold) and by

@@ -986,9 +986,10 @@ template <bool REG>
 __global__ __launch_bounds__(1024) void k_th4_select_persist(const unsigned long long *__restrict__ cnt, const float *__restrict__ s, uint64_t nblocks,
                                                              uint32_t *__restrict__ ctl, uint32_t k, ThreshState *__restrict__ ts,
                                                              uint32_t *__restrict__ chunk_ties, uint32_t *__restrict__ group_ties, uint32_t nchunks,
-                                                             uint32_t cpg, uint32_t *__restrict__ cand, unsigned long long *dbg)
+                                                             uint32_t cpg, uint32_t *__restrict__ cand
+                                                             CLV_PROBE(, unsigned long long *dbg))
 {
-#define TH4_STAMP(i) do { if (dbg && threadIdx.x == 0) dbg[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define TH4_STAMP(i) CLV_PROBE(do { if (dbg && threadIdx.x == 0) dbg[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0))
     TH4_STAMP(0);
     __shared__ __attribute__((aligned(16))) uint32_t lh[4096];
     __shared__ uint32_t tot[TH4_P_MAX_CPG];
@@ -1295,7 +1296,7 @@ static int threshold4_large(uint32_t *q, const float *s, uint64_t n, uint64_t n_
     uint32_t *chunk_ties = group_ties + TH4_GROUPS;
     unsigned long long *cnt = (unsigned long long *)((char *)chunk_ties + (((uint64_t)(n_pad / 64 / 256 + 1) * 4 + 255) & ~255ull));
     // the three-launch form (round 6): k != 0, a zeroed control block on this stream, at most TH4_P_MAX_CPG chunks per CU
-    const int three = [] { const char *e = getenv("CLV_THRESHOLD_THREE_LAUNCH"); return e ? atoi(e) : 1; }();      // read per call: A/B runs flip it
+    const int three = (int)clv_env_int("CLV_THRESHOLD_THREE_LAUNCH", 1);      // read per call: A/B runs flip it
     if (three && k != 0) {
         const uint32_t cus = (uint32_t)clv_cu_count();
         const uint32_t grid2 = nchunks < cus ? nchunks : cus, cpg2 = (nchunks + grid2 - 1) / grid2, groups2 = (nchunks + cpg2 - 1) / cpg2;
@@ -1310,15 +1311,17 @@ static int threshold4_large(uint32_t *q, const float *s, uint64_t n, uint64_t n_
                 (void)hipMemsetAsync(ctl, 0, TH4_CTL_WORDS * sizeof(uint32_t), st);
                 return rc;
             }
-            const bool in_regs = cpg2 <= 64 && !getenv("CLV_THRESHOLD_FORCE_CAND");      // (the variable: tests run the other form at small sizes)
-            unsigned long long *dbg = nullptr;
-            if (const char *e = getenv("CLV_THRESHOLD_DEBUG_STAMPS")) dbg = (unsigned long long *)strtoull(e, nullptr, 0);   // probe only: groups x 16 words
+            const bool in_regs = cpg2 <= 64 && !clv_env("CLV_THRESHOLD_FORCE_CAND");      // (the variable: tests run the other form at small sizes)
+#ifdef CLV_EXPERIMENTS
+            const char *dbg_env = clv_env("CLV_THRESHOLD_DEBUG_STAMPS");      // probe build: a device buffer of groups x 16 words
+            unsigned long long *dbg = dbg_env ? (unsigned long long *)strtoull(dbg_env, nullptr, 0) : nullptr;
+#endif
             if (in_regs)
                 hipLaunchKernelGGL(k_th4_select_persist<true>, dim3(groups2), dim3(1024), 0, st, cnt, s, nblocks, ctl, (uint32_t)k, ts, chunk_ties,
-                                   group_ties, nchunks, cpg2, cand, dbg);
+                                   group_ties, nchunks, cpg2, cand CLV_PROBE(, dbg));
             else
                 hipLaunchKernelGGL(k_th4_select_persist<false>, dim3(groups2), dim3(1024), 0, st, cnt, s, nblocks, ctl, (uint32_t)k, ts, chunk_ties,
-                                   group_ties, nchunks, cpg2, cand, dbg);
+                                   group_ties, nchunks, cpg2, cand CLV_PROBE(, dbg));
             clv_internal_persist_leave();
             hipLaunchKernelGGL(k_th4_apply3, dim3(nchunks), dim3(256), 0, st, (u32x4 *)q, s, n, nblocks, ts, chunk_ties, group_ties, cpg2, ctl,
                                TH4_CTL_WORDS);

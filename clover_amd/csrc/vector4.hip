@@ -375,7 +375,7 @@ extern "C" int clv4_dot(const int8_t *qu, const float *su, const int8_t *qv, con
     hipStream_t st = as_stream(stream);
     if (!n_pad) { CLV_HIP(hipMemsetAsync(out_dev, 0, sizeof(float), st)); return CLV_OK; }
     const int grid = dot_fast_grid(n_pad);
-    static const bool two_launches = getenv("CLV_DOT_FAST_TWO_LAUNCHES") != nullptr;      // A/B switch: the round-1..4 form (same bits)
+    static const bool two_launches = clv_env("CLV_DOT_FAST_TWO_LAUNCHES") != nullptr;      // A/B switch: the round-1..4 form (same bits)
     const bool needs_scratch = mode == CLV_DOT_EXACT || two_launches || grid > DOT_FAST_THREADS * DOT_MAX_SLOTS_PER_THREAD;
     if (!workspace && needs_scratch) {
         int rc = clv_internal_workspace(&workspace, clv4_dot_workspace_bytes(n_pad), as_stream(stream));
@@ -404,16 +404,13 @@ extern "C" int clv4_dot(const int8_t *qu, const float *su, const int8_t *qv, con
     int rc = clv_internal_sync_slots(&slots, (uint64_t)grid * 8, st);
     if (rc) return rc;
     const uint64_t nvec = n_pad / 32, per_thread = (nvec + (uint64_t)grid * DOT_FAST_THREADS - 1) / ((uint64_t)grid * DOT_FAST_THREADS);
-    static const int force_u = [] { const char *e = getenv("CLV_DOT_FAST_U"); return e ? atoi(e) : 0; }();      // A/B switch
     // loads in flight per thread, measured on one box (profiles/r05_dot_fast_ab.jsonl, us at n = 2^24 / 2^26 / 2^29 / 2^30): U = 1: 4.19 / 11.6 /
     // 88.7 / 174.0, U = 2: 4.02 / 12.2 / 92.5 / 189.3, U = 4: 5.05 / 12.3 / 120.0 / 217.1 (two launches: 6.38 / 14.7 / 91.0 / 181.7) -- deeper
     // only pays where a thread has two steps in all (one round trip instead of two); long vectors want the plain loop
-    const int u = force_u ? force_u : per_thread <= 2 ? 2 : 1;
 #define DOT1_LAUNCH(U)                                                                                                                      \
     hipLaunchKernelGGL(k_v4_dot_fast1<U>, dim3(grid), dim3(DOT_FAST_THREADS), 0, st, (const u32x4 *)qu, su, (const u32x4 *)qv, sv, nvec, \
                        (unsigned long long *)slots, out_dev)
-    if (u >= 4) DOT1_LAUNCH(4);
-    else if (u == 2) DOT1_LAUNCH(2);
+    if (per_thread <= 2) DOT1_LAUNCH(2);
     else DOT1_LAUNCH(1);
 #undef DOT1_LAUNCH
     CLV_LAUNCH_CHECK();

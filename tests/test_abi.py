@@ -49,6 +49,18 @@ def test_probe_build_is_not_beside_the_product_and_is_refused():
     assert load_library().clv_version().decode().startswith("clover_hip 0.")
 
 
+def test_probe_switches_are_not_in_the_product():
+    """the stamp buffers (device addresses read from the environment), the spin-wait overrides and the retired kernel variants' switches
+    exist only in the probe build"""
+    from clover_amd.build import build_probe_library
+    product = build_hip_library().read_bytes()
+    for name in (b"CLV_IHT_DEBUG_STAMPS", b"CLV_THRESHOLD_DEBUG_STAMPS", b"CLV_IHT_NAP", b"CLV_M4Q_TILE", b"CLV_M4Q_NV1", b"CLV_DOT_FAST_U"):
+        assert name not in product, name
+    probe = build_probe_library().read_bytes()
+    for name in (b"CLV_IHT_DEBUG_STAMPS", b"CLV_THRESHOLD_DEBUG_STAMPS"):
+        assert name in probe, name
+
+
 def test_error_codes_without_compute():
     lib = load_library()
     # argument validation happens before any device work: callable on a CPU-only box

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""clv4_dot FAST at the reference's published sizes (n = 2^24, 2^26, 2^29) and 2^30: ms per call, warm (same operands) -- run once per setting of
-CLV_DOT_FAST_U / CLV_DOT_FAST_TWO_LAUNCHES (read once per process)."""
+"""clv4_dot FAST at the reference's published sizes (n = 2^24, 2^26, 2^29) and 2^30: ms per call, warm (same operands) -- run once with and once
+without CLV_DOT_FAST_TWO_LAUNCHES (read once per process)."""
 import ctypes as C
 import json
 import os
@@ -13,7 +13,7 @@ from clover_amd.lib_binding import DOT_FAST, CloverHip  # noqa: E402
 hip = CloverHip(path=os.environ.get("CLV_LIB"))
 lib = hip.lib
 vp = C.c_void_p
-res = {"CLV_DOT_FAST_U": os.environ.get("CLV_DOT_FAST_U"), "two_launches": os.environ.get("CLV_DOT_FAST_TWO_LAUNCHES")}
+res = {"two_launches": os.environ.get("CLV_DOT_FAST_TWO_LAUNCHES")}
 out = hip.alloc(8)
 for logn in (24, 26, 29, 30):
     n = 1 << logn

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Persistent IHT kernel (iht_persist.hip) against the launch-per-step loop (iht4.hip): same inputs, every output bit for bit, then timing.
-Usage: iht_persist_probe.py [check] [time] [N ...]"""
+Usage: iht_persist_probe.py [check] [time] [N ...]; the phase-stamp modes (stamps, stamps8) run on the probe build, everything else on the
+product library or CLV_LIB"""
 import os
 import sys
 import time
@@ -9,10 +10,18 @@ from pathlib import Path
 import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from clover_amd.build import probe_library_path  # noqa: E402
 from clover_amd.lib_binding import CloverHip  # noqa: E402
 
 hip = CloverHip(path=os.environ.get("CLV_LIB"))      # CLV_LIB: another build of the library, for same-box A/B runs
 lib = hip.lib
+
+
+def use_probe_library():
+    """CLV_IHT_DEBUG_STAMPS is read only by the probe build (clover_amd/build.py build_probe_library)"""
+    global hip, lib
+    hip = CloverHip(path=probe_library_path(), allow_probe=True)
+    lib = hip.lib
 
 
 def problem(m, n, seed):
@@ -277,6 +286,13 @@ if __name__ == "__main__":
         timing8([int(a) for a in args if a.isdigit()] or [256, 4096, 8192], seed=(5, 6))
     if "check_st" in args:
         rc = check(seed=(12345, 67890))
+    if not args or "time" in args:
+        Ns = [int(a) for a in args if a.isdigit()] or [256, 1024, 2048, 4096, 8192]
+        timing(Ns)
+    if "time_st" in args:
+        timing([int(a) for a in args if a.isdigit()] or [256, 4096, 8192], seed=(5, 6))
+    if "stamps" in args or "stamps8" in args:
+        use_probe_library()
     if "stamps8" in args:
         for N in [int(a) for a in args if a.isdigit()] or [8192]:
             stamps8(N, 1)
@@ -286,9 +302,4 @@ if __name__ == "__main__":
         for N in [int(a) for a in args if a.isdigit()] or [256, 8192]:
             stamps(N, 1)
             stamps(N, 0)
-    if not args or "time" in args:
-        Ns = [int(a) for a in args if a.isdigit()] or [256, 1024, 2048, 4096, 8192]
-        timing(Ns)
-    if "time_st" in args:
-        timing([int(a) for a in args if a.isdigit()] or [256, 4096, 8192], seed=(5, 6))
     sys.exit(1 if rc else 0)

@@ -3,7 +3,8 @@
 (CLV_THRESHOLD_THREE_LAUNCH=0, read per call) on the same inputs, and both timed.
 
     python tools/thresh3_probe.py check            random sizes / data kinds, bit-exact comparison
-    python tools/thresh3_probe.py time [logn ...]  us per call (k = n / 4), back-to-back calls on one stream"""
+    python tools/thresh3_probe.py time [logn ...]  us per call (k = n / 4), back-to-back calls on one stream
+    python tools/thresh3_probe.py stamps [logn ...]  phase stamps of k_th4_select_persist (the probe build)"""
 import os
 import sys
 import time
@@ -12,6 +13,7 @@ from pathlib import Path
 import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from clover_amd.build import probe_library_path  # noqa: E402
 from clover_amd.lib_binding import CloverHip  # noqa: E402
 
 hip = CloverHip(path=os.environ.get("CLV_LIB"))      # CLV_LIB: another build of the library, for same-box A/B runs
@@ -92,7 +94,9 @@ def timing(logns):
 
 
 def stamps(logn):
-    """phase stamps of k_th4_select_persist (100 MHz wall clock), one call"""
+    """phase stamps of k_th4_select_persist (100 MHz wall clock), one call; CLV_THRESHOLD_DEBUG_STAMPS is read only by the probe build"""
+    hip = CloverHip(path=probe_library_path(), allow_probe=True)
+    lib = hip.lib
     n = 1 << logn
     q, s = hip.alloc(n // 2), hip.alloc(n // 16)
     hip.check(lib.clv_fill_random_scales(s.ptr, n // 64, 8, 0, None))
