@@ -89,6 +89,11 @@ SIGNATURES = {
     "clv8_threshold_heap": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp]),
     "clm4_transpose": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "clm4_mvm_f32": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm8_quantize": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "clm8_restore": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp]),
+    "clm8_mvm": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm8_mvm_f32": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm8_transpose": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "clm4_iht": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
                           C.c_float, C.c_int, _vp, _vp]),
     "clm4_shard_partition": (C.c_int, [_u64, C.c_int, C.c_int, C.POINTER(_u64), C.POINTER(_u64)]),
@@ -362,6 +367,38 @@ class CloverHip:
         d = self.alloc(max(rows * 4, 4))
         self.check(self.lib.clm4_mvm_f32(b[0].ptr, b[1].ptr, rows, cols, b[2].ptr, d.ptr, None))
         return d.download(np.float32, rows)
+
+    # -- CloverMatrix8 ---------------------------------------------------------------------------
+    def m8_quantize(self, A: np.ndarray, rng: DevBuf | None = None):
+        A = np.ascontiguousarray(A, dtype=np.float32)
+        rows, cols = A.shape
+        dA = self.to_device(A)
+        dq, ds = self.alloc(max(rows * cols, 1)), self.alloc(max((rows // 64) * (cols // 64) * 4, 4))
+        self.check(self.lib.clm8_quantize(dA.ptr, rows, cols, dq.ptr, ds.ptr, rng.ptr if rng else None, None))
+        return dq.download(np.int8, rows * cols), ds.download(np.float32, (rows // 64) * (cols // 64))
+
+    def m8_restore(self, q, s, rows, cols) -> np.ndarray:
+        dq, ds, dA = self.to_device(q), self.to_device(s), self.alloc(max(4 * rows * cols, 4))
+        self.check(self.lib.clm8_restore(dq.ptr, ds.ptr, rows, cols, dA.ptr, None))
+        return dA.download(np.float32, rows * cols).reshape(rows, cols)
+
+    def m8_mvm(self, qA, sA, rows, cols, qx, sx, rng: DevBuf | None = None):
+        b = [self.to_device(a) for a in (qA, sA, qx, sx)]
+        dr, dsr = self.alloc(max(rows, 1)), self.alloc(max(rows // 16, 4))
+        self.check(self.lib.clm8_mvm(b[0].ptr, b[1].ptr, rows, cols, b[2].ptr, b[3].ptr, dr.ptr, dsr.ptr, rng.ptr if rng else None, None))
+        return dr.download(np.int8, rows), dsr.download(np.float32, rows // 64)
+
+    def m8_mvm_f32(self, qA, sA, rows, cols, x) -> np.ndarray:
+        b = [self.to_device(a) for a in (qA, sA, np.ascontiguousarray(x, dtype=np.float32))]
+        d = self.alloc(max(rows * 4, 4))
+        self.check(self.lib.clm8_mvm_f32(b[0].ptr, b[1].ptr, rows, cols, b[2].ptr, d.ptr, None))
+        return d.download(np.float32, rows)
+
+    def m8_transpose(self, q, s, rows, cols):
+        dq, ds = self.to_device(q), self.to_device(s)
+        dt, dst = self.alloc(max(rows * cols, 1)), self.alloc(max((rows // 64) * (cols // 64) * 4, 4))
+        self.check(self.lib.clm8_transpose(dq.ptr, ds.ptr, rows, cols, dt.ptr, dst.ptr, None))
+        return dt.download(np.int8, rows * cols), dst.download(np.float32, (rows // 64) * (cols // 64))
 
     def m4_gemm_i32(self, qA, M, K, qB, N, kb_begin=0, kb_count=None) -> np.ndarray:
         b = [self.to_device(a) for a in (qA, qB)]

@@ -12,6 +12,7 @@
 #define CLOVER_IHT_H
 
 #include "CloverMatrix4.h"
+#include "CloverMatrix8.h"       /* Q_IHT<CloverMatrix8, CloverVector8> / Q_GD<...>: the generic templates below */
 #include "CloverVector4.h"
 
 /* Generic forms, for any container pair with the reference's method names (the five steps of 01_measure.h:930-944):

@@ -1,0 +1,242 @@
+/*
+ * CloverMatrix8.h -- 8-bit quantized matrix, MI355X-backed.
+ *
+ * Drop-in for the reference's include/CloverMatrix8.h: same class name, constructor, method names and data format (row-major int8
+ * values followed by a row-major grid of fp32 scales, one per 64x64 tile, value = q * scale / 127; rows/cols padded to multiples of
+ * 128; :36-90).  Hot methods call libclover_hip.so:
+ *
+ *   quantize / quantize_parallel       -> clm8_quantize   (CloverMatrix8.h:203-480)
+ *   restore                            -> clm8_restore    (get, :117-131; the reference has only restore_scalar, :1300-1309)
+ *   mvm / mvm_parallel (CloverVector8) -> clm8_mvm        (:1002-1299, :664-998)
+ *   mvm / mvm_parallel (CloverVector32)-> clm8_mvm_f32    (:558-662)
+ *   transpose / transpose_parallel     -> clm8_transpose  (:1312-1386)
+ *   *_scalar                           -> scalar HOST code, the reference's validation partners: quantize_scalar (:144-201),
+ *                                         restore_scalar, mvm_scalar (:480-556: row views + CloverVector8::dot, then the scalar
+ *                                         quantiser; for fp32 vectors a double accumulation), transpose_scalar (:1312-1340).  With
+ *                                         rounding disabled mvm == mvm_parallel == mvm_scalar bit for bit, as in the reference.
+ *
+ * Q_IHT<CloverMatrix8, CloverVector8> and Q_GD<...> are the generic templates of CloverIHT.h (which includes this header): every step is
+ * a kernel on the device mirrors, nothing is copied back between steps.
+ */
+#ifndef CLOVER_MATRIX8_H
+#define CLOVER_MATRIX8_H
+
+#include <cmath>
+#include <iomanip>
+#include <sstream>
+#include <string>
+
+#include "CloverMatrix32.h"
+#include "CloverVector32.h"
+#include "CloverVector8.h"
+
+class CloverMatrix8 {
+protected:
+    const uint64_t rows;
+    const uint64_t cols;
+    mutable clover_hip::Mirror mem;            /* [rows*cols value bytes][(rows/64)*(cols/64) scales] */
+    mutable clover_hip::RandomState random;
+    uint64_t value_bytes;
+
+    const int8_t *dev_values() const { return reinterpret_cast<const int8_t *>(mem.dev_ro()); }
+    const float *dev_scales() const { return reinterpret_cast<const float *>(mem.dev_ro() + value_bytes); }
+
+    void check_same_size(const CloverMatrix32 &m) const
+    {
+        if (m.getRows() != rows || m.getCols() != cols) {
+            std::cout << "Matrices do not have the same size. Exiting ..." << std::endl;
+            exit(1);
+        }
+    }
+    template <class V, class R>
+    void check_mvm(const V &productVector, const R &resultVector) const
+    {
+        if (productVector.size() != getCols() || resultVector.size_pad() != getRows()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+    }
+    void check_transpose(const CloverMatrix8 &other) const
+    {
+        if (other.rows != cols || other.cols != rows) {
+            std::cout << "Matrix can not be transposed. Exiting ..." << std::endl;
+            exit(1);
+        }
+    }
+
+public:
+    CloverMatrix8(uint64_t h, uint64_t w)
+        : rows(clover_hip::round_up(h, CLOVER_VECTOR_SIZE_PAD)), cols(clover_hip::round_up(w, CLOVER_VECTOR_SIZE_PAD))
+    {
+        value_bytes = rows * cols;
+        mem.allocate(value_bytes + (rows >> 6) * (cols >> 6) * sizeof(float));
+    }
+
+    uint64_t getRows() const { return rows; }
+    uint64_t getCols() const { return cols; }
+    uint64_t size() const { return rows * cols; }
+    uint64_t getBitsLength() const { return 8; }
+    uint64_t getBytes() const { return value_bytes + (rows >> 6) * (cols >> 6) * sizeof(float); }
+
+    /* explicit residency, as CloverMatrix4 (clover_device.h, -DCLOVER_HIP_EXPLICIT_SYNC) */
+    void toDevice() const { (void)mem.dev_ro(); }
+    void toHost() const { (void)mem.host_ro(); }
+    /* host views of the values and of the tile scales (protected in the reference; exposed for interop) */
+    int8_t *getData() const { return reinterpret_cast<int8_t *>(mem.host_ptr()); }
+    float *getScales() const { return reinterpret_cast<float *>(mem.host_ptr() + value_bytes); }
+
+    /* :117-131 */
+    float get(uint64_t i, uint64_t j) const
+    {
+        const uint8_t *h = mem.host_ro();
+        const float *s = reinterpret_cast<const float *>(h + value_bytes);
+        const float scale = s[(i >> 6) * (cols >> 6) + (j >> 6)] / 127.0f;
+        return scale * (float)(int8_t)h[i * cols + j];
+    }
+
+    /* :1388-1411: the restored elements row by row, then the grid of tile scales */
+    std::string toString() const
+    {
+        const uint8_t *h = mem.host_ro();
+        const float *s = reinterpret_cast<const float *>(h + value_bytes);
+        const uint64_t v_blocks = rows >> 6, h_blocks = cols >> 6;
+        std::stringstream sout;
+        for (uint64_t i = 0; i < rows; i++) {
+            for (uint64_t j = 0; j < cols; j++) sout << std::setw(7) << std::fixed << std::setprecision(2) << get(i, j) << " ";
+            sout << ";" << std::endl;
+        }
+        for (uint64_t i = 0; i < v_blocks; i++) {
+            for (uint64_t j = 0; j < h_blocks; j++) sout << std::setw(7) << std::fixed << std::setprecision(2) << s[i * h_blocks + j] << " ";
+            sout << ";" << std::endl;
+        }
+        return sout.str();
+    }
+
+    void setRandomKeys(const uint64_t key1[4], const uint64_t key2[4]) { random.set(key1, key2); }
+#ifdef CLOVER_HIP_M256_KEYS
+    void setRandomKeys(__m256i key1, __m256i key2) { clover_hip::set_keys_m256(random, key1, key2); }   /* CloverRandom.h:90-94 */
+#endif
+    void seedRandomKeys(uint64_t key1, uint64_t key2) { random.seed(key1, key2); }
+
+    void quantize(const CloverMatrix32 &m)
+    {
+        check_same_size(m);
+        uint8_t *d = mem.dev_wo();
+        clover_hip::check(clm8_quantize(m.device_ro(), rows, cols, reinterpret_cast<int8_t *>(d), reinterpret_cast<float *>(d + value_bytes),
+                                        clover_hip::rng_or_null(random), nullptr), "CloverMatrix8::quantize");
+    }
+    void quantize_parallel(const CloverMatrix32 &m) { quantize(m); }
+    /* the reference's scalar twin (:144-201), on the host: tiles column-block outer, maximum over the 64 x 64 tile */
+    void quantize_scalar(const CloverMatrix32 &m)
+    {
+        check_same_size(m);
+        const float *u = m.host_ro();
+        uint8_t *h = mem.host_rw();
+        int8_t *r = reinterpret_cast<int8_t *>(h);
+        float *sr = reinterpret_cast<float *>(h + value_bytes);
+        const uint64_t hb = cols >> 6, vb = rows >> 6;
+        for (uint64_t bj = 0; bj < hb; bj++)
+            for (uint64_t bi = 0; bi < vb; bi++) {
+                const uint64_t off = (bi << 6) * cols + (bj << 6);
+                float mx = 0.0f;
+                for (uint64_t i = 0; i < 64; i++)
+                    for (uint64_t j = 0; j < 64; j++) { const float a = std::fabs(u[off + i * cols + j]); if (a > mx) mx = a; }
+                if (mx == 0.0f) mx = 1.0f;                         /* the SIMD contract (:262-270); the scalar code divides by zero */
+                sr[bi * hb + bj] = mx;
+                const float k = 127.0f / mx;
+                for (uint64_t i = 0; i < 64; i++)
+                    for (uint64_t j = 0; j < 64; j++) {
+                        const float x = u[off + i * cols + j];
+                        const float mag = std::floor(std::fma(std::fabs(x), k, clover_hip::scalar::noise()));
+                        r[off + i * cols + j] = (int8_t)(std::signbit(x) ? -(int)mag : (int)mag);
+                    }
+            }
+    }
+
+    void restore(CloverMatrix32 &other) const
+    {
+        check_same_size(other);
+        clover_hip::check(clm8_restore(dev_values(), dev_scales(), rows, cols, other.device_wo(), nullptr), "CloverMatrix8::restore");
+    }
+    void restore_scalar(CloverMatrix32 &other) const
+    {
+        check_same_size(other);
+        float *out = other.host_rw();
+        for (uint64_t i = 0; i < rows; i++)
+            for (uint64_t j = 0; j < cols; j++) out[i * cols + j] = get(i, j);
+    }
+
+    /* 8-bit vector in, 8-bit vector out */
+    void mvm(const CloverVector8 &productVector, CloverVector8 &resultVector)
+    {
+        check_mvm(productVector, resultVector);
+        clover_hip::check(clm8_mvm(dev_values(), dev_scales(), rows, cols, productVector.dev_values_ro(), productVector.dev_scales_ro(),
+                                   resultVector.dev_values_wo(), resultVector.dev_scales_wo(), clover_hip::rng_or_null(random), nullptr),
+                          "CloverMatrix8::mvm");
+        resultVector.commit();
+    }
+    void mvm_parallel(const CloverVector8 &productVector, CloverVector8 &resultVector) { mvm(productVector, resultVector); }
+    /* :480-548: every row wrapped in a non-owning CloverVector8 view over the matrix's own memory and multiplied with dot() (the
+     * reference's order), then 64 results at a time quantised by scalar code -- an implementation independent of the mvm kernel */
+    void mvm_scalar(const CloverVector8 &productVector, CloverVector8 &resultVector)
+    {
+        check_mvm(productVector, resultVector);
+        int8_t *vals = getData();
+        float *scs = getScales();
+        int8_t *r = resultVector.getData();
+        float *sr = resultVector.getScales();
+        const uint64_t hb = cols >> 6;
+        for (uint64_t bi = 0; bi < (rows >> 6); bi++) {
+            float block[64];
+            for (uint64_t i = 0; i < 64; i++) {
+                CloverVector8 rowVector(cols, vals + ((bi << 6) + i) * cols, scs + bi * hb);
+                block[i] = rowVector.dot(productVector);
+            }
+            sr[bi] = clover_hip::scalar::quantize_block8(block, r + 64 * bi);
+        }
+    }
+
+    /* fp32 vector in, fp32 vector out */
+    void mvm(const CloverVector32 &productVector, CloverVector32 &resultVector)
+    {
+        check_mvm(productVector, resultVector);
+        clover_hip::check(clm8_mvm_f32(dev_values(), dev_scales(), rows, cols, productVector.device_ro(), resultVector.device_wo(), nullptr),
+                          "CloverMatrix8::mvm");
+        resultVector.commit();
+    }
+    void mvm_parallel(const CloverVector32 &productVector, CloverVector32 &resultVector) { mvm(productVector, resultVector); }
+    /* :550-556: double accumulation on the host */
+    void mvm_scalar(const CloverVector32 &productVector, CloverVector32 &resultVector)
+    {
+        check_mvm(productVector, resultVector);
+        for (uint64_t i = 0; i < rows; i++) {
+            double sum = 0;
+            for (uint64_t j = 0; j < cols; j++) sum += (double)get(i, j) * (double)productVector.get(j);
+            resultVector.set(i, (float)sum);
+        }
+    }
+
+    /* other = this^T, values and tile scales */
+    void transpose(CloverMatrix8 &other) const
+    {
+        check_transpose(other);
+        uint8_t *d = other.mem.dev_wo();
+        clover_hip::check(clm8_transpose(dev_values(), dev_scales(), rows, cols, reinterpret_cast<int8_t *>(d),
+                                         reinterpret_cast<float *>(d + other.value_bytes), nullptr), "CloverMatrix8::transpose");
+    }
+    void transpose_parallel(CloverMatrix8 &other) const { transpose(other); }
+    void transpose_scalar(CloverMatrix8 &other) const
+    {
+        check_transpose(other);
+        const uint8_t *h = mem.host_ro();
+        uint8_t *o = other.mem.host_rw();
+        const float *s = reinterpret_cast<const float *>(h + value_bytes);
+        float *so = reinterpret_cast<float *>(o + other.value_bytes);
+        for (uint64_t i = 0; i < rows; i++)
+            for (uint64_t j = 0; j < cols; j++) o[j * rows + i] = h[i * cols + j];
+        for (uint64_t bi = 0; bi < (rows >> 6); bi++)
+            for (uint64_t bj = 0; bj < (cols >> 6); bj++) so[bj * (rows >> 6) + bi] = s[bi * (cols >> 6) + bj];
+    }
+};
+
+#endif

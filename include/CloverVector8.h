@@ -15,7 +15,7 @@
  *
  * on the device: what Q_IHT / Q_GD need when they run with a CloverMatrix4 and CloverVector8 vectors, the configuration the
  * reference publishes as "4-bit" (test/performance/02_bit04.cpp:140), and with round 5 every method of the reference's class.
- * CloverMatrix8 belongs to the 8-bit containers' own path and is not part of this backend.
+ * CloverMatrix8 (include/CloverMatrix8.h) takes these vectors in its mvm; Q_IHT<CloverMatrix8, CloverVector8> runs on the device.
  */
 #ifndef CLOVER_VECTOR8_H
 #define CLOVER_VECTOR8_H

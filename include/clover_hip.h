@@ -26,7 +26,8 @@
  *    (rng == NULL); with an rng state the same XORShift stream as the reference's sequential methods is
  *    consumed (bit-identical nibbles for identical keys).  Exceptions are spelled out per function.
  *  - STOCHASTIC CALLS (any function given a non-NULL rng_state_dev: clv4_quantize, clm4_quantize, clm4_mvm, clv4_scale_and_add,
- *    clm4_mvm_scale_and_add, clv8_quantize, clv8_scale_and_add, clm4_mvm_v8, clm4_mvm_v8_scale_and_add, clm4_iht, clm4_iht_v8):
+ *    clm4_mvm_scale_and_add, clv8_quantize, clv8_scale_and_add, clm4_mvm_v8, clm4_mvm_v8_scale_and_add, clm4_iht, clm4_iht_v8,
+ *    clm8_quantize, clm8_mvm):
  *      (1) calls that share a state buffer must be STREAM-ORDERED -- the same stream, or an event / sync between them: they consume one
  *          sequential XORShift stream, as the reference's methods do on one object, and each launch reads the state its predecessor left;
  *      (2) such a call must NOT be captured into a hipGraph unless its state is in graph mode (clv_rng_graph_mode): ordinarily every launch
@@ -281,6 +282,29 @@ int  clm4_transpose(const int8_t *q, const float *s, uint64_t rows, uint64_t col
 /* mixed precision CloverMatrix4::mvm(const CloverVector32&, CloverVector32&) (CloverMatrix4.h:1451-1547):
  * x: cols floats, r: rows floats (fp32 row dots, no re-quantisation).  Bit-identical (32 fma chains per row). */
 int  clm4_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *r, void *stream);
+
+/* ---- CloverMatrix8 ---------------------------------------------------------------------------- */
+/* Layout (CloverMatrix8.h:36-90): rows*cols int8 values row-major, then (rows/64)*(cols/64) fp32 tile scales row-major;
+ * value = q * (s_tile / 127).  rows and cols are multiples of 128 (the mvm family also takes rows % 64 == 0, a row shard).
+ * CloverMatrix8::quantize (CloverMatrix8.h:203-480): per 64x64 tile m = max|x| (0 -> 1), q = trunc(fma(|x|, 127/m, noise)) with the
+ * sign of x.  With an rng the tiles consume the stream in the reference's order (column-block outer, row-block inner, two draws per
+ * tile row; draw 2i + (e >> 5), word e & 7, byte (e >> 3) & 3 for tile row i, column e): stream-ordered per state, no graph capture. */
+int  clm8_quantize(const float *A, uint64_t rows, uint64_t cols, int8_t *q, float *s, uint64_t *rng_state_dev, void *stream);
+/* CloverMatrix8::restore / get (CloverMatrix8.h:117-131, 1300-1309): A[i][j] = f32(s_tile / 127) * q, rows*cols floats row-major */
+int  clm8_restore(const int8_t *q, const float *s, uint64_t rows, uint64_t cols, float *A, void *stream);
+/* CloverMatrix8::mvm(const CloverVector8&, CloverVector8&) (CloverMatrix8.h:1002-1299) and mvm_parallel (:664-998; the same order per
+ * row).  x: cols bytes + cols/64 scales (CloverVector8); r: rows bytes + rows/64 scales, the row values re-quantised as
+ * CloverVector8::quantize does.  Per block, 8 exact integer lanes (bytes 4k..4k+3 and 32+4k..32+4k+3), one fp32 fma chain per lane
+ * with factor f32(f32(su * 1/127) * f32(sv * 1/127)), then the extractf128 / movehl / shuffle tree.  Bit-identical when
+ * rng_state_dev == NULL; with an rng the re-quantisation draws two values per 64-row group: stream-ordered, no graph capture. */
+int  clm8_mvm(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx, int8_t *r, float *sr,
+              uint64_t *rng_state_dev, void *stream);
+/* CloverMatrix8::mvm(const CloverVector32&, CloverVector32&) (CloverMatrix8.h:558-662): x: cols floats, r: rows floats.
+ * Bit-identical (4 accumulators x 8 lanes, fma(f32(v * f32(s / 127)), q, acc), then (a1+a2)+(a3+a4) and _mm256_haddf32_ps). */
+int  clm8_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *r, void *stream);
+/* CloverMatrix8::transpose / transpose_parallel (CloverMatrix8.h:1312-1386): qt(j,i) = q(i,j), the tile scale grid transposed.
+ * q is rows x cols, qt is cols x rows; not in place.  Exact. */
+int  clm8_transpose(const int8_t *q, const float *s, uint64_t rows, uint64_t cols, int8_t *qt, float *st, void *stream);
 /* Q_IHT / Q_GD (test/performance/01_measure.h:923-946, 999-1021): x.clear(), then `iterations` times
  *   t1 = Phi*x; t2 = y - t1; t3 = PhiT*t2; x = x + mu*t3; [threshold(K)]          (threshold != 0: IHT, else GD)
  * entirely on the device.  Phi is m x n, PhiT its transpose (n x m), x has n (padded) / x_len (logical)

@@ -2,7 +2,8 @@
 """Per-kernel achieved bandwidth at HBM-resident sizes (operands >> 256 MiB Infinity Cache), printed as JSON.
 
 Algorithmic bytes per element follow SURVEY 8(d): quantize/restore 4.5625, dot 1.125, scaleAndAdd 1.6875,
-threshold 1.125 (nibbles + scales read and written once each), transpose 2 x (1/2 + 4/4096), matrix quantize 4.5625."""
+threshold 1.125 (nibbles + scales read and written once each), transpose 2 x (1/2 + 4/4096), matrix quantize 4.5625;
+CloverMatrix8 (m8_*): quantize 4 + 1 + 4/4096, transpose 2 x (1 + 4/4096), mvm 1 + 4/4096 per matrix element."""
 import ctypes as C
 import json
 import os
@@ -151,4 +152,67 @@ rec("mvm_65536^2", base + (N2 // 2 + N2 // 16) + (M2 // 2 + M2 // 16),
     lambda: hip.check(lib.clm4_mvm(big.ptr, sbig.ptr, M2, N2, xb4.ptr, sxb.ptr, rb.ptr, srb.ptr, None, None)))
 rec("mvm_v8_65536^2", base + (N2 + N2 // 16) + (M2 + M2 // 16),
     lambda: hip.check(lib.clm4_mvm_v8(big.ptr, sbig.ptr, M2, N2, xb8.ptr, sxb.ptr, rb.ptr, srb.ptr, None, None)))
+# ---- CloverMatrix8: int8 values + one fp32 scale per 64x64 tile (1 + 4/4096 bytes per element)
+del big, sbig, xb4, xb8, sxb, rb, srb, qA, sA
+for n8 in (32768, 65536):
+    vals, scs = n8 * n8, 4 * (n8 // 64) ** 2
+    A8 = hip.alloc(4 * vals)
+    hip.check(lib.clv_fill_random_ints_f32(A8.ptr, vals, 10, 31, 0, None))
+    q8m, s8m, q8t, s8t = hip.alloc(vals), hip.alloc(scs), hip.alloc(vals), hip.alloc(scs)
+    rng8 = hip.new_rng(5, 6)
+    rec(f"m8_quantize_{n8}^2", 4 * vals + vals + scs, lambda: hip.check(lib.clm8_quantize(A8.ptr, n8, n8, q8m.ptr, s8m.ptr, None, None)), reps=3)
+    rec(f"m8_quantize_stochastic_{n8}^2", 4 * vals + vals + scs,
+        lambda: hip.check(lib.clm8_quantize(A8.ptr, n8, n8, q8t.ptr, s8t.ptr, rng8.ptr, None)), reps=3)
+    del A8
+    rec(f"m8_transpose_{n8}^2", 2 * (vals + scs), lambda: hip.check(lib.clm8_transpose(q8m.ptr, s8m.ptr, n8, n8, q8t.ptr, s8t.ptr, None)), reps=3)
+    xv8, sxv8, rv8, srv8 = hip.alloc(n8), hip.alloc(n8 // 16), hip.alloc(n8), hip.alloc(n8 // 16)
+    hip.check(lib.clv_fill_random_nibbles(xv8.ptr, n8, 41, 0, None))
+    hip.check(lib.clv_fill_random_scales(sxv8.ptr, n8 // 64, 42, 0, None))
+    mv8 = vals + scs + 2 * (n8 + n8 // 16)
+    rec(f"m8_mvm_v8_{n8}^2", mv8, lambda: hip.check(lib.clm8_mvm(q8m.ptr, s8m.ptr, n8, n8, xv8.ptr, sxv8.ptr, rv8.ptr, srv8.ptr, None, None)))
+    rec(f"m8_mvm_v8_stochastic_{n8}^2", mv8,
+        lambda: hip.check(lib.clm8_mvm(q8m.ptr, s8m.ptr, n8, n8, xv8.ptr, sxv8.ptr, rv8.ptr, srv8.ptr, rng8.ptr, None)))
+    xf, rf = hip.alloc(4 * n8), hip.alloc(4 * n8)
+    hip.check(lib.clv_fill_random_ints_f32(xf.ptr, n8, 10, 43, 0, None))
+    rec(f"m8_mvm_f32_{n8}^2", vals + scs + 8 * n8, lambda: hip.check(lib.clm8_mvm_f32(q8m.ptr, s8m.ptr, n8, n8, xf.ptr, rf.ptr, None)))
+    del q8m, s8m, q8t, s8t, xv8, sxv8, rv8, srv8, xf, rf
+# the published mvm size (doc/results/performance.txt, 8-bit column): 8192^2 = 64 MiB, cache-resident across calls
+n8 = 8192
+q8m, s8m = hip.alloc(n8 * n8), hip.alloc(4 * (n8 // 64) ** 2)
+hip.check(lib.clv_fill_random_nibbles(q8m.ptr, n8 * n8, 44, 0, None))
+hip.check(lib.clv_fill_random_scales(s8m.ptr, (n8 // 64) ** 2, 45, 0, None))
+xv8, sxv8, rv8, srv8 = hip.alloc(n8), hip.alloc(n8 // 16), hip.alloc(n8), hip.alloc(n8 // 16)
+hip.check(lib.clv_fill_random_nibbles(xv8.ptr, n8, 46, 0, None))
+hip.check(lib.clv_fill_random_scales(sxv8.ptr, n8 // 64, 47, 0, None))
+rec("m8_mvm_v8_8192^2", n8 * n8 + 4 * (n8 // 64) ** 2 + 2 * (n8 + n8 // 16),
+    lambda: hip.check(lib.clm8_mvm(q8m.ptr, s8m.ptr, n8, n8, xv8.ptr, sxv8.ptr, rv8.ptr, srv8.ptr, None, None)))
+del q8m, s8m, xv8, sxv8, rv8, srv8
+# one iteration of Q_IHT<CloverMatrix8, CloverVector8> as CloverIHT.h's generic template issues it (Phi m x n with m = N/2, K = N/4):
+# mvm, scaleAndAdd, mvm (PhiT), scaleAndAdd, threshold -- five launches; threshold in both tie rules (the headers' default is the reference's)
+from clover_amd.lib_binding import THRESHOLD_FAST, THRESHOLD_REFERENCE  # noqa: E402
+for N8 in (8192, 16384):
+    m8r, n8c, K8 = N8 // 2, N8, N8 // 4
+    P, sP, PT, sPT = hip.alloc(m8r * n8c), hip.alloc(4 * (m8r // 64) * (n8c // 64)), hip.alloc(m8r * n8c), hip.alloc(4 * (m8r // 64) * (n8c // 64))
+    hip.check(lib.clv_fill_random_nibbles(P.ptr, m8r * n8c, 51, 0, None))
+    hip.check(lib.clv_fill_random_scales(sP.ptr, (m8r // 64) * (n8c // 64), 52, 0, None))
+    hip.check(lib.clm8_transpose(P.ptr, sP.ptr, m8r, n8c, PT.ptr, sPT.ptr, None))
+    vx, svx, vt3, svt3 = hip.alloc(n8c), hip.alloc(n8c // 16), hip.alloc(n8c), hip.alloc(n8c // 16)
+    vy, svy, vt1, svt1, vt2, svt2 = hip.alloc(m8r), hip.alloc(m8r // 16), hip.alloc(m8r), hip.alloc(m8r // 16), hip.alloc(m8r), hip.alloc(m8r // 16)
+    hip.check(lib.clv_fill_random_nibbles(vx.ptr, n8c, 53, 0, None))
+    hip.check(lib.clv_fill_random_scales(svx.ptr, n8c // 64, 54, 0, None))
+    hip.check(lib.clv_fill_random_nibbles(vy.ptr, m8r, 55, 0, None))
+    hip.check(lib.clv_fill_random_scales(svy.ptr, m8r // 64, 56, 0, None))
+
+    def iht8_iteration(mode):
+        hip.check(lib.clm8_mvm(P.ptr, sP.ptr, m8r, n8c, vx.ptr, svx.ptr, vt1.ptr, svt1.ptr, None, None))
+        hip.check(lib.clv8_scale_and_add(vy.ptr, svy.ptr, vt1.ptr, svt1.ptr, -1.0, m8r, vt2.ptr, svt2.ptr, None, None))
+        hip.check(lib.clm8_mvm(PT.ptr, sPT.ptr, n8c, m8r, vt2.ptr, svt2.ptr, vt3.ptr, svt3.ptr, None, None))
+        hip.check(lib.clv8_scale_and_add(vx.ptr, svx.ptr, vt3.ptr, svt3.ptr, 0.5, n8c, vx.ptr, svx.ptr, None, None))
+        hip.check(lib.clv8_threshold_mode(vx.ptr, svx.ptr, n8c, n8c, K8, mode, None, None))
+    itb = 2 * (m8r * n8c + 4 * (m8r // 64) * (n8c // 64))
+    rec(f"m8_q_iht_iteration_N{N8}", itb, lambda: iht8_iteration(THRESHOLD_REFERENCE), reps=5,
+        extra={"note": "bytes = the two matrices only; threshold in the reference's tie rule (the headers' default)"})
+    rec(f"m8_q_iht_iteration_fast_threshold_N{N8}", itb, lambda: iht8_iteration(THRESHOLD_FAST), reps=5,
+        extra={"note": "bytes = the two matrices only; threshold with lowest-index ties (-DCLOVER_FAST)"})
+    del P, sP, PT, sPT, vx, svx, vt3, svt3, vy, svy, vt1, svt1, vt2, svt2
 print(json.dumps(res, indent=1))
