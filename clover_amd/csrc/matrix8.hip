@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void k_m8_quantize(const f32x4 *__restrict__ A
             w = ((uint32_t)quant1_det(v[j].x, k) & 0xFFu) | (((uint32_t)quant1_det(v[j].y, k) & 0xFFu) << 8) |
                 (((uint32_t)quant1_det(v[j].z, k) & 0xFFu) << 16) | ((uint32_t)quant1_det(v[j].w, k) << 24);
         }
-        // k == inf (tile maximum below 2^-126 * 127): the reference's cvttps gives 0x80000000, whose low byte is 0
+        // k == inf (tile maximum below 127 / FLT_MAX, about 3.7e-37): the reference's cvttps gives 0x80000000, whose low byte is 0
         __builtin_nontemporal_store(k < __builtin_inff() ? w : 0u, &q[base4 + (uint64_t)i * cols4]);
     }
     if (tid == 0) s[(uint64_t)b_i * h_blocks + b_j] = m;

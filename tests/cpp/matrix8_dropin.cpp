@@ -1,8 +1,11 @@
 // matrix8_dropin.cpp -- a client of include/CloverMatrix8.h written with the reference's method names (tests/test_matrix8.py).
 //   matrix8_dropin <dir> <iht|gd> <m> <n> <iterations> <K> <mu>
+//   matrix8_dropin <dir> ragged <m> <n>
 // reads <dir>/phi.f32 (m x n) and <dir>/y.f32 (m), checks mvm == mvm_parallel == mvm_scalar for 8-bit and fp32 vectors (rounding
 // disabled: validate/03_matrix.cpp does the same for CloverMatrix4), runs Q_IHT<CloverMatrix8, CloverVector8> or Q_GD<...> through
 // the generic templates of CloverIHT.h and writes Phi, PhiT, y, x, t1, t2, t3 (values then scales) to <dir>/<name>.bin.
+// ragged: a CloverMatrix8(m, n) with m, n not multiples of 128, from <dir>/phi.f32 (m x n) and <dir>/x.f32 (n): writes Phi, PhiT, the
+// 8-bit mvm r1 and the fp32 mvm (<dir>/f1.f32), all at the padded size.
 #include <CloverIHT.h>
 #include <CloverMatrix8.h>
 
@@ -44,8 +47,34 @@ static bool same8(const CloverVector8 &a, const CloverVector8 &b)
     return !memcmp(a.getData(), b.getData(), a.size_pad()) && !memcmp(a.getScales(), b.getScales(), a.size_pad() / 64 * sizeof(float));
 }
 
+static int ragged(const std::string &dir, uint64_t m, uint64_t n)
+{
+    const std::vector<float> phi = read_f32(dir + "/phi.f32", m * n), xv = read_f32(dir + "/x.f32", n);
+    CloverMatrix8 Phi(m, n), PhiT(n, m);
+    const uint64_t rows = Phi.getRows(), cols = Phi.getCols();
+    CloverMatrix32 Phi32(m, n);
+    for (uint64_t i = 0; i < rows; i++)
+        for (uint64_t j = 0; j < cols; j++) Phi32.set(i, j, i < m && j < n ? phi[i * n + j] : 0.0f);
+    CloverVector32 x32(cols);
+    for (uint64_t j = 0; j < cols; j++) x32.set(j, j < n ? xv[j] : 0.0f);
+    Phi.quantize(Phi32);
+    Phi.transpose(PhiT);
+    CloverVector8 xq(x32), r1(rows);
+    CloverVector32 f1(rows);
+    Phi.mvm(xq, r1);
+    Phi.mvm(x32, f1);
+    dump(dir, "phi", Phi);
+    dump(dir, "phit", PhiT);
+    dump(dir, "xq", xq);
+    dump(dir, "r1", r1);
+    write_bytes(dir + "/f1.f32", f1.getData(), rows * sizeof(float), f1.getData(), 0);
+    printf("rows=%llu cols=%llu done\n", (unsigned long long)rows, (unsigned long long)cols);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 5 && !strcmp(argv[2], "ragged")) return ragged(argv[1], strtoull(argv[3], 0, 10), strtoull(argv[4], 0, 10));
     if (argc != 8) { fprintf(stderr, "usage: %s dir iht|gd m n iterations K mu\n", argv[0]); return 2; }
     const std::string dir = argv[1], mode = argv[2];
     const uint64_t m = strtoull(argv[3], 0, 10), n = strtoull(argv[4], 0, 10), iterations = strtoull(argv[5], 0, 10),

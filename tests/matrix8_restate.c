@@ -1,12 +1,31 @@
 /* matrix8_restate.c -- plain-C restatement of CloverMatrix8 (the reference's include/CloverMatrix8.h) in its SIMD order, the
- * checker of tests/test_matrix8.py.  Built by that test with  cc -O2 -ffp-contract=off -fno-fast-math  and linked against the
- * oracle (oracle/liboracle.so) for the XORShift stream: every draw is orc_rng_draw, the generator of the other restatements.
- * Every fused multiply-add is an explicit fmaf(); every other operation is a separately rounded fp32 operation.
+ * checker of the CloverMatrix8 tests.  Built by tests/matrix8_helpers.py with  cc -O2 -ffp-contract=off -fno-fast-math  and linked
+ * against the oracle (oracle/liboracle.so) for the XORShift stream: every draw is orc_rng_draw, the generator of the other
+ * restatements.  Every fused multiply-add is an explicit fmaf(); every other operation is a separately rounded fp32 operation.
+ *
+ * The same file is built a second time with  -mfma -fopenmp  for the large shapes: fmaf() becomes one instruction (same result), and
+ * the loops whose iterations are independent -- the row dots, rm8_mvm_f32, rm8_transpose and the deterministic quantize -- run on at
+ * most 16 threads.  Everything that draws from the stream stays sequential and in the reference's order.
  *
  * Layout: rows*cols int8 values row-major, then (rows/64)*(cols/64) fp32 tile scales row-major; value = q * (s / 127). */
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
+#ifdef _OPENMP
+#include <omp.h>
+#endif
+
+/* threads of the -fopenmp build: never more than 16 (the CPUs one command may use) */
+static inline int rm8_threads(void)
+{
+#ifdef _OPENMP
+    const int n = omp_get_max_threads();
+    return n < 16 ? n : 16;
+#else
+    return 1;
+#endif
+}
 
 typedef struct { uint64_t s0[4]; uint64_t s1[4]; } orc_rng;      /* oracle/clover4_oracle.h */
 void orc_rng_draw(orc_rng *r, uint32_t W[8]);
@@ -68,6 +87,8 @@ static float fix_zero(float m)
 void rm8_quantize(const float *A, uint64_t rows, uint64_t cols, int8_t *q, float *s, orc_rng *rng)
 {
     const uint64_t h_blocks = cols >> 6, v_blocks = rows >> 6;
+    /* with a generator the tiles draw in this loop order: sequential */
+#pragma omp parallel for collapse(2) num_threads(rm8_threads()) if (!rng)
     for (uint64_t b_j = 0; b_j < h_blocks; b_j++)
         for (uint64_t b_i = 0; b_i < v_blocks; b_i++) {
             const uint64_t off = (b_i << 6) * cols + (b_j << 6);
@@ -137,23 +158,24 @@ static void requant64(const float d[64], int8_t r[64], float *sr, orc_rng *rng)
     for (int l = 0; l < 64; l++) r[l] = quant1(d[l], k, n[l]);
 }
 
-/* CloverMatrix8::mvm(const CloverVector8 &, CloverVector8 &) (:1002-1299) */
-void rm8_mvm(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx, int8_t *r, float *sr,
-             orc_rng *rng)
-{
-    const uint64_t h_blocks = cols >> 6;
-    for (uint64_t rb = 0; rb < rows / 64; rb++) {
-        float d[64];
-        for (uint64_t l = 0; l < 64; l++) d[l] = row_dot8(A + (rb * 64 + l) * cols, sA + rb * h_blocks, x, sx, h_blocks);
-        requant64(d, r + rb * 64, sr + rb, rng);
-    }
-}
-
-/* the fp32 row values of the same (before re-quantisation) */
+/* the fp32 row values of CloverMatrix8::mvm (before re-quantisation) */
 void rm8_rowdots(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx, float *d)
 {
     const uint64_t h_blocks = cols >> 6;
+#pragma omp parallel for num_threads(rm8_threads())
     for (uint64_t i = 0; i < rows; i++) d[i] = row_dot8(A + i * cols, sA + (i >> 6) * h_blocks, x, sx, h_blocks);
+}
+
+/* CloverMatrix8::mvm(const CloverVector8 &, CloverVector8 &) (:1002-1299): every row dot first, then the row groups re-quantised in
+ * order (with a generator, row group rb takes the stream's draws 2 rb, 2 rb + 1) */
+void rm8_mvm(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx, int8_t *r, float *sr,
+             orc_rng *rng)
+{
+    float *d = (float *)malloc((rows ? rows : 1) * sizeof(float));
+    if (!d) abort();
+    rm8_rowdots(A, sA, rows, cols, x, sx, d);
+    for (uint64_t rb = 0; rb < rows / 64; rb++) requant64(d + rb * 64, r + rb * 64, sr + rb, rng);
+    free(d);
 }
 
 /* CloverMatrix8::mvm(const CloverVector32 &, CloverVector32 &) (:558-662): element 8j + l of a block -> accumulator j mod 4, lane l
@@ -162,6 +184,7 @@ void rm8_rowdots(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols,
 void rm8_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *r)
 {
     const uint64_t h_blocks = cols >> 6;
+#pragma omp parallel for num_threads(rm8_threads())
     for (uint64_t i = 0; i < rows; i++) {
         const int8_t *u = A + i * cols;
         const float *su = sA + (i >> 6) * h_blocks;
@@ -187,9 +210,13 @@ void rm8_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols,
 /* CloverMatrix8::transpose (:1312-1386): values and the tile scale grid */
 void rm8_transpose(const int8_t *q, const float *s, uint64_t rows, uint64_t cols, int8_t *qt, float *st)
 {
-    for (uint64_t i = 0; i < rows; i++)
-        for (uint64_t j = 0; j < cols; j++) qt[j * rows + i] = q[i * cols + j];
     const uint64_t v_blocks = rows >> 6, h_blocks = cols >> 6;
+    /* 64 x 64 tiles at a time: the same bytes, without a cache miss per byte at 65536 columns */
+#pragma omp parallel for collapse(2) num_threads(rm8_threads())
+    for (uint64_t bi = 0; bi < v_blocks; bi++)
+        for (uint64_t bj = 0; bj < h_blocks; bj++)
+            for (uint64_t i = 64 * bi; i < 64 * bi + 64; i++)
+                for (uint64_t j = 64 * bj; j < 64 * bj + 64; j++) qt[j * rows + i] = q[i * cols + j];
     for (uint64_t bi = 0; bi < v_blocks; bi++)
         for (uint64_t bj = 0; bj < h_blocks; bj++) st[bj * v_blocks + bi] = s[bi * h_blocks + bj];
 }

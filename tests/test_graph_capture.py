@@ -109,3 +109,94 @@ def test_captured_dot_fast_replays(hip, oracle, n):
     ok(rt.hipGraphExecDestroy(gexec))
     ok(rt.hipGraphDestroy(graph))
     ok(rt.hipStreamDestroy(stream))
+
+
+def test_captured_matrix_stochastic_calls_walk_the_stream_on_every_replay(hip, oracle, tmp_path_factory):
+    """one stochastic call of each matrix-level entry and of the 8-bit vector calls, captured into ONE linear stream on one state in
+    graph mode: clm8_quantize, clm8_mvm, clm4_quantize (its public entry always has rows / 64 >= 2: the <2> strip kernel, sequence
+    number in the argument list), clm4_mvm, clm4_mvm_v8, clm4_mvm_scale_and_add, clv8_quantize, clv8_scale_and_add.  Every replay gives
+    the next part of the oracle's walk, and ordinary calls continue from where the replays left the state.  (clm4_iht* and the large-n
+    threshold are not captured: their persistent kernels spin-wait on each other and need every workgroup co-resident.)"""
+    from conftest import random_packed
+    from matrix8_helpers import build_restate
+    m8 = build_restate(tmp_path_factory.getbasetemp(), parallel=False)
+    lib = hip.lib
+    rows, cols = 256, 512
+    rng = np.random.default_rng(88)
+    A = (rng.standard_normal((rows, cols)) * 2).astype(np.float32)
+    q8A, s8A = m8.quantize(A)
+    q4A, _ = random_packed(rng, rows * cols)
+    s4A = rng.uniform(0.5, 2, size=(rows // 64) * (cols // 64)).astype(np.float32)
+    (q4x, s4x), (q4u, s4u) = random_packed(rng, cols), random_packed(rng, rows)
+    x = (rng.standard_normal(cols) * 3).astype(np.float32)
+    q8x, s8x = oracle.v8_quantize(x)
+    q8u, s8u = oracle.v8_quantize((rng.standard_normal(cols) * 3).astype(np.float32))
+    d = {k: hip.to_device(v) for k, v in dict(A=A, q8A=q8A, s8A=s8A, q4A=q4A, s4A=s4A, q4x=q4x, s4x=s4x, q4u=q4u, s4u=s4u, x=x, q8x=q8x,
+                                                  s8x=s8x, q8u=q8u, s8u=s8u).items()}
+    n_tiles = (rows // 64) * (cols // 64)
+    out = dict(m8q=(rows * cols, 4 * n_tiles), m8r=(rows, rows // 16), m4q=(rows * cols // 2, 4 * n_tiles), m4r=(rows // 2, rows // 16),
+               m4r8=(rows, rows // 16), m4t=(rows // 2, rows // 16), m4sa=(rows // 2, rows // 16), v8q=(cols, cols // 16), v8sa=(cols, cols // 16))
+    o = {k: (hip.alloc(a), hip.alloc(b)) for k, (a, b) in out.items()}
+    st = hip.new_rng(2718, 2818)
+    orng = oracle.rng(2718, 2818)
+
+    def enqueue(stream):
+        hip.check(lib.clm8_quantize(d["A"].ptr, rows, cols, o["m8q"][0].ptr, o["m8q"][1].ptr, st.ptr, stream))
+        hip.check(lib.clm8_mvm(d["q8A"].ptr, d["s8A"].ptr, rows, cols, d["q8x"].ptr, d["s8x"].ptr, o["m8r"][0].ptr, o["m8r"][1].ptr, st.ptr, stream))
+        hip.check(lib.clm4_quantize(d["A"].ptr, rows, cols, o["m4q"][0].ptr, o["m4q"][1].ptr, st.ptr, stream))
+        hip.check(lib.clm4_mvm(d["q4A"].ptr, d["s4A"].ptr, rows, cols, d["q4x"].ptr, d["s4x"].ptr, o["m4r"][0].ptr, o["m4r"][1].ptr, st.ptr, stream))
+        hip.check(lib.clm4_mvm_v8(d["q4A"].ptr, d["s4A"].ptr, rows, cols, d["q8x"].ptr, d["s8x"].ptr, o["m4r8"][0].ptr, o["m4r8"][1].ptr,
+                                  st.ptr, stream))
+        hip.check(lib.clm4_mvm_scale_and_add(d["q4A"].ptr, d["s4A"].ptr, rows, cols, d["q4x"].ptr, d["s4x"].ptr, d["q4u"].ptr, d["s4u"].ptr,
+                                             -0.37, o["m4t"][0].ptr, o["m4t"][1].ptr, o["m4sa"][0].ptr, o["m4sa"][1].ptr, st.ptr, stream))
+        hip.check(lib.clv8_quantize(d["x"].ptr, cols, o["v8q"][0].ptr, o["v8q"][1].ptr, st.ptr, stream))
+        hip.check(lib.clv8_scale_and_add(d["q8u"].ptr, d["s8u"].ptr, d["q8x"].ptr, d["s8x"].ptr, 0.625, cols, o["v8sa"][0].ptr,
+                                         o["v8sa"][1].ptr, st.ptr, stream))
+
+    def check(rep):
+        def got(k, dt_q):
+            return o[k][0].download(dt_q), o[k][1].download(np.float32)
+        want = {}
+        want["m8q"] = m8.quantize(A, orng)
+        want["m8r"] = m8.mvm(q8A, s8A, rows, cols, q8x, s8x, orng)
+        want["m4q"] = oracle.m4_quantize(A, orng)
+        want["m4r"] = oracle.m4_mvm(q4A, s4A, rows, cols, q4x, s4x, orng)
+        want["m4r8"] = oracle.m4_mvm_v8(q4A, s4A, rows, cols, q8x, s8x, orng)
+        want["m4t"] = oracle.m4_mvm(q4A, s4A, rows, cols, q4x, s4x, orng)
+        want["m4sa"] = oracle.v4_scale_and_add(q4u, s4u, *want["m4t"], -0.37, orng)
+        want["v8q"] = oracle.v8_quantize(x, orng)
+        want["v8sa"] = oracle.v8_scale_and_add(q8u, s8u, q8x, s8x, 0.625, orng)
+        for k, (wq, ws) in want.items():
+            gq, gs = got(k, np.asarray(wq).dtype)
+            assert same(gq, wq) and same(gs, ws), (rep, k)
+
+    # ordinary (host-stamped) calls first: the generator tables and any per-stream state are built outside the capture
+    enqueue(None)
+    hip.sync()
+    check("ordinary")
+    hip.check(lib.clv_rng_graph_mode(st.ptr, 1, None))
+    hip.sync()
+    rt = C.CDLL("libamdhip64.so")
+    stream, graph, gexec = C.c_void_p(), C.c_void_p(), C.c_void_p()
+
+    def ok(rc):
+        assert rc == 0, f"HIP runtime call failed: {rc}"
+    ok(rt.hipStreamCreate(C.byref(stream)))
+    ok(rt.hipStreamBeginCapture(stream, 0))
+    enqueue(stream)
+    ok(rt.hipStreamEndCapture(stream, C.byref(graph)))
+    ok(rt.hipGraphInstantiate(C.byref(gexec), graph, None, None, 0))
+    for rep in range(3):
+        ok(rt.hipGraphLaunch(gexec, stream))
+        ok(rt.hipStreamSynchronize(stream))
+        check(rep)
+    ok(rt.hipGraphExecDestroy(gexec))
+    ok(rt.hipGraphDestroy(graph))
+    ok(rt.hipStreamDestroy(stream))
+    k1, k2 = hip.rng_get(st)
+    ok1, ok2 = oracle.rng_keys(orng)
+    assert np.array_equal(k1, ok1) and np.array_equal(k2, ok2)
+    hip.check(lib.clv_rng_graph_mode(st.ptr, 0, None))
+    enqueue(None)
+    hip.sync()
+    check("after")
