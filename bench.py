@@ -10,9 +10,12 @@ overlaps the next step's kernel (two result buffers), every step's gather is com
 per-GPU shard is fixed (default 65536 x 65536 = BASELINE.json configs[2], "C3"); --rows-per-gpu 131072
 at N=8 is exactly configs[4] ("C5", 2^20 x 2^16).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HBM, algorithmic bytes /
-HIP-event kernel time) and `cpu_baseline` (the AVX2+OpenMP restatement of the reference on the host cores,
-bounded sample, N=1 only).  Inputs are synthetic and generated on the device before the timed region.
+Prints ONE JSON line on rank 0 with the headline figures and `roofline` (HBM, algorithmic bytes / HIP-event
+kernel time of the sampled timed steps).  A plain run does only that: set up, warm up, time the K steps, write
+--dump-outputs, print.  Everything else the benchmark measures or checks runs behind --full: the cold figures, the
+`c5` object, the product's own multi-GPU loops, the gathered-result checks, at N=1 the `gemm` and `extras`
+objects, and `cpu_baseline` (the AVX2+OpenMP restatement of the reference on the host cores, bounded sample).
+Inputs are synthetic and generated on the device before the timed region.
 """
 from __future__ import annotations
 
@@ -250,21 +253,28 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500,
-                    help=f"timed steps of the headline (ms_per_step = their wall time / K); the side measurements behind it -- the cold pass, "
-                         f"the c5 object, the product's loops -- time min(K, {SIDE_STEPS}) steps each, so that K alone sets the run's length")
+                    help=f"timed steps of the headline (ms_per_step = their wall time / K); the cold pass in front of them and the side "
+                         f"measurements of --full -- the c5 object, the product's loops -- time min(K, {SIDE_STEPS}) steps each, so that K alone "
+                         f"sets the run's length")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps before the timed ones (default 20; 80 for --workload gemm: the matrix "
                                                                "pipe's clocks settle after about 50 calls)")
     ap.add_argument("--rows-per-gpu", type=int, default=65536)
     ap.add_argument("--preset", choices=("c3", "c5-weak", "c5-strong"), default=None,
-                    help="default (no preset): the headline is c3 -- 65536 x 65536 per GPU, weak scaling (BASELINE configs[2] at N=1) -- and the SAME "
-                         "line carries a `c5` object timed right behind it: BASELINE configs[4], the 2^20 x 2^16 matrix row-sharded over the N GPUs "
-                         "(2^20 / N rows each, CloverMatrix4.h:1700-1705's split).  c3 / c5-weak (131072 x 65536 per GPU = configs[4] at N=8) / "
-                         "c5-strong (configs[4] split over the N GPUs as the headline): one configuration, no c5 object")
-    ap.add_argument("--no-c5", action="store_true", help="leave the c5 object out of a default (no --preset) run")
+                    help="default (no preset): the headline is c3 -- 65536 x 65536 per GPU, weak scaling (BASELINE configs[2] at N=1) -- and with "
+                         "--full the SAME line carries a `c5` object timed right behind it: BASELINE configs[4], the 2^20 x 2^16 matrix row-sharded "
+                         "over the N GPUs (2^20 / N rows each, CloverMatrix4.h:1700-1705's split).  c3 / c5-weak (131072 x 65536 per GPU = configs[4] "
+                         "at N=8) / c5-strong (configs[4] split over the N GPUs as the headline): one configuration, no c5 object")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline, on the same line: ms_per_step_cold (the cold pass runs in every run, as the "
+                         "start of the warm-up; --full reports it), the c5 object, the product's "
+                         "own multi-GPU loops (one_process, gemm_sharded), for N > 1 the blocking gather time and the check of the gathered result, "
+                         "for N = 1 the gemm and extras objects, and the CPU baseline; the --no-* options below leave parts out.  Off by default: "
+                         "a plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-c5", action="store_true", help="leave the c5 object out of a --full run without --preset")
     ap.add_argument("--cols", type=int, default=65536)
     ap.add_argument("--cpu-sample-rows", type=int, default=65536,
-                    help="rows of the matrix the CPU baseline multiplies (default: all 65536 rows of C3 = 2 GiB of nibbles: beyond the 2 x 256 MB "
-                         "of L3 of the host, so the number is a DRAM number like the reference's)")
+                    help="rows of the matrix the CPU baseline of --full multiplies (default: all 65536 rows of C3 = 2 GiB of nibbles: beyond the "
+                         "2 x 256 MB of L3 of the host, so the number is a DRAM number like the reference's)")
     ap.add_argument("--workload", choices=("mvm", "gemm"), default="mvm",
                     help="mvm (default): the headline GEMV of BASELINE configs[2]; gemm: configs[3], one GPU, its own JSON line")
     ap.add_argument("--gemm-size", type=int, default=8192)
@@ -281,11 +291,11 @@ def main() -> None:
                     help="untimed launches of the same step for this many milliseconds BEFORE the W warm-up steps: after an idle period the chip "
                          "needs ~20-30 ms of work to reach its steady clocks (the driver's --warmup 5 is 1.6 ms: the 20 timed steps behind it ran "
                          "0.349 ms per step against 0.330 in steady state).  Reported in the JSON; 0 switches it off")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="leave the CPU baseline out of a --full run")
+    ap.add_argument("--no-extras", action="store_true", help="leave the gemm and extras objects out of a --full run")
     ap.add_argument("--no-one-process", action="store_true",
-                    help="leave out the `one_process` and `gemm_sharded` objects (the product's clm4_sharded_* loops over the same N devices, "
-                         "driven by rank 0 behind the ranks' timed regions)")
+                    help="leave out of a --full run the `one_process` and `gemm_sharded` objects (the product's clm4_sharded_* loops over the "
+                         "same N devices, driven by rank 0 behind the ranks' timed regions)")
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
                     help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64, "
                          f"at most {DUMP_LIMIT_BYTES >> 20} MB in all; a fixed, seeded sample of a larger output).  The inputs are seeded: the "
@@ -504,6 +514,7 @@ def main() -> None:
             pr = [torch.zeros(1, dtype=torch.float64, device=red_dev) for _ in range(world)]
             dist.all_gather(pr, torch.tensor([kern_mine], dtype=torch.float64, device=red_dev))
             r["per_rank_kernel_ms"] = [round(float(v.item()), 5) for v in pr]
+        if dist_on and args.full:
             # the exchange alone, outside the timed region: K blocking all-gathers of the packed result
             reps = 50
             dist.barrier()
@@ -527,6 +538,8 @@ def main() -> None:
         return r
 
     rows = args.rows_per_gpu
+    # the cold pass runs in every run: its W + min(K, SIDE_STEPS) steps (about 10 ms at C3) are the start of the warm-up that the settled
+    # steps have always been timed behind; only --full reports them (ms_per_step_cold)
     head = time_config(rows, cold_first=True, steps=args.steps)
     rows_total = head["rows_total"]
     if args.dump_outputs:
@@ -555,7 +568,7 @@ def main() -> None:
     # fit one GPU, so N = 1 carries it too).  Only when no --preset was asked for: the presets time one configuration each.
     c5 = None
     c5_total = int(os.environ.get("CLOVER_BENCH_C5_ROWS", str(1 << 20)))       # tests shrink it; the object says so
-    if args.preset is None and not args.no_c5:
+    if args.full and args.preset is None and not args.no_c5:
         if c5_total % (64 * world) != 0:
             c5 = {"skipped": f"{c5_total} rows do not split into {world} equal shards of whole 64-row blocks"}
         else:
@@ -598,7 +611,8 @@ def main() -> None:
     elapsed, kern_avg_ms, settle_launches = head["elapsed"], head["kern_avg_ms"], head["settle_launches"]
     per_rank_kernel_ms, gather_us, gather_ok = head["per_rank_kernel_ms"], head["gather_us"], head["gather_ok"]
     ms_per_step = elapsed / args.steps * 1e3
-    ms_cold = head["cold"][0] / head["cold_steps"] * 1e3
+    cold = head["cold"] if args.full else None
+    ms_cold = cold[0] / head["cold_steps"] * 1e3 if cold else None
     bytes_total = mvm_bytes(rows_total, cols)
     bytes_gpu = mvm_bytes(rows, cols)
     value = bytes_total / (ms_per_step * 1e-3) / 1e9
@@ -608,8 +622,8 @@ def main() -> None:
         "metric": "int4 GEMV (CloverMatrix4::mvm) effective GB/s, algorithmic operand bytes / time",
         "value": round(value, 2), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 5),
-        # the same K steps measured FIRST, behind nothing but the data fill and the driver's W warm-up steps (no clock settle)
-        "ms_per_step_cold": round(ms_cold, 5), "value_cold": round(bytes_total / (ms_cold * 1e-3) / 1e9, 2),
+        # --full: the first min(K, SIDE_STEPS) steps, measured FIRST, behind nothing but the data fill and the W warm-up steps (no clock settle)
+        **({"ms_per_step_cold": round(ms_cold, 5), "value_cold": round(bytes_total / (ms_cold * 1e-3) / 1e9, 2)} if cold else {}),
         "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
         "dtype": "int4", "data": "synthetic",
         # degraded: the RCCL group could not be used and every timed step carried a device->host copy + a gloo all-gather: `value` is NOT
@@ -623,24 +637,25 @@ def main() -> None:
                         f"x and result CloverVector4, STOCHASTIC_ROUNDING_DISABLED, bit-exact reference order",
             "rows_per_gpu": rows, "cols": cols, "parallelism": f"row-shard x{world}" + (" + all-gather of every step's packed result, overlapped with the next step" if dist_on else ""),
             "settle_launches": settle_launches, "settle_ms": args.settle_ms,
-            **({"gathered_result_verified": gather_ok, "rccl_ranks": rccl_ranks, "backend": data_backend,
+            **({**({"gathered_result_verified": gather_ok} if args.full else {}), "rccl_ranks": rccl_ranks, "backend": data_backend,
                 **({"nccl_fallback_reason": nccl_error or "the RCCL group failed on another rank"} if host_exchange and not debug_one_gpu else {}),
-                "per_rank_kernel_ms": per_rank_kernel_ms, "gather_us_blocking": gather_us,
+                "per_rank_kernel_ms": per_rank_kernel_ms, **({"gather_us_blocking": gather_us} if args.full else {}),
                 "gather_bytes_per_rank": packed_bytes(rows)} if dist_on else {}),
             **({"mode": "ranks", "launcher": os.environ.get("CLOVER_BENCH_LAUNCHER", "external torch.distributed.run")} if dist_on else {}),
             **({"DEBUG": "CLOVER_BENCH_DEBUG_ONE_GPU rehearsal: all ranks on one GPU, gloo through the host -- not a measurement"} if debug_one_gpu else {}),
             "gflops": round(2.0 * rows_total * cols / (ms_per_step * 1e-3) / 1e9, 1),
             "algorithmic_bytes_per_step": bytes_total,
             "clock_settle": f"{settle_launches} untimed launches of the same step ({args.settle_ms:g} ms) before the {args.warmup} warm-up steps "
-                            "(steady clocks need 20-30 ms of work after idle); the K timed steps and their barriers are unchanged; "
-                            f"ms_per_step_cold = the first min(K, {SIDE_STEPS}) = {head['cold_steps']} of the same steps, measured before any of that",
+                            "(steady clocks need 20-30 ms of work after idle); the K timed steps and their barriers are unchanged"
+                            + (f"; ms_per_step_cold = the first min(K, {SIDE_STEPS}) = {head['cold_steps']} of the same steps, measured before any of that"
+                               if cold else ""),
             "arithmetic": "int4 x int4 products summed exactly per 32-bit word (v_dot8_i32_i4), fp32 per-block scale + fma chains in reference order",
         },
         "roofline": {
             "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
             "kernel": "k_m4_mvm64", "kernel_avg_ms": round(kern_avg_ms, 5), "algorithmic_bytes_per_launch": bytes_gpu,
-            "kernel_avg_ms_cold": round(head["cold"][1], 5),
+            **({"kernel_avg_ms_cold": round(cold[1], 5)} if cold else {}),
             "kernel_avg_of": f"HIP event pairs around every {args.event_every}. timed step ({head['kern_samples']} launches) on the launch stream",
         },
     }
@@ -652,13 +667,13 @@ def main() -> None:
         out["roofline"]["traffic"] = tr[0]
         out["roofline"]["traffic_source"] = f"profiles/{tr[1]} (FETCH_SIZE x1024 x2 gfx950 correction + WRITE_SIZE x1024, per launch)"
 
-    # The product's own multi-GPU loops, timed by the very command the driver runs: rank 0 -- the other ranks have left their timed regions
+    # --full: the product's own multi-GPU loops, timed by the same command: rank 0 -- the other ranks have left their timed regions
     # and are idle or gone -- drives all N devices through the C ABI: `one_process` = clm4_sharded_mvm_enqueue over the same shards (c3
     # headline + c5), `gemm_sharded` = configs[3] split by rows of A with the C row panels all-gathered
     if dist_on:
         dist.barrier()                                           # every rank is past its last kernel and collective
         dist.destroy_process_group()                             # torch's RCCL communicators are gone before the product builds its own
-    if not args.no_one_process:
+    if args.full and not args.no_one_process:
         if world == 1 or debug_one_gpu or torch.cuda.device_count() >= world:
             torch.cuda.empty_cache()
             out.update(run_product_loops(args, world))
@@ -668,14 +683,14 @@ def main() -> None:
 
     # side measurements first, while the chip is warm from the timed loop (the matrix pipe's clocks need ~50 calls to settle after an idle
     # period, and the CPU baseline below leaves the GPU idle for half a minute: round 3 measured the GEMM 5 % slower behind it)
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         for key, fn in (("gemm", gemm_object), ("extras", extras)):      # side measurements must never cost the headline line
             try:
                 out[key] = fn(hip, torch, dev, stream)
             except Exception as e:
                 out[key] = {"failed": f"{type(e).__name__}: {e}"}
 
-    if not args.no_cpu_baseline:                                  # rank 0's own shard (the whole C3 matrix by default), at every N
+    if args.full and not args.no_cpu_baseline:                    # rank 0's own shard (the whole C3 matrix by default), at every N
         try:
             res = head["res"]
             out["cpu_baseline"] = run_cpu_baseline(hip, head["A"], head["sA"], x, sx, res[: rows // 2], res[rows // 2:].view(torch.float32),
@@ -782,25 +797,30 @@ def one_process_measure(args, torch, hip, n: int) -> dict:
                     gs += gm.value
                 per_k.append(ks / len(sampled))
                 per_g.append(gs / len(sampled))
-            # every device holds the full result, and it equals the unsharded call's (n * 72 KiB: compared on the host)
-            last = (steps - 1) & 1
-            full = []
-            for d in range(n):
-                rp, sp = C.c_void_p(), C.c_void_p()
-                hip.check(lib.clm4_sharded_result_buf(ctx, d, last, C.byref(rp), C.byref(sp)))
-                rr = np.empty(rows_total // 2, np.uint8)
-                ss = np.empty(rows_total // 64, np.float32)
-                hip.check(lib.clv_set_device(0 if debug else d))
-                hip.check(lib.clv_memcpy_d2h(rr.ctypes.data, rp, rr.nbytes, None))
-                hip.check(lib.clv_memcpy_d2h(ss.ctypes.data, sp, ss.nbytes, None))
-                hip.check(lib.clv_device_sync())
-                full.append((rr, ss))
-            hip.check(lib.clv_set_device(0))
-            same = all(np.array_equal(full[0][0], f[0]) and np.array_equal(full[0][1].view(np.uint32), f[1].view(np.uint32)) for f in full[1:])
             ranks, equal = C.c_int(), C.c_int()
             hip.check(lib.clm4_sharded_comm_info(ctx, C.byref(ranks), C.byref(equal)))
+            full = []
+            if args.full:
+                # every device holds the full result, and it equals the unsharded call's (n * 72 KiB: compared on the host)
+                last = (steps - 1) & 1
+                for d in range(n):
+                    rp, sp = C.c_void_p(), C.c_void_p()
+                    hip.check(lib.clm4_sharded_result_buf(ctx, d, last, C.byref(rp), C.byref(sp)))
+                    rr = np.empty(rows_total // 2, np.uint8)
+                    ss = np.empty(rows_total // 64, np.float32)
+                    hip.check(lib.clv_set_device(0 if debug else d))
+                    hip.check(lib.clv_memcpy_d2h(rr.ctypes.data, rp, rr.nbytes, None))
+                    hip.check(lib.clv_memcpy_d2h(ss.ctypes.data, sp, ss.nbytes, None))
+                    hip.check(lib.clv_device_sync())
+                    full.append((rr, ss))
+                hip.check(lib.clv_set_device(0))
         finally:
             lib.clm4_sharded_destroy(ctx)
+        base = {"rows": rows, "rows_total": rows_total, "elapsed": elapsed, "per_k": per_k, "per_g": per_g, "rccl_ranks": ranks.value,
+                "settle_launches": settle}
+        if not args.full:
+            return base
+        same = all(np.array_equal(full[0][0], f[0]) and np.array_equal(full[0][1].view(np.uint32), f[1].view(np.uint32)) for f in full[1:])
         # shard 0's rows against a plain clm4_mvm of the same (regenerated) rows on device 0 (after the context released its memory)
         A0 = torch.empty(rows * cols // 2, dtype=torch.uint8, device="cuda:0")
         sA0 = torch.empty((rows // 64) * (cols // 64), dtype=torch.float32, device="cuda:0")
@@ -814,8 +834,7 @@ def one_process_measure(args, torch, hip, n: int) -> dict:
                    np.array_equal(sr0.cpu().numpy().view(np.uint32), full[0][1][: rows // 64].view(np.uint32)))
         del A0, sA0, r0, sr0
         torch.cuda.empty_cache()
-        return {"rows": rows, "rows_total": rows_total, "elapsed": elapsed, "per_k": per_k, "per_g": per_g, "verified": bool(same and ok0),
-                "rccl_ranks": ranks.value, "settle_launches": settle}
+        return {**base, "verified": bool(same and ok0)}
 
     rows = args.rows_per_gpu
     h = time_config(rows, args.steps)
@@ -840,7 +859,7 @@ def one_process_measure(args, torch, hip, n: int) -> dict:
             "parallelism": f"row-shard x{n}, one process drives all devices (clm4_sharded_mvm_enqueue): grouped in-place ncclAllGather pair per "
                            "step on a second stream per device, overlapped with the next step's kernel",
             "settle_launches": h["settle_launches"], "settle_ms": args.settle_ms,
-            "gathered_result_verified": h["verified"], "rccl_ranks": h["rccl_ranks"], "backend": backend(h),
+            **({"gathered_result_verified": h["verified"]} if args.full else {}), "rccl_ranks": h["rccl_ranks"], "backend": backend(h),
             "per_rank_kernel_ms": [round(v, 5) for v in h["per_k"]], "gather_ms_behind_kernel": [round(v, 5) for v in h["per_g"]],
             "gather_bytes_per_rank": rows // 2 + rows // 16,
             **({"DEBUG": "CLOVER_BENCH_DEBUG_ONE_GPU rehearsal: all shards on device 0, exchanges are copies -- not a measurement"} if debug else {}),
@@ -850,7 +869,7 @@ def one_process_measure(args, torch, hip, n: int) -> dict:
                      "traffic": None, "kernel": "k_m4_mvm64", "kernel_avg_ms": round(kern_avg_ms, 5), "algorithmic_bytes_per_launch": bytes_gpu},
     }
     c5_total = int(os.environ.get("CLOVER_BENCH_C5_ROWS", str(1 << 20)))
-    if args.preset is None and not args.no_c5:
+    if args.full and args.preset is None and not args.no_c5:
         if c5_total % (64 * n) != 0:
             out["c5"] = {"skipped": f"{c5_total} rows do not split into {n} equal shards of whole 64-row blocks"}
         else:
@@ -900,7 +919,7 @@ def run_product_loops(args, n: int) -> dict:
     """The product's own loops over the same N devices (`one_process`, `gemm_sharded`) in a CHILD process with a time limit: a side
     measurement -- RCCL through dlopen, ncclCommInitAll over N devices, paths no one-GPU box can rehearse with more than one rank --
     must never cost the headline line, whether it raises, crashes or hangs."""
-    cmd = [sys.executable, str(Path(__file__).resolve()), "--product-loops-child", str(n), "--gpus", str(n), "--steps", str(min(args.steps, SIDE_STEPS)), "--warmup", str(args.warmup),
+    cmd = [sys.executable, str(Path(__file__).resolve()), "--product-loops-child", str(n), "--full", "--gpus", str(n), "--steps", str(min(args.steps, SIDE_STEPS)), "--warmup", str(args.warmup),
            "--rows-per-gpu", str(args.rows_per_gpu), "--cols", str(args.cols), "--settle-ms", str(args.settle_ms), "--event-every", str(args.event_every),
            "--gemm-size", str(args.gemm_size), *(["--preset", args.preset] if args.preset else []), *(["--no-c5"] if args.no_c5 else [])]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",

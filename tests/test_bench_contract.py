@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 from pathlib import Path
 
 import pytest
@@ -10,6 +11,8 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config", "roofline")
+# what only --full measures or checks: a plain run's line carries none of it
+FULL_ONLY = ("ms_per_step_cold", "value_cold", "c5", "one_process", "gemm_sharded", "gemm", "extras", "cpu_baseline")
 
 
 def _run(args):
@@ -27,9 +30,32 @@ def test_help_runs_without_a_gpu():
     assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout and "--warmup" in out.stdout
 
 
+def test_help_offers_full():
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean():
+    """a plain run sets up, warms up, times its K steps and prints the line: the contract keys and nothing that only --full measures; the
+    whole process spends less than 30 s outside its W + K steps"""
+    t0 = time.perf_counter()
+    d = _run(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    outside = time.perf_counter() - t0 - (20 + 5) * d["ms_per_step"] * 1e-3
+    for k in CONTRACT:
+        assert k in d, k
+    assert not set(FULL_ONLY) & set(d), set(FULL_ONLY) & set(d)
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "GB/s" and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["config"]["rows_per_gpu"] == 65536 and d["config"]["cols"] == 65536 and d["config"]["settle_launches"] >= 8
+    assert "ms_per_step_cold" not in d["config"]["clock_settle"] and "kernel_avg_ms_cold" not in d["roofline"]
+    assert d["roofline"]["kernel_avg_ms"] > 0 and 0 < d["roofline"]["frac"] < 1
+    assert outside < 30, outside
+
+
 @pytest.mark.gpu
 def test_mvm_line():
-    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "8192", "--cols", "8192", "--cpu-sample-rows", "1024", "--no-c5"])
+    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "8192", "--cols", "8192", "--cpu-sample-rows", "1024", "--no-c5",
+              "--full"])
     for k in CONTRACT + ("cpu_baseline",):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "GB/s" and d["higher_is_better"] is True

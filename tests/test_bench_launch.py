@@ -15,7 +15,10 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
             "data", "config", "roofline")
-SMALL = ["--steps", "6", "--warmup", "2", "--rows-per-gpu", "4096", "--cols", "8192", "--no-cpu-baseline", "--no-extras"]
+SMALL = ["--steps", "6", "--warmup", "2", "--rows-per-gpu", "4096", "--cols", "8192", "--no-cpu-baseline", "--no-extras", "--full"]
+PLAIN = ["--steps", "6", "--warmup", "2", "--rows-per-gpu", "4096", "--cols", "8192"]
+# what only --full measures or checks: a plain run's line carries none of it
+FULL_ONLY = ("ms_per_step_cold", "value_cold", "c5", "one_process", "gemm_sharded", "gemm", "extras", "cpu_baseline")
 
 
 def run_bench(args, env_extra=None, launcher=None, timeout=600):
@@ -113,6 +116,26 @@ def test_product_loops_child_failure_costs_two_objects_not_the_line(monkeypatch)
     assert bench.run_product_loops(A, 8) == {"one_process": {"ms_per_step": 1.0}, "gemm_sharded": {"value": 2.0}}
 
 
+def test_product_loops_child_runs_the_full_measurements(monkeypatch):
+    """the product's loops are a --full measurement with c5 and checks of their own: the child they run in is started with --full"""
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    class A:
+        steps, warmup, rows_per_gpu, cols, settle_ms, event_every, gemm_size, preset, no_c5 = 20, 5, 65536, 65536, 60.0, 2, 8192, None, False
+    seen = {}
+
+    class Bad:
+        returncode, stdout, stderr = 1, "", "boom"
+
+    def fake_run(cmd, env=None, **kw):
+        seen["cmd"] = cmd
+        return Bad()
+    monkeypatch.setattr(bench.subprocess, "run", fake_run)
+    bench.run_product_loops(A, 2)
+    assert "--full" in seen["cmd"] and "--product-loops-child" in seen["cmd"]
+
+
 REHEARSAL = {"CLOVER_BENCH_DEBUG_ONE_GPU": "1", "CLOVER_BENCH_C5_ROWS": "16384", "CLOVER_BENCH_GEMM_SIZE": "1024"}
 
 
@@ -137,7 +160,7 @@ def check_product_loops(out, n, rehearsal, gemm_size=1024):
 
 
 def check_c5(out, n, rows_total=16384, cols=8192):
-    """the object a plain `bench.py --gpus N` adds behind the headline: BASELINE configs[4]'s matrix split N ways (here shrunk)"""
+    """the object `bench.py --gpus N --full` adds behind the headline: BASELINE configs[4]'s matrix split N ways (here shrunk)"""
     c5 = out["c5"]
     assert c5["scaling"] == "strong" and c5["n_gpus"] == n and c5["rows_per_gpu"] == rows_total // n and c5["cols"] == cols
     assert c5["algorithmic_bytes_per_step"] == rows_total * cols // 2 + 4 * (rows_total // 64) * (cols // 64) + cols * 9 // 16 + rows_total * 9 // 16
@@ -262,9 +285,9 @@ def test_gpus1_preset_c5_weak():
 
 @pytest.mark.gpu
 def test_default_line_carries_baseline_config_4():
-    """plain `bench.py --gpus 1 --steps K --warmup W` (what the driver runs): c3 headline with cold + settled figures, and the c5 object =
-    the whole 2^20 x 2^16 matrix (32 GiB) on this one GPU"""
-    out = json_line(run_bench(["--gpus", "1", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-extras"]))
+    """`bench.py --gpus 1 --steps K --warmup W --full`: c3 headline with cold + settled figures, and the c5 object = the whole 2^20 x 2^16
+    matrix (32 GiB) on this one GPU"""
+    out = json_line(run_bench(["--gpus", "1", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-extras", "--full"]))
     assert out["config"]["rows_per_gpu"] == 65536 and out["config"]["settle_launches"] >= 8 and "degraded" not in out
     assert out["ms_per_step_cold"] >= out["ms_per_step"] * 0.9 and out["value_cold"] > 0
     c5 = check_c5(out, 1, 1 << 20, 65536)
@@ -273,11 +296,32 @@ def test_default_line_carries_baseline_config_4():
 
 @pytest.mark.gpu
 def test_steps_sets_the_headline_and_caps_the_side_measurements():
-    """--steps K times K headline steps; the cold pass, the c5 object and the product's loops behind it time min(K, 20) each, so that
-    the run's length follows K and ms_per_step alone"""
+    """--steps K times K headline steps; with --full the cold pass, the c5 object and the product's loops behind it time min(K, 20) each,
+    so that the run's length follows K and ms_per_step alone"""
     out = json_line(run_bench(["--gpus", "1", "--steps", "48", "--warmup", "2", "--rows-per-gpu", "4096", "--cols", "8192", "--no-cpu-baseline",
-                               "--no-extras"], {"CLOVER_BENCH_C5_ROWS": "16384", "CLOVER_BENCH_GEMM_SIZE": "1024"}))
+                               "--no-extras", "--full"], {"CLOVER_BENCH_C5_ROWS": "16384", "CLOVER_BENCH_GEMM_SIZE": "1024"}))
     assert out["steps"] == 48 and out["ms_per_step"] > 0 and out["ms_per_step_cold"] > 0
     assert "min(K, 20) = 20 " in out["config"]["clock_settle"]
     assert out["c5"]["steps"] == 20 and out["c5"]["ms_per_step"] > 0
     assert out["one_process"]["steps"] == 20 and out["one_process"]["c5"]["steps"] == 20
+
+
+@pytest.mark.gpu
+def test_two_rank_rehearsal_plain_line_is_lean():
+    """without --full the ranks time their steps and rank 0 prints the line: no blocking gather timing, no check of the gathered result, none
+    of the objects behind the headline"""
+    out = json_line(run_bench(["--gpus", "2", *PLAIN], REHEARSAL))
+    assert out["n_gpus"] == 2 and out["steps"] == 6 and out["warmup"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert not set(FULL_ONLY) & set(out), set(FULL_ONLY) & set(out)
+    cfg = out["config"]
+    assert cfg["mode"] == "ranks" and len(cfg["per_rank_kernel_ms"]) == 2 and cfg["settle_launches"] >= 8
+    assert "gathered_result_verified" not in cfg and "gather_us_blocking" not in cfg
+    assert out["degraded"] is True and out["roofline"]["kernel_avg_ms"] > 0
+
+
+@pytest.mark.gpu
+def test_one_process_plain_line_is_lean():
+    out = json_line(run_bench(["--gpus", "2", "--mode", "one-process", *PLAIN], REHEARSAL))
+    assert out["n_gpus"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0 and "c5" not in out
+    cfg = out["config"]
+    assert cfg["mode"] == "one-process" and "gathered_result_verified" not in cfg and len(cfg["per_rank_kernel_ms"]) == 2

@@ -20,7 +20,7 @@ MB_SIZES=8192x8192,16384x16384,4096x8192 MB_VARIANTS=1,5,7,8 MB_SKIP_READ=1 time
 for f in "" "-DCLOVER_HIP_EXPLICIT_SYNC"; do
   g++ -std=c++11 -O2 -DCLOVER_STOCHASTIC_ROUNDING_DISABLED=1 $f -Iinclude tools/iht_dropin.cpp -o /tmp/iht_dropin -Lclover_amd/lib -lclover_hip -Wl,-rpath,$PWD/clover_amd/lib -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib && timeout 300 /tmp/iht_dropin >> $O/iht_dropin.json 2>> $O/iht_dropin.err
 done
-CLOVER_BENCH_DEBUG_ONE_GPU=1 CLOVER_BENCH_C5_ROWS=16384 timeout 600 python bench.py --gpus 2 --steps 6 --warmup 2 --rows-per-gpu 4096 --cols 8192 --no-extras --cpu-sample-rows 1024 > $O/bench_rehearsal2.json 2> $O/bench_rehearsal2.err
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err
+CLOVER_BENCH_DEBUG_ONE_GPU=1 CLOVER_BENCH_C5_ROWS=16384 timeout 600 python bench.py --gpus 2 --steps 6 --warmup 2 --rows-per-gpu 4096 --cols 8192 --no-extras --cpu-sample-rows 1024 --full > $O/bench_rehearsal2.json 2> $O/bench_rehearsal2.err
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench_n1.json 2> $O/bench_n1.err
 echo "batch done"; ls -la $O
 for f in $O/kb_*.json $O/microbench_L8.json $O/iht_dropin.json; do echo "== $f"; cat $f; done 2>/dev/null | head -150

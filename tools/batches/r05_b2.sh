@@ -9,7 +9,7 @@ timeout 200 python tools/dot_fast_ab.py >> $O/dot_fast_ab.jsonl 2>> $O/dot_fast_
 cat $O/dot_fast_ab.jsonl
 ( timeout 1500 python -m pytest tests/test_bench_launch.py tests/test_next_rows.py tests/test_sharded_cpp.py tests/test_cpp_dropin.py tests/test_gpu_large.py -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log )
 tail -8 $O/pytest.log
-timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --full > $O/bench_n1.json 2> $O/bench_n1.err
 python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r05_b2/bench_n1.json") if l.startswith("{")][-1])
