@@ -28,17 +28,30 @@ __device__ __forceinline__ uint32_t mag_key(uint32_t w, int e, float s7)
     return __float_as_uint(__builtin_fabsf(s7 * (float)unpack1(w, e)));
 }
 
-// The large-n kernels below serve both element widths.  BITS = 4: CloverVector4, 8 elements per word, |value| = |f32(s/7) * q|
+// |f32(h)| of a binary16 bit pattern as fp32 bits: CloverVector16::getAbs (CloverVector16.h:96-102), the exact widening (subnormals too)
+__device__ __forceinline__ uint32_t f16_abs_key(uint16_t h)
+{
+    _Float16 v;
+    const uint16_t a = h & 0x7FFFu;
+    __builtin_memcpy(&v, &a, 2);
+    return __float_as_uint((float)v);
+}
+
+// The large-n kernels below serve every element width.  BITS = 16: CloverVector16, 2 raw binary16 values per word, no scales,
+// |value| = |f32(h)|.  BITS = 4: CloverVector4, 8 elements per word, |value| = |f32(s/7) * q|
 // (CloverVector4::get, :206-209).  BITS = 8: CloverVector8 (same algorithm, CloverVector8.h:1680-1740), 4 elements per word,
 // |value| = |f32((float)q * s) / 127| (CloverVector8::get, :137-140).
 template <int BITS>
 struct ThreshElems {
     static constexpr int EPW = 32 / BITS;                                   // elements per 32-bit word
     static constexpr int WPB = 64 / EPW;                                    // words per 64-element block
-    __device__ static __forceinline__ uint32_t mask(int e) { return BITS == 4 ? 0xFu << nib_shift(e) : 0xFFu << (8 * e); }
+    __device__ static __forceinline__ uint32_t mask(int e) { return BITS == 4 ? 0xFu << nib_shift(e) : BITS == 8 ? 0xFFu << (8 * e) : 0xFFFFu << (16 * e); }
+    // the scale of word i's block; the 16-bit elements have none (s is NULL there)
+    __device__ static __forceinline__ float scale(const float *__restrict__ s, uint64_t i) { return BITS == 16 ? 0.0f : s[i / WPB]; }
     __device__ static __forceinline__ uint32_t key(uint32_t w, int e, float sc)
     {
         if (BITS == 4) return mag_key(w, e, div7(sc));
+        if (BITS == 16) return f16_abs_key((uint16_t)(w >> (16 * e)));
         const float q = (float)((int)(w << (24 - 8 * e)) >> 24);
         return __float_as_uint(__builtin_fabsf(div127(q * sc)));
     }
@@ -59,7 +72,7 @@ __global__ __launch_bounds__(256) void k_thresh_hist(const uint32_t *__restrict_
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += stride) {
         const uint32_t w = q[i];
-        const float sc = s[i / E::WPB];
+        const float sc = E::scale(s, i);
 #pragma unroll
         for (int e = 0; e < E::EPW; e++) {
             if (i * E::EPW + e >= n) break;
@@ -126,7 +139,7 @@ __global__ __launch_bounds__(256) void k_thresh_count_ties(const uint32_t *__res
         const uint64_t i = w0 + k;
         if (i * E::EPW >= n) break;
         const uint32_t w = q[i];
-        const float sc = s[i / E::WPB];
+        const float sc = E::scale(s, i);
 #pragma unroll
         for (int e = 0; e < E::EPW; e++) if (i * E::EPW + e < n && E::key(w, e, sc) == tau) c++;
     }
@@ -171,7 +184,7 @@ __global__ __launch_bounds__(256) void k_thresh_apply(uint32_t *__restrict__ q, 
         tie_mask[k] = 0;
         if (i * E::EPW >= n) continue;
         const uint32_t w = q[i];
-        const float sc = s[i / E::WPB];
+        const float sc = E::scale(s, i);
         uint32_t outw = 0;
 #pragma unroll
         for (int e = 0; e < E::EPW; e++) {
@@ -453,7 +466,7 @@ __global__ __launch_bounds__(TS_THREADS) void k_thresh8_small(uint32_t *__restri
         const uint32_t i = w0 + j;
         const bool in = j < W && i < nwords;
         words[j] = in ? q[i] : 0u;
-        const float sc = in ? s[i / E::WPB] : 0.0f;
+        const float sc = in ? E::scale(s, i) : 0.0f;
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             keys[j][e] = E::key(words[j], e, sc);
@@ -1455,7 +1468,7 @@ __global__ __launch_bounds__(256) void k_thr_ref_keys(const uint32_t *__restrict
     const uint64_t nwords = (n + E::EPW - 1) / E::EPW, stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += stride) {
         const uint32_t w = q[i];
-        const float sc = s[i / E::WPB];
+        const float sc = E::scale(s, i);
 #pragma unroll
         for (int e = 0; e < E::EPW; e++)
             if (i * E::EPW + e < n) vals[i * E::EPW + e] = __uint_as_float(E::key(w, e, sc));
@@ -1764,4 +1777,36 @@ extern "C" int clv8_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64
     CLV_REQUIRE(n < (1ull << 32), "clv8_threshold_mode: vectors of 2^32 or more elements are not supported");
     if (k >= n || n == 0) return CLV_OK;
     return threshold_reference<8>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream));
+}
+
+// CloverVector16::threshold(K) / threshold_min_heap (CloverVector16.h:612-768): the same selection on |f32(h)|, two elements per word and no
+// scales.  Every n takes the large-vector path (the one-workgroup kernels above are written for the 4- and 8-bit word layouts).
+extern "C" uint64_t clv_f16_threshold_workspace_bytes(uint64_t n_pad)
+{
+    const uint64_t blocks = (n_pad / 2 + TH_WORDS_PER_BLOCK - 1) / TH_WORDS_PER_BLOCK;
+    return 4096 * sizeof(uint32_t) + 256 + blocks * sizeof(uint32_t) + 256;
+}
+
+extern "C" int clv_f16_threshold_mode(uint16_t *h, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream)
+{
+    CLV_REQUIRE(mode == CLV_THRESHOLD_FAST || mode == CLV_THRESHOLD_REFERENCE, "clv_f16_threshold_mode: unknown mode %d", mode);
+    CLV_REQUIRE(h, "clv_f16_threshold_mode: null pointer");
+    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv_f16_threshold_mode: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
+    CLV_REQUIRE(n < (1ull << 32), "clv_f16_threshold_mode: vectors of 2^32 or more elements are not supported");
+    if (k >= n || n == 0) return CLV_OK;
+    if (mode == CLV_THRESHOLD_REFERENCE) return threshold_reference<16>((uint32_t *)h, nullptr, n, n_pad, k, workspace, as_stream(stream));
+    if (!workspace) {
+        int rc = clv_internal_workspace(&workspace, clv_f16_threshold_workspace_bytes(n_pad), as_stream(stream));
+        if (rc) return rc;
+    }
+    return threshold_large<16>((uint32_t *)h, nullptr, n, k, workspace, as_stream(stream));
+}
+
+extern "C" int clv_f16_threshold_heap(uint16_t *h, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream)
+{
+    CLV_REQUIRE(h && heap_dev, "clv_f16_threshold_heap: null pointer");
+    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv_f16_threshold_heap: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
+    CLV_REQUIRE(n < (1ull << 32), "clv_f16_threshold_heap: vectors of 2^32 or more elements are not supported");
+    CLV_REQUIRE(k >= 1 && k <= n, "clv_f16_threshold_heap: k=%llu must lie in 1 .. n=%llu", (unsigned long long)k, (unsigned long long)n);
+    return threshold_reference<16>((uint32_t *)h, nullptr, n, n_pad, k, workspace, as_stream(stream), (uint2 *)heap_dev);
 }

@@ -94,6 +94,18 @@ SIGNATURES = {
     "clm8_mvm": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clm8_mvm_f32": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "clm8_transpose": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "clv_f16_quantize": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "clv_f16_restore": (C.c_int, [_vp, _u64, _vp, _vp]),
+    "clv_f16_scale_and_add": (C.c_int, [_vp, _vp, C.c_float, _u64, _vp, _vp]),
+    "clv_f16_dot_workspace_bytes": (_u64, [_u64]),
+    "clv_f16_dot": (C.c_int, [_vp, _vp, _u64, C.c_int, _vp, _vp, _vp]),
+    "clv_f16_threshold_workspace_bytes": (_u64, [_u64]),
+    "clv_f16_threshold_mode": (C.c_int, [_vp, _u64, _u64, _u64, C.c_int, _vp, _vp]),
+    "clv_f16_threshold_heap": (C.c_int, [_vp, _u64, _u64, _u64, _vp, _vp, _vp]),
+    "clm_f16_quantize": (C.c_int, [_vp, _u64, _u64, _vp, _vp]),
+    "clm_f16_mvm": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm_f16_mvm_f32": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm_f16_transpose": (C.c_int, [_vp, _u64, _u64, _vp, _vp]),
     "clm4_iht": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
                           C.c_float, C.c_int, _vp, _vp]),
     "clm4_shard_partition": (C.c_int, [_u64, C.c_int, C.c_int, C.POINTER(_u64), C.POINTER(_u64)]),
@@ -399,6 +411,63 @@ class CloverHip:
         dt, dst = self.alloc(max(rows * cols, 1)), self.alloc(max((rows // 64) * (cols // 64) * 4, 4))
         self.check(self.lib.clm8_transpose(dq.ptr, ds.ptr, rows, cols, dt.ptr, dst.ptr, None))
         return dt.download(np.int8, rows * cols), dst.download(np.float32, (rows // 64) * (cols // 64))
+
+    # -- CloverVector16 / CloverMatrix16 (raw binary16 bit patterns as uint16) ---------------------
+    def f16_quantize(self, x: np.ndarray) -> np.ndarray:
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        dx, dh = self.to_device(x), self.alloc(max(2 * x.size, 2))
+        self.check(self.lib.clv_f16_quantize(dx.ptr, x.size, dh.ptr, None))
+        return dh.download(np.uint16, x.size)
+
+    def f16_restore(self, h: np.ndarray) -> np.ndarray:
+        dh, dx = self.to_device(h), self.alloc(max(4 * h.size, 4))
+        self.check(self.lib.clv_f16_restore(dh.ptr, h.size, dx.ptr, None))
+        return dx.download(np.float32, h.size)
+
+    def f16_scale_and_add(self, u, v, a: float, in_place: bool = False) -> np.ndarray:
+        du, dv = self.to_device(u), self.to_device(v)
+        dr = du if in_place else self.alloc(max(2 * u.size, 2))
+        self.check(self.lib.clv_f16_scale_and_add(du.ptr, dv.ptr, a, u.size, dr.ptr, None))
+        return dr.download(np.uint16, u.size)
+
+    def f16_dot(self, u, v, mode: int = DOT_EXACT) -> np.float32:
+        du, dv, out = self.to_device(u), self.to_device(v), self.alloc(4)
+        self.check(self.lib.clv_f16_dot(du.ptr, dv.ptr, u.size, mode, out.ptr, None, None))
+        return out.download(np.float32, 1)[0]
+
+    def f16_threshold(self, h, n: int, k: int, mode: int = THRESHOLD_FAST) -> np.ndarray:
+        dh = self.to_device(h)
+        self.check(self.lib.clv_f16_threshold_mode(dh.ptr, n, h.size, k, mode, None, None))
+        return dh.download(np.uint16, h.size)
+
+    def f16_threshold_heap(self, h, n: int, k: int):
+        """(thresholded vector, heap values fp32[k], heap indices uint32[k]) of clv_f16_threshold_heap"""
+        dh, dheap = self.to_device(h), self.alloc(8 * k)
+        self.check(self.lib.clv_f16_threshold_heap(dh.ptr, n, h.size, k, dheap.ptr, None, None))
+        heap = dheap.download(np.uint32, 2 * k).reshape(k, 2)
+        return dh.download(np.uint16, h.size), heap[:, 0].copy().view(np.float32), heap[:, 1].copy()
+
+    def mf16_quantize(self, A: np.ndarray) -> np.ndarray:
+        A = np.ascontiguousarray(A, dtype=np.float32)
+        rows, cols = A.shape
+        dA, dh = self.to_device(A), self.alloc(max(2 * rows * cols, 2))
+        self.check(self.lib.clm_f16_quantize(dA.ptr, rows, cols, dh.ptr, None))
+        return dh.download(np.uint16, rows * cols)
+
+    def mf16_mvm(self, hA, rows, cols, hx) -> np.ndarray:
+        dA, dx, dr = self.to_device(hA), self.to_device(hx), self.alloc(max(2 * rows, 2))
+        self.check(self.lib.clm_f16_mvm(dA.ptr, rows, cols, dx.ptr, dr.ptr, None))
+        return dr.download(np.uint16, rows)
+
+    def mf16_mvm_f32(self, hA, rows, cols, x) -> np.ndarray:
+        dA, dx, dr = self.to_device(hA), self.to_device(np.ascontiguousarray(x, dtype=np.float32)), self.alloc(max(4 * rows, 4))
+        self.check(self.lib.clm_f16_mvm_f32(dA.ptr, rows, cols, dx.ptr, dr.ptr, None))
+        return dr.download(np.float32, rows)
+
+    def mf16_transpose(self, h, rows, cols) -> np.ndarray:
+        dh, dt = self.to_device(h), self.alloc(max(2 * rows * cols, 2))
+        self.check(self.lib.clm_f16_transpose(dh.ptr, rows, cols, dt.ptr, None))
+        return dt.download(np.uint16, rows * cols)
 
     def m4_gemm_i32(self, qA, M, K, qB, N, kb_begin=0, kb_count=None) -> np.ndarray:
         b = [self.to_device(a) for a in (qA, qB)]

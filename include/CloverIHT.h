@@ -13,6 +13,7 @@
 
 #include "CloverMatrix4.h"
 #include "CloverMatrix8.h"       /* Q_IHT<CloverMatrix8, CloverVector8> / Q_GD<...>: the generic templates below */
+#include "CloverMatrix16.h"      /* Q_IHT<CloverMatrix16, CloverVector16> / Q_GD<...>: the same templates */
 #include "CloverVector4.h"
 
 /* Generic forms, for any container pair with the reference's method names (the five steps of 01_measure.h:930-944):

@@ -305,6 +305,43 @@ int  clm8_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols
 /* CloverMatrix8::transpose / transpose_parallel (CloverMatrix8.h:1312-1386): qt(j,i) = q(i,j), the tile scale grid transposed.
  * q is rows x cols, qt is cols x rows; not in place.  Exact. */
 int  clm8_transpose(const int8_t *q, const float *s, uint64_t rows, uint64_t cols, int8_t *qt, float *st, void *stream);
+/* ---- CloverVector16 / CloverMatrix16: the half-precision containers ----------------------------- */
+/* Storage (CloverVector16.h:35-66, CloverMatrix16.h:36-66): raw IEEE binary16 bit patterns in uint16_t, no scales.  Vector: n_pad values
+ * (multiple of 128, the padding zero); matrix: rows x cols values row-major.  Every pointer is 16-byte aligned.
+ * clv_f16_quantize = CloverVector16::quantize (CloverVector16.h:212-243): fp32 -> f16, round to nearest even, subnormal results kept
+ * (_mm256_cvtps_ph(.., 0)); NaN stays NaN (payload not specified).  clv_f16_restore = ::restore (:279-307), the exact widening. */
+int  clv_f16_quantize(const float *x, uint64_t n_pad, uint16_t *h, void *stream);
+int  clv_f16_restore(const uint16_t *h, uint64_t n_pad, float *x, void *stream);
+/* CloverVector16::scaleAndAdd (CloverVector16.h:309-386; _parallel :388-470): r = f16(fma(f32(v), a, f32(u))), one fused fp32 fma per
+ * element; r may be u (the in-place overload). */
+int  clv_f16_scale_and_add(const uint16_t *u, const uint16_t *v, float a, uint64_t n_pad, uint16_t *r, void *stream);
+/* CloverVector16::dot (CloverVector16.h:473-530): 32 fp32 fma chains, element j in chain j mod 32 (accumulator (j mod 32) / 8, lane j mod 8),
+ * (acc0 + acc1) + (acc2 + acc3), then _mm256_haddf32_ps (CloverBase.h:149-157).  CLV_DOT_EXACT: that order, bit for bit (n / 32 dependent
+ * fmas per chain: latency-bound by definition); CLV_DOT_FAST (= dot_parallel, :532-610): the same exact products in a tree order, one
+ * launch, memory-bound (first call on a stream outside a capture, as for clv4_dot).  Neither mode uses `workspace`; the query returns 0. */
+uint64_t clv_f16_dot_workspace_bytes(uint64_t n_pad);
+int  clv_f16_dot(const uint16_t *u, const uint16_t *v, uint64_t n_pad, int mode, float *out_dev, void *workspace, void *stream);
+/* CloverVector16::threshold (CloverVector16.h:612-626) and ::threshold_min_heap (:628-673) on |f32(h)|: CLV_THRESHOLD_FAST keeps the same
+ * multiset of magnitudes with lowest-index ties, CLV_THRESHOLD_REFERENCE the reference's survivors index for index (its heap walk);
+ * survivors keep their bits, the other elements below n become 0x0000.  Workspace (NULL = the stream's scratch):
+ * clv_f16_threshold_workspace_bytes(n_pad) for FAST, clv_threshold_reference_workspace_bytes_k(n_pad, k) for REFERENCE and the heap form
+ * (heap_dev: k entries {fp32 |value|, uint32 index}, 1 <= k <= n). */
+uint64_t clv_f16_threshold_workspace_bytes(uint64_t n_pad);
+int  clv_f16_threshold_mode(uint16_t *h, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream);
+int  clv_f16_threshold_heap(uint16_t *h, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream);
+/* CloverMatrix16::quantize (CloverMatrix16.h:383-410): the vector conversion over rows * cols elements (multiples of 128). */
+int  clm_f16_quantize(const float *A, uint64_t rows, uint64_t cols, uint16_t *h, void *stream);
+/* CloverMatrix16::mvm(const CloverVector16 &, CloverVector16 &) (CloverMatrix16.h:230-308; mvm_parallel :133-228, the same order per row):
+ * every row is the dot above against x (cols values), the fp32 row value rounded to f16 (RNE).  r: rows values.  cols is a multiple of
+ * 128; any row count is accepted (a row shard of a matrix at a pointer offset).  Bit-identical. */
+int  clm_f16_mvm(const uint16_t *A, uint64_t rows, uint64_t cols, const uint16_t *x, uint16_t *r, void *stream);
+/* CloverMatrix16::mvm(const CloverVector32 &, CloverVector32 &) (CloverMatrix16.h:321-381): the same chains and tree with x as fp32, the
+ * row value stored as fp32.  Bit-identical. */
+int  clm_f16_mvm_f32(const uint16_t *A, uint64_t rows, uint64_t cols, const float *x, float *r, void *stream);
+/* CloverMatrix16::transpose / transpose_parallel (CloverMatrix16.h:424-474): ht(j,i) = h(i,j); h is rows x cols, ht is cols x rows
+ * (multiples of 8: a whole matrix has multiples of 128); not in place.  Exact. */
+int  clm_f16_transpose(const uint16_t *h, uint64_t rows, uint64_t cols, uint16_t *ht, void *stream);
+
 /* Q_IHT / Q_GD (test/performance/01_measure.h:923-946, 999-1021): x.clear(), then `iterations` times
  *   t1 = Phi*x; t2 = y - t1; t3 = PhiT*t2; x = x + mu*t3; [threshold(K)]          (threshold != 0: IHT, else GD)
  * entirely on the device.  Phi is m x n, PhiT its transpose (n x m), x has n (padded) / x_len (logical)

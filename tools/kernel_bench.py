@@ -3,7 +3,9 @@
 
 Algorithmic bytes per element follow SURVEY 8(d): quantize/restore 4.5625, dot 1.125, scaleAndAdd 1.6875,
 threshold 1.125 (nibbles + scales read and written once each), transpose 2 x (1/2 + 4/4096), matrix quantize 4.5625;
-CloverMatrix8 (m8_*): quantize 4 + 1 + 4/4096, transpose 2 x (1 + 4/4096), mvm 1 + 4/4096 per matrix element."""
+CloverMatrix8 (m8_*): quantize 4 + 1 + 4/4096, transpose 2 x (1 + 4/4096), mvm 1 + 4/4096 per matrix element;
+CloverVector16 / CloverMatrix16 (f16_*): 2 bytes per element and no scales -- quantize / restore 4 + 2, scaleAndAdd 2 + 2 + 2, dot 2 + 2,
+threshold 2 + 2 (read once, written once), matrix quantize 4 + 2, transpose 2 + 2, mvm 2 per matrix element + x + r."""
 import ctypes as C
 import json
 import os
@@ -215,4 +217,54 @@ for N8 in (8192, 16384):
     rec(f"m8_q_iht_iteration_fast_threshold_N{N8}", itb, lambda: iht8_iteration(THRESHOLD_FAST), reps=5,
         extra={"note": "bytes = the two matrices only; threshold with lowest-index ties (-DCLOVER_FAST)"})
     del P, sP, PT, sPT, vx, svx, vt3, svt3, vy, svy, vt1, svt1, vt2, svt2
+# ---- CloverVector16 / CloverMatrix16: raw binary16, 2 bytes per element, no scales
+if not ONLY or "f16" in ONLY:
+    SLAB = 1 << 28
+
+    def f16_fill(dst, count, seed):
+        """count f16 values = quantized random fp32 integers in [-10, 10], through a 1 GiB fp32 slab"""
+        src = hip.alloc(4 * min(SLAB, count))
+        for o in range(0, count, SLAB):
+            c = min(SLAB, count - o)
+            hip.check(lib.clv_fill_random_ints_f32(src.ptr, c, 10, seed, o, None))
+            hip.check(lib.clv_f16_quantize(src.ptr, c, dst.ptr + 2 * o, None))
+        hip.sync()
+
+    for logn in (24, 30):
+        n = 1 << logn
+        x = hip.alloc(4 * n)
+        hip.check(lib.clv_fill_random_ints_f32(x.ptr, n, 10, 61, 0, None))
+        hu, hv, hr, out = hip.alloc(2 * n), hip.alloc(2 * n), hip.alloc(2 * n), hip.alloc(8)
+        f16_fill(hv, n, 62)
+        rec(f"f16_quantize_n2^{logn}", 6 * n, lambda: hip.check(lib.clv_f16_quantize(x.ptr, n, hu.ptr, None)))
+        rec(f"f16_scale_and_add_n2^{logn}", 6 * n, lambda: hip.check(lib.clv_f16_scale_and_add(hu.ptr, hv.ptr, 0.5, n, hr.ptr, None)))
+        rec(f"f16_dot_fast_n2^{logn}", 4 * n, lambda: hip.check(lib.clv_f16_dot(hu.ptr, hv.ptr, n, DOT_FAST, out.ptr, None, None)))
+        rec(f"f16_dot_exact_n2^{logn}", 4 * n, lambda: hip.check(lib.clv_f16_dot(hu.ptr, hv.ptr, n, DOT_EXACT, out.ptr, None, None)), reps=1,
+            extra={"note": "32 sequential fma chains of n / 32 steps: latency-bound by definition"})
+        rec(f"f16_threshold_fast_k25pct_n2^{logn}", 4 * n, lambda: hip.check(lib.clv_f16_threshold_mode(hr.ptr, n, n, n // 4, THRESHOLD_FAST, None, None)),
+            reps=3, extra={"note": "the large-vector radix select (nine launches, four passes over the values); bytes = the values read and "
+                                   "written once; thresholded in place, so calls after the first find the vector already thresholded"})
+        rec(f"f16_restore_n2^{logn}", 6 * n, lambda: hip.check(lib.clv_f16_restore(hu.ptr, n, x.ptr, None)))
+        del x, hu, hv, hr
+    for nf in (8192, 32768, 65536):
+        vals = nf * nf
+        hA = hip.alloc(2 * vals)
+        if nf == 65536:
+            A32 = hip.alloc(4 * vals)
+            hip.check(lib.clv_fill_random_ints_f32(A32.ptr, vals, 10, 63, 0, None))
+            rec(f"f16_matrix_quantize_{nf}^2", 6 * vals, lambda: hip.check(lib.clm_f16_quantize(A32.ptr, nf, nf, hA.ptr, None)), reps=3)
+            hip.check(lib.clm_f16_quantize(A32.ptr, nf, nf, hA.ptr, None))
+            hip.sync()
+            del A32
+            hT = hip.alloc(2 * vals)
+            rec(f"f16_transpose_{nf}^2", 4 * vals, lambda: hip.check(lib.clm_f16_transpose(hA.ptr, nf, nf, hT.ptr, None)), reps=3)
+            del hT
+        else:
+            f16_fill(hA, vals, 63)
+        hx, hr16, xf, rf = hip.alloc(2 * nf), hip.alloc(2 * nf), hip.alloc(4 * nf), hip.alloc(4 * nf)
+        f16_fill(hx, nf, 64)
+        hip.check(lib.clv_fill_random_ints_f32(xf.ptr, nf, 10, 65, 0, None))
+        rec(f"f16_mvm_{nf}^2", 2 * vals + 4 * nf, lambda: hip.check(lib.clm_f16_mvm(hA.ptr, nf, nf, hx.ptr, hr16.ptr, None)))
+        rec(f"f16_mvm_f32_{nf}^2", 2 * vals + 8 * nf, lambda: hip.check(lib.clm_f16_mvm_f32(hA.ptr, nf, nf, xf.ptr, rf.ptr, None)))
+        del hA, hx, hr16, xf, rf
 print(json.dumps(res, indent=1))
