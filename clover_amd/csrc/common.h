@@ -28,6 +28,10 @@ void clv_set_error(const char *fmt, ...);
         }                                \
     } while (0)
 
+// a caller's workspace is cast to f32x4 / u64 by the kernels: NULL (the library's own scratch) or 16-byte aligned
+#define CLV_REQUIRE_WORKSPACE(fn, ws) \
+    CLV_REQUIRE(!(ws) || ((uintptr_t)(ws) & 15) == 0, "%s: workspace must be 16-byte aligned", fn)
+
 #define CLV_LAUNCH_CHECK()                                                             \
     do {                                                                               \
         hipError_t e__ = hipGetLastError();                                            \

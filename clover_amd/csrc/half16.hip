@@ -406,11 +406,11 @@ extern "C" uint64_t clv_f16_dot_workspace_bytes(uint64_t n_pad)
 
 extern "C" int clv_f16_dot(const uint16_t *u, const uint16_t *v, uint64_t n_pad, int mode, float *out_dev, void *workspace, void *stream)
 {
-    (void)workspace;
     CLV_REQUIRE(u && v && out_dev, "clv_f16_dot: null pointer");
     CLV_REQUIRE(F16_ALIGNED(u) && F16_ALIGNED(v), "clv_f16_dot: pointers must be 16-byte aligned");
     CLV_REQUIRE(n_pad % 128 == 0, "clv_f16_dot: n_pad=%llu is not a multiple of 128", (unsigned long long)n_pad);
     CLV_REQUIRE(mode == CLV_DOT_EXACT || mode == CLV_DOT_FAST, "clv_f16_dot: unknown mode %d", mode);
+    CLV_REQUIRE_WORKSPACE("clv_f16_dot", workspace);      // unused, but one rule for every workspace argument
     hipStream_t st = as_stream(stream);
     if (!n_pad) { CLV_HIP(hipMemsetAsync(out_dev, 0, sizeof(float), st)); return CLV_OK; }
     if (mode == CLV_DOT_EXACT) {

@@ -652,6 +652,7 @@ extern "C" int clv8_dot(const int8_t *qu, const float *su, const int8_t *qv, con
     CLV_REQUIRE(qu && su && qv && sv && out_dev, "clv8_dot: null pointer");
     CLV_REQUIRE(n_pad % 128 == 0, "clv8_dot: n_pad=%llu is not a multiple of 128", (unsigned long long)n_pad);
     CLV_REQUIRE(mode == CLV_DOT_EXACT || mode == CLV_DOT_FAST, "clv8_dot: unknown mode %d", mode);
+    CLV_REQUIRE_WORKSPACE("clv8_dot", workspace);
     hipStream_t st = as_stream(stream);
     if (!n_pad) { CLV_HIP(hipMemsetAsync(out_dev, 0, sizeof(float), st)); return CLV_OK; }
     if (mode == CLV_DOT_EXACT) {

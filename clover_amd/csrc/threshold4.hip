@@ -1424,6 +1424,7 @@ extern "C" int clv4_threshold(int8_t *q, const float *s, uint64_t n, uint64_t n_
     CLV_REQUIRE(q && s, "clv4_threshold: null pointer");
     CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv4_threshold: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
     CLV_REQUIRE(n < (1ull << 32), "clv4_threshold: vectors of 2^32 or more elements are not supported");
+    CLV_REQUIRE_WORKSPACE("clv4_threshold", workspace);
     hipStream_t st = as_stream(stream);
     if (k >= n || n == 0) return CLV_OK;                       // everything survives
     if (n_pad <= (uint64_t)TS_THREADS * TS_MAXW * 8) {
@@ -1718,6 +1719,7 @@ extern "C" int clv4_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64
     CLV_REQUIRE(q && s, "clv4_threshold_mode: null pointer");
     CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv4_threshold_mode: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
     CLV_REQUIRE(n < (1ull << 32), "clv4_threshold_mode: vectors of 2^32 or more elements are not supported");
+    CLV_REQUIRE_WORKSPACE("clv4_threshold_mode", workspace);
     if (k >= n || n == 0) return CLV_OK;
     return threshold_reference<4>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream));
 }
@@ -1731,6 +1733,7 @@ static int threshold_heap(const char *fn, int8_t *q, const float *s, uint64_t n,
     CLV_REQUIRE(n < (1ull << 32), "%s: vectors of 2^32 or more elements are not supported", fn);
     // the reference's loop copies the first k elements into the heap unconditionally: k > n reads beyond the vector there -- rejected here
     CLV_REQUIRE(k >= 1 && k <= n, "%s: k=%llu must lie in 1 .. n=%llu", fn, (unsigned long long)k, (unsigned long long)n);
+    CLV_REQUIRE_WORKSPACE(fn, workspace);
     return threshold_reference<BITS>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream), (uint2 *)heap_dev);
 }
 extern "C" int clv4_threshold_heap(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream)
@@ -1748,6 +1751,7 @@ extern "C" int clv8_threshold(int8_t *q, const float *s, uint64_t n, uint64_t n_
     CLV_REQUIRE(q && s, "clv8_threshold: null pointer");
     CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv8_threshold: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
     CLV_REQUIRE(n < (1ull << 32), "clv8_threshold: vectors of 2^32 or more elements are not supported");
+    CLV_REQUIRE_WORKSPACE("clv8_threshold", workspace);
     hipStream_t st = as_stream(stream);
     if (k >= n || n == 0) return CLV_OK;
     if (n_pad <= (uint64_t)TS_THREADS * TS8_MAXW * 4) {
@@ -1775,6 +1779,7 @@ extern "C" int clv8_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64
     CLV_REQUIRE(q && s, "clv8_threshold_mode: null pointer");
     CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv8_threshold_mode: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
     CLV_REQUIRE(n < (1ull << 32), "clv8_threshold_mode: vectors of 2^32 or more elements are not supported");
+    CLV_REQUIRE_WORKSPACE("clv8_threshold_mode", workspace);
     if (k >= n || n == 0) return CLV_OK;
     return threshold_reference<8>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream));
 }
@@ -1793,6 +1798,7 @@ extern "C" int clv_f16_threshold_mode(uint16_t *h, uint64_t n, uint64_t n_pad, u
     CLV_REQUIRE(h, "clv_f16_threshold_mode: null pointer");
     CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv_f16_threshold_mode: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
     CLV_REQUIRE(n < (1ull << 32), "clv_f16_threshold_mode: vectors of 2^32 or more elements are not supported");
+    CLV_REQUIRE_WORKSPACE("clv_f16_threshold_mode", workspace);
     if (k >= n || n == 0) return CLV_OK;
     if (mode == CLV_THRESHOLD_REFERENCE) return threshold_reference<16>((uint32_t *)h, nullptr, n, n_pad, k, workspace, as_stream(stream));
     if (!workspace) {
@@ -1808,5 +1814,6 @@ extern "C" int clv_f16_threshold_heap(uint16_t *h, uint64_t n, uint64_t n_pad, u
     CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv_f16_threshold_heap: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
     CLV_REQUIRE(n < (1ull << 32), "clv_f16_threshold_heap: vectors of 2^32 or more elements are not supported");
     CLV_REQUIRE(k >= 1 && k <= n, "clv_f16_threshold_heap: k=%llu must lie in 1 .. n=%llu", (unsigned long long)k, (unsigned long long)n);
+    CLV_REQUIRE_WORKSPACE("clv_f16_threshold_heap", workspace);
     return threshold_reference<16>((uint32_t *)h, nullptr, n, n_pad, k, workspace, as_stream(stream), (uint2 *)heap_dev);
 }

@@ -14,6 +14,10 @@
  *    CloverVector.h:86-92), matrix rows/cols (multiples of 128, CloverMatrix.h:48-53).  The mvm family (clm4_mvm,
  *    clm4_rowdots, clm4_mvm_scale_and_add, clm4_mvm_v8*, clm4_rowdots_v8, clm4_mvm_f32) also accepts rows % 64 == 0:
  *    a row shard of a matrix, the unit mvm_parallel gives a thread (CloverMatrix4.h:1700-1705).
+ *  - `workspace` arguments: NULL (the library's own scratch of the stream) or device memory of at least the bytes the function's
+ *    *_workspace_bytes query returns, 16-BYTE ALIGNED (the kernels access it as float4 / uint64), uninitialised; a misaligned non-NULL
+ *    workspace is rejected with CLV_ERR_INVALID before anything touches the device.  A call writes nothing outside its outputs and
+ *    that many workspace bytes (tests/test_guard_bands.py, tests/test_caller_workspace.py).
  *  - data format = the reference's: byte i holds element 2i in its HIGH nibble and 2i+1 in its LOW nibble,
  *    two's complement, values in [-7,7] (CloverVector4.h:511-514); one fp32 scale (the block's absolute
  *    maximum, 0 -> 1.0) per 64 elements (CloverVector4.h:661-673) / per 64x64 tile, row-major tile grid
@@ -133,7 +137,7 @@ int  clv4_restore(const int8_t *q, const float *s, uint64_t n_pad, float *x, voi
 /* CloverVector4::dot (CloverVector4.h:1095-1192).  *out_dev receives one float.  CLV_DOT_EXACT is
  * bit-identical to the reference; CLV_DOT_FAST differs only in fp32 summation order (the per-block
  * integer sums are exact either way; one launch, deterministic: a fixed tree whatever order the workgroups finish in).
- * workspace: clv4_dot_workspace_bytes() bytes or NULL (internal); only CLV_DOT_EXACT uses it. */
+ * workspace: clv4_dot_workspace_bytes() bytes, 16-byte aligned, or NULL (internal); only CLV_DOT_EXACT uses it. */
 uint64_t clv4_dot_workspace_bytes(uint64_t n_pad);
 int  clv4_dot(const int8_t *qu, const float *su, const int8_t *qv, const float *sv, uint64_t n_pad,
               int mode, float *out_dev, void *workspace, void *stream);
@@ -216,11 +220,11 @@ int  clv8_scale_and_add(const int8_t *qu, const float *su, const int8_t *qv, con
 /* clv8_dot = CloverVector8::dot (CloverVector8.h:911-977): per block the 64 byte products summed exactly per 32-bit lane of the block's two
  * halves, scale = f32(f32(su * 1/127) * f32(sv * 1/127)), 8 fma chains over ALL blocks, then the _mm256_haddf32_ps tree.  CLV_DOT_EXACT: that
  * order, bit for bit (n/64 dependent fmas per chain: latency-bound by definition); CLV_DOT_FAST (= dot_parallel, :979-1061): the same exact
- * block integers, fp32 tree order, one launch, memory-bound.  workspace: clv8_dot_workspace_bytes() bytes or NULL (internal; EXACT only). */
+ * block integers, fp32 tree order, one launch, memory-bound.  workspace: clv8_dot_workspace_bytes() bytes, 16-byte aligned, or NULL (internal; EXACT only). */
 uint64_t clv8_dot_workspace_bytes(uint64_t n_pad);
 int  clv8_dot(const int8_t *qu, const float *su, const int8_t *qv, const float *sv, uint64_t n_pad, int mode, float *out_dev,
               void *workspace, void *stream);
-uint64_t clv8_threshold_workspace_bytes(uint64_t n_pad);
+uint64_t clv8_threshold_workspace_bytes(uint64_t n_pad);      /* FAST mode; 16-byte aligned, no initialisation (as clv4_threshold) */
 int  clv8_threshold(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *workspace, void *stream);
 int  clv8_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream);
 /* CloverMatrix4::mvm(const CloverVector8 &, CloverVector8 &) (CloverMatrix4.h:1093-1441; _parallel :2017-2387):
@@ -252,7 +256,8 @@ int  clm4_rowdots_v8(const int8_t *A, const float *sA, uint64_t rows, uint64_t c
  * that hands its radix levels over through a zero-initialised control block of the (device, stream), allocated -- like the hand-over
  * slots of the single-launch dots -- by the first such call there: a FIRST call made inside a stream capture runs the older six-launch
  * form instead (same result); after one ordinary call the three launches capture and replay (tests/test_threshold_large3.py).
- * `workspace` (or NULL: library scratch of the stream) needs clv4_threshold_workspace_bytes(n_pad) bytes and no initialisation. */
+ * `workspace` (or NULL: library scratch of the stream) needs clv4_threshold_workspace_bytes(n_pad) bytes, 16-byte alignment and no
+ * initialisation. */
 uint64_t clv4_threshold_workspace_bytes(uint64_t n_pad);
 int  clv4_threshold(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *workspace, void *stream);
 /* The same with the tie rule chosen by `mode` (the threshold counterpart of clv4_dot's CLV_DOT_EXACT / CLV_DOT_FAST):
@@ -267,6 +272,7 @@ int  clv4_threshold(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint6
  * clm4_iht / clm4_iht_v8 take threshold = 2 for this mode (1 = FAST, 0 = no threshold: Q_GD). */
 #define CLV_THRESHOLD_FAST 0
 #define CLV_THRESHOLD_REFERENCE 1
+/* (both: 16-byte aligned, no initialisation; shared by the REFERENCE mode and the heap forms of all three widths) */
 uint64_t clv_threshold_reference_workspace_bytes(uint64_t n_pad);                    /* enough for any k */
 uint64_t clv_threshold_reference_workspace_bytes_k(uint64_t n_pad, uint64_t k);      /* for this k: the 8 (k + 1)-byte heap region only when k > 20000 */
 int  clv4_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream);
@@ -318,14 +324,15 @@ int  clv_f16_scale_and_add(const uint16_t *u, const uint16_t *v, float a, uint64
 /* CloverVector16::dot (CloverVector16.h:473-530): 32 fp32 fma chains, element j in chain j mod 32 (accumulator (j mod 32) / 8, lane j mod 8),
  * (acc0 + acc1) + (acc2 + acc3), then _mm256_haddf32_ps (CloverBase.h:149-157).  CLV_DOT_EXACT: that order, bit for bit (n / 32 dependent
  * fmas per chain: latency-bound by definition); CLV_DOT_FAST (= dot_parallel, :532-610): the same exact products in a tree order, one
- * launch, memory-bound (first call on a stream outside a capture, as for clv4_dot).  Neither mode uses `workspace`; the query returns 0. */
+ * launch, memory-bound (first call on a stream outside a capture, as for clv4_dot).  Neither mode uses `workspace`; the query returns 0
+ * (a non-NULL workspace must still be 16-byte aligned, the one rule of every workspace argument). */
 uint64_t clv_f16_dot_workspace_bytes(uint64_t n_pad);
 int  clv_f16_dot(const uint16_t *u, const uint16_t *v, uint64_t n_pad, int mode, float *out_dev, void *workspace, void *stream);
 /* CloverVector16::threshold (CloverVector16.h:612-626) and ::threshold_min_heap (:628-673) on |f32(h)|: CLV_THRESHOLD_FAST keeps the same
  * multiset of magnitudes with lowest-index ties, CLV_THRESHOLD_REFERENCE the reference's survivors index for index (its heap walk);
  * survivors keep their bits, the other elements below n become 0x0000.  Workspace (NULL = the stream's scratch):
  * clv_f16_threshold_workspace_bytes(n_pad) for FAST, clv_threshold_reference_workspace_bytes_k(n_pad, k) for REFERENCE and the heap form
- * (heap_dev: k entries {fp32 |value|, uint32 index}, 1 <= k <= n). */
+ * (heap_dev: k entries {fp32 |value|, uint32 index}, 1 <= k <= n).  16-byte aligned, no initialisation. */
 uint64_t clv_f16_threshold_workspace_bytes(uint64_t n_pad);
 int  clv_f16_threshold_mode(uint16_t *h, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream);
 int  clv_f16_threshold_heap(uint16_t *h, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream);
