@@ -75,6 +75,8 @@ void clv_internal_persist_forget(hipStream_t stream);     // iht_persist.hip: th
 uint64_t clv_internal_dot_chain_blocks_padded(uint64_t steps);
 uint64_t clv_internal_dot_chain_bytes(uint64_t steps);
 int clv_internal_dot_chain(const void *X, uint64_t blocks_padded, float *out_dev, hipStream_t st);
+// CloverVector8::clear() as one launch (mixed8.hip): bytes 0, scales 1.0; first step of clm4_iht_v8 and clm8_iht
+int clv_internal_v8_clear(int8_t *x, float *sx, uint64_t n_pad, hipStream_t st);
 // zero-initialised hand-over slots per (device, stream), <= 64 KiB; every user leaves them zero again (runtime.hip)
 int clv_internal_sync_slots(void **ptr, uint64_t bytes, hipStream_t stream);
 

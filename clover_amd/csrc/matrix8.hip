@@ -149,17 +149,51 @@ __device__ __forceinline__ void m8_mvm_steps(const u32x2 *__restrict__ Ar, const
     }
 }
 
-template <bool NT, bool ST>
-__global__ __launch_bounds__(256) void k_m8_mvm(const uint8_t *__restrict__ A, const float *__restrict__ sA, uint64_t cols,
-                                                const uint8_t *__restrict__ x, const float *__restrict__ sx, int8_t *__restrict__ r,
-                                                float *__restrict__ sr, uint64_t *rng_state, uint64_t seq, const uint64_t *__restrict__ pow_rows)
+// FUSE (clm8_mvm_scale_and_add): the CloverVector8::scaleAndAdd that follows this mvm in the IHT / GD loops (CloverVector8.h:1089-1358),
+// done on the row group while the first wave still holds it: r2 = quantize8(u + a * quantize8(A x)).  Its two draws per block follow ALL
+// the mvm draws in the stream (row group rb: draws 2 G + 2 rb, + 1 with G = rows / 64), as two separate calls leave them; element l takes
+// draw l >> 5, word (l & 31) >> 2, byte l & 3 (k_v8_scale_and_add_st).  r (the quantised A x) may be NULL under FUSE: it is then not stored.
+struct M8Fuse {
+    const int8_t *qu;        // u, one 64-element block per row group
+    const float *su;
+    float a;
+    int8_t *r2;              // may alias qu (the in-place form): the block of u is read before the streaming loop
+    float *sr2;
+};
+
+template <bool NT, bool ST, bool FUSE>
+__device__ __forceinline__ void m8_mvm_body(const uint8_t *__restrict__ A, const float *__restrict__ sA, uint64_t cols, const uint8_t *__restrict__ x,
+                                            const float *__restrict__ sx, int8_t *r, float *sr, uint64_t *rng_state, uint64_t seq,
+                                            const uint64_t *__restrict__ pow_rows, const M8Fuse &fuse)
 {
     __shared__ float dsh[64];
     __shared__ __attribute__((aligned(16))) uint64_t raw[8];          // ST: the row group's two draws
     __shared__ uint64_t rbase[4];
-    if (ST) rng_workgroup_begin(rng_state, seq, pow_rows, blockIdx.x, 1, 2ull * gridDim.x, rbase);
+    __shared__ __attribute__((aligned(16))) uint64_t raw2[8];         // ST && FUSE: the two draws of the scaleAndAdd
+    __shared__ uint64_t rbase2[4];
+    if (ST && !FUSE) rng_workgroup_begin(rng_state, seq, pow_rows, blockIdx.x, 1, 2ull * gridDim.x, rbase);
+    if (ST && FUSE) {
+        // rng_workgroup_begin with a second base, both written before its barrier
+        const int k = threadIdx.x >> 6;
+        seq = rng_effective_seq(rng_state, seq);
+        const int slot = rng_read_slot(rng_state, seq);
+        const uint64_t g0 = rng_state[slot * RNG_SLOT_WORDS + 4 + k];
+        const uint64_t b1 = wave_pow_apply(pow_rows, g0, blockIdx.x, 1);
+        const uint64_t b2 = wave_pow_apply(pow_rows, g0, (uint64_t)gridDim.x + blockIdx.x, 1);
+        if ((threadIdx.x & 63) == 0) {
+            rbase[k] = b1;
+            rbase2[k] = b2;
+        }
+        rng_commit(rng_state, seq, slot, pow_rows, g0, 4ull * gridDim.x);
+    }
     const uint64_t rb = blockIdx.x;
     const int tid = threadIdx.x, p = tid & 3, rho = tid >> 2;
+    int fuse_q = 0;
+    float fuse_s = 0.0f;
+    if (FUSE && tid < 64) {                                           // this row group's block of u, ahead of the streaming loop
+        fuse_q = fuse.qu[rb * 64 + tid];
+        fuse_s = fuse.su[rb];
+    }
     const uint64_t row = rb * 64 + rho;
     const uint32_t nblk = (uint32_t)(cols / 64);
     const u32x2 *Ar = reinterpret_cast<const u32x2 *>(A + row * cols);
@@ -174,7 +208,10 @@ __global__ __launch_bounds__(256) void k_m8_mvm(const uint8_t *__restrict__ A, c
     const float t0 = a0 + __shfl_xor(a0, 2), t1 = a1 + __shfl_xor(a1, 2);
     const float x0 = t0 + __shfl_xor(t0, 1), x1 = t1 + __shfl_xor(t1, 1);
     if (p == 0) dsh[rho] = x0 + x1;
-    if (ST && tid < 4) gen_blocks(rbase[tid], 1, raw, tid);
+    if (ST && tid < 4) {
+        gen_blocks(rbase[tid], 1, raw, tid);
+        if (FUSE) gen_blocks(rbase2[tid], 1, raw2, tid);
+    }
     __syncthreads();
     if (tid < 64) {
         const float d = dsh[tid];
@@ -182,9 +219,38 @@ __global__ __launch_bounds__(256) void k_m8_mvm(const uint8_t *__restrict__ A, c
         if (ST) noise = noise_of(reinterpret_cast<const uint32_t *>(raw + (size_t)(tid >> 5) * 4)[tid & 7], (tid >> 3) & 3);
         const float m = fix_zero_max(wave_max(__builtin_fabsf(d)));
         const float k = 127.0f / m;
-        r[rb * 64 + tid] = (int8_t)quant1(d, k, noise);
-        if (tid == 0) sr[rb] = m;
+        const int qv = quant1(d, k, noise);
+        if (!FUSE || r) {
+            r[rb * 64 + tid] = (int8_t)qv;
+            if (tid == 0) sr[rb] = m;
+        }
+        if (FUSE) {
+            const float val = __builtin_fmaf((float)qv, div127(m * fuse.a), (float)fuse_q * div127(fuse_s));
+            float noise2 = 0.0f;
+            if (ST) noise2 = noise_of(reinterpret_cast<const uint32_t *>(raw2 + (size_t)(tid >> 5) * 4)[(tid & 31) >> 2], tid & 3);
+            const float m2 = fix_zero_max(wave_max(__builtin_fabsf(val)));
+            fuse.r2[rb * 64 + tid] = (int8_t)quant1(val, 127.0f / m2, noise2);
+            if (tid == 0) fuse.sr2[rb] = m2;
+        }
     }
+}
+
+template <bool NT, bool ST>
+__global__ __launch_bounds__(256) void k_m8_mvm(const uint8_t *__restrict__ A, const float *__restrict__ sA, uint64_t cols,
+                                                const uint8_t *__restrict__ x, const float *__restrict__ sx, int8_t *__restrict__ r,
+                                                float *__restrict__ sr, uint64_t *rng_state, uint64_t seq, const uint64_t *__restrict__ pow_rows)
+{
+    const M8Fuse none = {nullptr, nullptr, 0.0f, nullptr, nullptr};
+    m8_mvm_body<NT, ST, false>(A, sA, cols, x, sx, r, sr, rng_state, seq, pow_rows, none);
+}
+
+// r / sr: the quantised A x (t of the ABI), NULL = not stored.  No __restrict__ on the vectors: fuse.r2 may be fuse.qu.
+template <bool NT, bool ST>
+__global__ __launch_bounds__(256) void k_m8_mvm_saa(const uint8_t *__restrict__ A, const float *__restrict__ sA, uint64_t cols,
+                                                    const uint8_t *__restrict__ x, const float *__restrict__ sx, int8_t *r, float *sr,
+                                                    uint64_t *rng_state, uint64_t seq, const uint64_t *__restrict__ pow_rows, M8Fuse fuse)
+{
+    m8_mvm_body<NT, ST, true>(A, sA, cols, x, sx, r, sr, rng_state, seq, pow_rows, fuse);
 }
 
 // ================================================================================================
@@ -393,6 +459,64 @@ extern "C" int clm8_mvm(const int8_t *A, const float *sA, uint64_t rows, uint64_
     }
     CLV_LAUNCH_CHECK();
     return CLV_OK;
+}
+
+#define M8_SAA "clm8_mvm_scale_and_add"
+extern "C" int clm8_mvm_scale_and_add(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
+                                      const int8_t *qu, const float *su, float a, int8_t *t, float *st_, int8_t *r, float *sr,
+                                      uint64_t *rng_state_dev, void *stream)
+{
+    int rc = m8_check_mvm(M8_SAA, A, sA, rows, cols, x, r);
+    if (rc) return rc;
+    CLV_REQUIRE(sx && qu && su && sr, M8_SAA ": null pointer");
+    CLV_REQUIRE((t == nullptr) == (st_ == nullptr), M8_SAA ": t and st must both be given or both be NULL");
+    CLV_REQUIRE((const void *)r != (const void *)x && (const void *)sr != (const void *)sx && (!t || ((const void *)t != (const void *)x && st_ != sx)),
+                M8_SAA ": the results must not alias the vector being multiplied");
+    CLV_REQUIRE(!t || (r != t && sr != st_), M8_SAA ": r must not alias t");
+    if (!rows) return CLV_OK;
+    hipStream_t st = as_stream(stream);
+    const dim3 grid((unsigned)(rows / 64)), block(256);
+    const bool streaming = rows * cols > (256ull << 20);      // the clm8_mvm rule
+    const M8Fuse fuse = {qu, su, a, r, sr};
+    RngTables T = {nullptr, nullptr, nullptr};
+    uint64_t seq = 0;
+    if (rng_state_dev) {
+        rc = clv_rng_tables(&T);
+        if (rc) return rc;
+        seq = clv_rng_seq_for(rng_state_dev, st);
+    }
+#define M8_SAA_LAUNCH(NT, ST)                                                                                                             \
+    hipLaunchKernelGGL((k_m8_mvm_saa<NT, ST>), grid, block, 0, st, (const uint8_t *)A, sA, cols, (const uint8_t *)x, sx, t, st_, rng_state_dev, \
+                       seq, T.pow_rows, fuse)
+    if (streaming) {
+        if (rng_state_dev) M8_SAA_LAUNCH(true, true); else M8_SAA_LAUNCH(true, false);
+    } else {
+        if (rng_state_dev) M8_SAA_LAUNCH(false, true); else M8_SAA_LAUNCH(false, false);
+    }
+#undef M8_SAA_LAUNCH
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+#undef M8_SAA
+
+// Q_IHT / Q_GD (test/performance/01_measure.h:923-946, 999-1021) over a CloverMatrix8 with CloverVector8 vectors, the reference's pure
+// 8-bit configuration (02_bit08.cpp).  One call enqueues all iterations: 3 launches per iteration (2 for GD), nothing copied back.
+extern "C" int clm8_iht(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, int8_t *x,
+                        float *sx, uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2,
+                        int8_t *t3, float *st3, uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev,
+                        void *stream)
+{
+    CLV_REQUIRE(Phi && sPhi && PhiT && sPhiT && x && sx && y && sy && t1 && st1 && t2 && st2 && t3 && st3, "clm8_iht: null pointer");
+    CLV_REQUIRE(m % 128 == 0 && n % 128 == 0 && x_len <= n, "clm8_iht: m=%llu n=%llu x_len=%llu", (unsigned long long)m,
+                (unsigned long long)n, (unsigned long long)x_len);
+    int rc = clv_internal_v8_clear(x, sx, n, as_stream(stream));      // x.clear()
+    for (uint64_t it = 0; !rc && it < iterations; it++) {
+        rc = clm8_mvm_scale_and_add(Phi, sPhi, m, n, x, sx, y, sy, -1.0f, t1, st1, t2, st2, rng_state_dev, stream);              // t1 = Phi x; t2 = y - t1
+        if (!rc) rc = clm8_mvm_scale_and_add(PhiT, sPhiT, n, m, t2, st2, x, sx, mu, t3, st3, x, sx, rng_state_dev, stream);      // t3 = Phi' t2; x += mu t3
+        if (!rc && threshold)                                                                    // keep the K largest (2: the reference's survivor order)
+            rc = clv8_threshold_mode(x, sx, x_len, n, K, threshold == 2 ? CLV_THRESHOLD_REFERENCE : CLV_THRESHOLD_FAST, nullptr, stream);
+    }
+    return rc;
 }
 
 extern "C" int clm8_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *r, void *stream)

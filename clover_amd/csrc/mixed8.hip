@@ -877,6 +877,14 @@ int clm4_iht_v8_persistent(const int8_t *Phi, const float *sPhi, const int8_t *P
                            uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3, float *st3,
                            uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng, hipStream_t st);
 
+// CloverVector8::clear() on the stream (also the first step of clm8_iht, matrix8.hip)
+int clv_internal_v8_clear(int8_t *x, float *sx, uint64_t n_pad, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_v8_clear, dim3(64), dim3(256), 0, st, (uint32_t *)x, sx, n_pad / 4, n_pad / 64);
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+
 extern "C" int clm4_iht_v8(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, int8_t *x,
                            float *sx, uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2,
                            int8_t *t3, float *st3, uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev,
@@ -892,8 +900,8 @@ extern "C" int clm4_iht_v8(const int8_t *Phi, const float *sPhi, const int8_t *P
         if (p < 0) return CLV_ERR_HIP;
         if (p > 0) return CLV_OK;
     }
-    hipLaunchKernelGGL(k_v8_clear, dim3(64), dim3(256), 0, st, (uint32_t *)x, sx, n / 4, n / 64);      // x.clear()
-    CLV_LAUNCH_CHECK();
+    int rc0 = clv_internal_v8_clear(x, sx, n, st);      // x.clear()
+    if (rc0) return rc0;
     for (uint64_t it = 0; it < iterations; it++) {
         int rc = clm4_mvm_v8_scale_and_add(Phi, sPhi, m, n, x, sx, y, sy, -1.0f, t1, st1, t2, st2, rng_state_dev, stream);      // t1 = Phi x; t2 = y - t1
         if (!rc) rc = clm4_mvm_v8_scale_and_add(PhiT, sPhiT, n, m, t2, st2, x, sx, mu, t3, st3, x, sx, rng_state_dev, stream);  // t3 = Phi' t2; x += mu t3

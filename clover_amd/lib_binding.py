@@ -92,6 +92,9 @@ SIGNATURES = {
     "clm8_quantize": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "clm8_restore": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "clm8_mvm": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm8_mvm_scale_and_add": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm8_iht": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float,
+                           C.c_int, _vp, _vp]),
     "clm8_mvm_f32": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "clm8_transpose": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "clv_f16_quantize": (C.c_int, [_vp, _u64, _vp, _vp]),
@@ -399,6 +402,33 @@ class CloverHip:
         dr, dsr = self.alloc(max(rows, 1)), self.alloc(max(rows // 16, 4))
         self.check(self.lib.clm8_mvm(b[0].ptr, b[1].ptr, rows, cols, b[2].ptr, b[3].ptr, dr.ptr, dsr.ptr, rng.ptr if rng else None, None))
         return dr.download(np.int8, rows), dsr.download(np.float32, rows // 64)
+
+    def m8_mvm_scale_and_add(self, qA, sA, rows, cols, qx, sx, qu, su, a: float, rng: DevBuf | None = None, in_place: bool = False,
+                             want_t: bool = True):
+        """(t, st, r, sr) of clm8_mvm_scale_and_add; t/st are None when want_t is False"""
+        b = [self.to_device(v) for v in (qA, sA, qx, sx, qu, su)]
+        dt, dst = (self.alloc(rows), self.alloc(rows // 16)) if want_t else (None, None)
+        dr, dsr = (b[4], b[5]) if in_place else (self.alloc(rows), self.alloc(rows // 16))
+        self.check(self.lib.clm8_mvm_scale_and_add(b[0].ptr, b[1].ptr, rows, cols, b[2].ptr, b[3].ptr, b[4].ptr, b[5].ptr, a,
+                                                   dt.ptr if dt else None, dst.ptr if dst else None, dr.ptr, dsr.ptr,
+                                                   rng.ptr if rng else None, None))
+        t = (dt.download(np.int8, rows), dst.download(np.float32, rows // 64)) if want_t else (None, None)
+        return t[0], t[1], dr.download(np.int8, rows), dsr.download(np.float32, rows // 64)
+
+    def m8_iht(self, qPhi, sPhi, qPhiT, sPhiT, m, n, qy, sy, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+               rng: DevBuf | None = None, prefill: int = 0x55):
+        """clm8_iht on buffers prefilled with `prefill` bytes: {"x": (q, s), "t1": ..., "t2": ..., "t3": ...}"""
+        b = [self.to_device(v) for v in (qPhi, sPhi, qPhiT, sPhiT, qy, sy)]
+        lens = {"x": n, "t1": m, "t2": m, "t3": n}
+        v = {}
+        for name, ln in lens.items():
+            v[name] = (self.alloc(ln), self.alloc(ln // 16))
+            for d in v[name]:
+                self.check(self.lib.clv_memset(d.ptr, prefill, d.nbytes, None))
+        self.check(self.lib.clm8_iht(b[0].ptr, b[1].ptr, b[2].ptr, b[3].ptr, m, n, v["x"][0].ptr, v["x"][1].ptr, n if x_len is None else x_len,
+                                     b[4].ptr, b[5].ptr, v["t1"][0].ptr, v["t1"][1].ptr, v["t2"][0].ptr, v["t2"][1].ptr, v["t3"][0].ptr,
+                                     v["t3"][1].ptr, iterations, K, mu, threshold, rng.ptr if rng else None, None))
+        return {name: (v[name][0].download(np.int8, ln), v[name][1].download(np.float32, ln // 64)) for name, ln in lens.items()}
 
     def m8_mvm_f32(self, qA, sA, rows, cols, x) -> np.ndarray:
         b = [self.to_device(a) for a in (qA, sA, np.ascontiguousarray(x, dtype=np.float32))]

@@ -12,7 +12,7 @@
 #define CLOVER_IHT_H
 
 #include "CloverMatrix4.h"
-#include "CloverMatrix8.h"       /* Q_IHT<CloverMatrix8, CloverVector8> / Q_GD<...>: the generic templates below */
+#include "CloverMatrix8.h"       /* Q_IHT<CloverMatrix8, CloverVector8> / Q_GD<...>: the specialisations at the end */
 #include "CloverMatrix16.h"      /* Q_IHT<CloverMatrix16, CloverVector16> / Q_GD<...>: the same templates */
 #include "CloverVector4.h"
 
@@ -99,6 +99,43 @@ inline void Q_IHT(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector8 &x, Clo
 
 inline void Q_GD(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector8 &x, CloverVector8 &y, CloverVector8 &t1, CloverVector8 &t2,
                  CloverVector8 &t3, const uint64_t iterations, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, 0, mu, false);
+    return;
+#endif
+    x.clear();
+    for (uint64_t i = 0; i < iterations; i += 1) {
+        Phi.mvm_scaleAndAdd(x, y, -1.0f, t1, t2);
+        PhiT.mvm_scaleAndAdd(t2, x, mu, t3);
+    }
+}
+
+
+/* CloverMatrix8 with CloverVector8 vectors: the reference's pure 8-bit configuration (test/performance/02_bit08.cpp).  Explicit
+ * specialisations of the generic templates, not overloads: callers that spell the template arguments out --
+ * Q_IHT<CloverMatrix8, CloverVector8>(Phi, ...) -- reach them as well as those that let them be deduced.  The whole loop in one call
+ * (CloverMatrix8::iht_loop -> clm8_iht, three launches per iteration) when rounding is deterministic, else every scaleAndAdd paired with
+ * the mvm before it; identical results either way. */
+template <>
+inline void Q_IHT<CloverMatrix8, CloverVector8>(CloverMatrix8 &Phi, CloverMatrix8 &PhiT, CloverVector8 &x, CloverVector8 &y, CloverVector8 &t1,
+                                                CloverVector8 &t2, CloverVector8 &t3, const uint64_t iterations, const uint64_t K, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, K, mu, true);
+    return;
+#endif
+    x.clear();
+    for (uint64_t i = 0; i < iterations; i += 1) {
+        Phi.mvm_scaleAndAdd(x, y, -1.0f, t1, t2);
+        PhiT.mvm_scaleAndAdd(t2, x, mu, t3);
+        x.threshold_parallel(K);
+    }
+}
+
+template <>
+inline void Q_GD<CloverMatrix8, CloverVector8>(CloverMatrix8 &Phi, CloverMatrix8 &PhiT, CloverVector8 &x, CloverVector8 &y, CloverVector8 &t1,
+                                               CloverVector8 &t2, CloverVector8 &t3, const uint64_t iterations, const float mu)
 {
 #ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
     Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, 0, mu, false);

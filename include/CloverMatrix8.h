@@ -15,8 +15,11 @@
  *                                         quantiser; for fp32 vectors a double accumulation), transpose_scalar (:1312-1340).  With
  *                                         rounding disabled mvm == mvm_parallel == mvm_scalar bit for bit, as in the reference.
  *
- * Q_IHT<CloverMatrix8, CloverVector8> and Q_GD<...> are the generic templates of CloverIHT.h (which includes this header): every step is
- * a kernel on the device mirrors, nothing is copied back between steps.
+ *   mvm_scaleAndAdd                    -> clm8_mvm_scale_and_add  (not in the reference: mvm + the scaleAndAdd behind it, one launch)
+ *   iht_loop                           -> clm8_iht        (the whole Q_IHT / Q_GD loop of 01_measure.h:923-946, 999-1021 in one call)
+ *
+ * Q_IHT<CloverMatrix8, CloverVector8> and Q_GD<...> are specialised in CloverIHT.h (which includes this header): iht_loop when rounding is
+ * deterministic, the mvm_scaleAndAdd pairs otherwise; every step is a kernel on the device mirrors, nothing is copied back between steps.
  */
 #ifndef CLOVER_MATRIX8_H
 #define CLOVER_MATRIX8_H
@@ -176,6 +179,63 @@ public:
         resultVector.commit();
     }
     void mvm_parallel(const CloverVector8 &productVector, CloverVector8 &resultVector) { mvm(productVector, resultVector); }
+    /* Not in the reference: t = this * x immediately followed by r = quantize(u + a * t), the pair of steps the IHT / GD loops repeat
+     * (01_measure.h:940-941, :942-943), as CloverMatrix4::mvm_scaleAndAdd.  One launch when rounding is deterministic; with stochastic
+     * rounding the two steps draw from two objects' generators (the matrix's, then u's), as they do in the reference, and are issued as
+     * the two calls.  Results are identical to mvm(x, t); u.scaleAndAdd(t, a, r) either way. */
+    void mvm_scaleAndAdd(const CloverVector8 &x, const CloverVector8 &u, float a, CloverVector8 &t, CloverVector8 &r)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        if (x.size() != getCols() || t.size_pad() != getRows()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
+        if (u.size_pad() != getRows() || r.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        clover_hip::check(clm8_mvm_scale_and_add(dev_values(), dev_scales(), rows, cols, x.dev_values_ro(), x.dev_scales_ro(),
+                                                 u.dev_values_ro(), u.dev_scales_ro(), a, t.dev_values_wo(), t.dev_scales_wo(),
+                                                 r.dev_values_wo(), r.dev_scales_wo(), nullptr, nullptr), "CloverMatrix8::mvm_scaleAndAdd");
+        t.commit();
+        r.commit();
+#else
+        mvm(x, t);
+        const_cast<CloverVector8 &>(u).scaleAndAdd(t, a, r);
+#endif
+    }
+    /* in place: u = quantize(u + a * (this * x)) */
+    void mvm_scaleAndAdd(const CloverVector8 &x, CloverVector8 &u, float a, CloverVector8 &t)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        if (x.size() != getCols() || t.size_pad() != getRows()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
+        if (u.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        int8_t *qu = u.dev_values_rw();
+        float *su = u.dev_scales_rw();
+        clover_hip::check(clm8_mvm_scale_and_add(dev_values(), dev_scales(), rows, cols, x.dev_values_ro(), x.dev_scales_ro(), qu, su, a,
+                                                 t.dev_values_wo(), t.dev_scales_wo(), qu, su, nullptr, nullptr),
+                          "CloverMatrix8::mvm_scaleAndAdd");
+        t.commit();
+        u.commit();
+#else
+        mvm(x, t);
+        u.scaleAndAdd(t, a);
+#endif
+    }
+    /* The WHOLE quantized IHT / GD loop of 01_measure.h:923-946, 999-1021 with this matrix as Phi, in one call (clm8_iht): x.clear(), then
+     * `iterations` times t1 = Phi x; t2 = y - t1; t3 = PhiT t2; x += mu t3; [threshold(K)] -- three launches per iteration, same bits as
+     * the five method calls.  Deterministic rounding only (each step of a stochastic loop draws from its own object's generator:
+     * CloverIHT.h keeps the calls apart there). */
+    void iht_loop(CloverMatrix8 &PhiT, CloverVector8 &x, const CloverVector8 &y, CloverVector8 &t1, CloverVector8 &t2, CloverVector8 &t3,
+                  uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    {
+        if (PhiT.getRows() != getCols() || PhiT.getCols() != getRows() || x.size_pad() != getCols() || y.size_pad() != getRows() ||
+            t1.size_pad() != getRows() || t2.size_pad() != getRows() || t3.size_pad() != getCols()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm8_iht(dev_values(), dev_scales(), PhiT.dev_values(), PhiT.dev_scales(), rows, cols, x.dev_values_wo(), x.dev_scales_wo(),
+                                   x.size(), y.dev_values_ro(), y.dev_scales_ro(), t1.dev_values_wo(), t1.dev_scales_wo(), t2.dev_values_wo(),
+                                   t2.dev_scales_wo(), t3.dev_values_wo(), t3.dev_scales_wo(), iterations, K, mu, thr, nullptr, nullptr),
+                          "CloverMatrix8::iht_loop");
+        x.commit();
+        if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
+    }
     /* :480-548: every row wrapped in a non-owning CloverVector8 view over the matrix's own memory and multiplied with dot() (the
      * reference's order), then 64 results at a time quantised by scalar code -- an implementation independent of the mvm kernel */
     void mvm_scalar(const CloverVector8 &productVector, CloverVector8 &resultVector)

@@ -31,7 +31,7 @@
  *    consumed (bit-identical nibbles for identical keys).  Exceptions are spelled out per function.
  *  - STOCHASTIC CALLS (any function given a non-NULL rng_state_dev: clv4_quantize, clm4_quantize, clm4_mvm, clv4_scale_and_add,
  *    clm4_mvm_scale_and_add, clv8_quantize, clv8_scale_and_add, clm4_mvm_v8, clm4_mvm_v8_scale_and_add, clm4_iht, clm4_iht_v8,
- *    clm8_quantize, clm8_mvm):
+ *    clm8_quantize, clm8_mvm, clm8_mvm_scale_and_add, clm8_iht):
  *      (1) calls that share a state buffer must be STREAM-ORDERED -- the same stream, or an event / sync between them: they consume one
  *          sequential XORShift stream, as the reference's methods do on one object, and each launch reads the state its predecessor left;
  *      (2) such a call must NOT be captured into a hipGraph unless its state is in graph mode (clv_rng_graph_mode): ordinarily every launch
@@ -304,6 +304,26 @@ int  clm8_restore(const int8_t *q, const float *s, uint64_t rows, uint64_t cols,
  * with factor f32(f32(su * 1/127) * f32(sv * 1/127)), then the extractf128 / movehl / shuffle tree.  Bit-identical when
  * rng_state_dev == NULL; with an rng the re-quantisation draws two values per 64-row group: stream-ordered, no graph capture. */
 int  clm8_mvm(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx, int8_t *r, float *sr,
+              uint64_t *rng_state_dev, void *stream);
+/* clm8_mvm immediately followed by clv8_scale_and_add on its result (CloverMatrix8.h:1002-1299, then CloverVector8.h:1089-1358), one
+ * launch -- the pair of steps the IHT / GD loops repeat (test/performance/01_measure.h:940-943, 1016-1019):
+ *   t = quantize8(A x), stored only if t and st are given (both NULL or both non-NULL);  r = quantize8(u + a * t), u and r of `rows` elements.
+ * Bit-identical to the two calls for either rounding mode.  With an rng the launch consumes 4 (rows/64) draws: the mvm's 2 (rows/64) first,
+ * then two per block for the scaleAndAdd (row group rb: draws 2 (rows/64) + 2 rb, + 1) -- the state two separate calls leave behind;
+ * stream-ordered, no graph capture.  r/sr may alias qu/su (the in-place form); r and t must not alias x, and r must not alias t.
+ * Shapes as clm8_mvm. */
+int  clm8_mvm_scale_and_add(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
+                            const int8_t *qu, const float *su, float a, int8_t *t, float *st, int8_t *r, float *sr,
+                            uint64_t *rng_state_dev, void *stream);
+/* Q_IHT / Q_GD (test/performance/01_measure.h:923-946, 999-1021) with CloverMatrix8 and CloverVector8 vectors -- the reference's pure
+ * 8-bit configuration (test/performance/02_bit08.cpp).  Arguments as clm4_iht_v8, Phi (m x n) and PhiT (n x m) being CloverMatrix8 images:
+ * x.clear(), then `iterations` times  t1 = Phi x; t2 = y - t1; t3 = PhiT t2; x += mu t3; x.threshold(K) over the first x_len elements
+ * (threshold: 0 = none, Q_GD; 1 = FAST; 2 = REFERENCE) -- 3 launches per iteration (2 without threshold), all on `stream`, nothing copied
+ * back.  m and n are multiples of 128, x_len <= n; x, t3 have n elements, y, t1, t2 have m; the six vectors are distinct buffers.
+ * iterations == 0 clears x and touches nothing else.  With an rng: as clm8_mvm_scale_and_add, no graph capture. */
+int  clm8_iht(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n,
+              int8_t *x, float *sx, uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1,
+              int8_t *t2, float *st2, int8_t *t3, float *st3, uint64_t iterations, uint64_t K, float mu, int threshold,
               uint64_t *rng_state_dev, void *stream);
 /* CloverMatrix8::mvm(const CloverVector32&, CloverVector32&) (CloverMatrix8.h:558-662): x: cols floats, r: rows floats.
  * Bit-identical (4 accumulators x 8 lanes, fma(f32(v * f32(s / 127)), q, acc), then (a1+a2)+(a3+a4) and _mm256_haddf32_ps). */

@@ -174,6 +174,17 @@ for n8 in (32768, 65536):
     rec(f"m8_mvm_v8_{n8}^2", mv8, lambda: hip.check(lib.clm8_mvm(q8m.ptr, s8m.ptr, n8, n8, xv8.ptr, sxv8.ptr, rv8.ptr, srv8.ptr, None, None)))
     rec(f"m8_mvm_v8_stochastic_{n8}^2", mv8,
         lambda: hip.check(lib.clm8_mvm(q8m.ptr, s8m.ptr, n8, n8, xv8.ptr, sxv8.ptr, rv8.ptr, srv8.ptr, rng8.ptr, None)))
+    # the same mvm with the scaleAndAdd behind it in its epilogue (clm8_mvm_scale_and_add): + u read and r written, one wave of work per row group
+    uv8, suv8, r2v8, sr2v8 = hip.alloc(n8), hip.alloc(n8 // 16), hip.alloc(n8), hip.alloc(n8 // 16)
+    hip.check(lib.clv_fill_random_nibbles(uv8.ptr, n8, 48, 0, None))
+    hip.check(lib.clv_fill_random_scales(suv8.ptr, n8 // 64, 49, 0, None))
+    rec(f"m8_mvm_scale_and_add_{n8}^2", mv8 + 2 * (n8 + n8 // 16),
+        lambda: hip.check(lib.clm8_mvm_scale_and_add(q8m.ptr, s8m.ptr, n8, n8, xv8.ptr, sxv8.ptr, uv8.ptr, suv8.ptr, -1.0, rv8.ptr, srv8.ptr, r2v8.ptr,
+                                                     sr2v8.ptr, None, None)))
+    rec(f"m8_mvm_scale_and_add_stochastic_{n8}^2", mv8 + 2 * (n8 + n8 // 16),
+        lambda: hip.check(lib.clm8_mvm_scale_and_add(q8m.ptr, s8m.ptr, n8, n8, xv8.ptr, sxv8.ptr, uv8.ptr, suv8.ptr, -1.0, rv8.ptr, srv8.ptr, r2v8.ptr,
+                                                     sr2v8.ptr, rng8.ptr, None)))
+    del uv8, suv8, r2v8, sr2v8
     xf, rf = hip.alloc(4 * n8), hip.alloc(4 * n8)
     hip.check(lib.clv_fill_random_ints_f32(xf.ptr, n8, 10, 43, 0, None))
     rec(f"m8_mvm_f32_{n8}^2", vals + scs + 8 * n8, lambda: hip.check(lib.clm8_mvm_f32(q8m.ptr, s8m.ptr, n8, n8, xf.ptr, rf.ptr, None)))
@@ -216,6 +227,23 @@ for N8 in (8192, 16384):
         extra={"note": "bytes = the two matrices only; threshold in the reference's tie rule (the headers' default)"})
     rec(f"m8_q_iht_iteration_fast_threshold_N{N8}", itb, lambda: iht8_iteration(THRESHOLD_FAST), reps=5,
         extra={"note": "bytes = the two matrices only; threshold with lowest-index ties (-DCLOVER_FAST)"})
+    # the same loop as ONE call (clm8_iht): x.clear(), then per iteration two fused mvm + scaleAndAdd launches and the threshold -- three
+    # launches instead of five (two for GD).  ms is per iteration: a call of LOOP_ITERS iterations, divided.  mu = 2^-24 keeps x finite over
+    # the call on these random operands (the launch-by-launch rows above run on whatever their x has become; the kernels' time does not
+    # depend on the data, the REFERENCE threshold's heap walk does)
+    LOOP_ITERS = 10
+
+    def iht8_loop(thr):
+        hip.check(lib.clm8_iht(P.ptr, sP.ptr, PT.ptr, sPT.ptr, m8r, n8c, vx.ptr, svx.ptr, n8c, vy.ptr, svy.ptr, vt1.ptr, svt1.ptr, vt2.ptr, svt2.ptr,
+                               vt3.ptr, svt3.ptr, LOOP_ITERS, K8, 2.0 ** -24, thr, None, None))
+    for row, thr, note in ((f"m8_iht_loop_N{N8}", 1, "threshold with lowest-index ties (-DCLOVER_FAST)"),
+                           (f"m8_iht_loop_reference_threshold_N{N8}", 2, "threshold in the reference's tie rule (the headers' default)"),
+                           (f"m8_gd_loop_N{N8}", 0, "no threshold (Q_GD)")):
+        if ONLY and ONLY not in row:
+            continue
+        rec(row, itb * LOOP_ITERS, lambda thr=thr: iht8_loop(thr), reps=2,
+            extra={"note": f"one clm8_iht call of {LOOP_ITERS} iterations, ms per iteration; bytes = the two matrices only; " + note})
+        res[row]["ms"] = round(res[row]["ms"] / LOOP_ITERS, 5)
     del P, sP, PT, sPT, vx, svx, vt3, svt3, vy, svy, vt1, svt1, vt2, svt2
 # ---- CloverVector16 / CloverMatrix16: raw binary16, 2 bytes per element, no scales
 if not ONLY or "f16" in ONLY:
