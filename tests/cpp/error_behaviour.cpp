@@ -1,7 +1,9 @@
 // error_behaviour.cpp -- the containers keep the reference's error convention: a message on stdout and exit(1)
 // (CloverMatrix4.h:779-782, CloverVector4.h:100-101).  The shape checks run before any device work, so this
 // program needs no GPU.  argv[1] selects the case.
+#include <CloverMatrix16.h>
 #include <CloverMatrix4.h>
+#include <CloverMatrix8.h>
 #include <CloverVector4.h>
 
 #include <cstring>
@@ -24,6 +26,43 @@ int main(int argc, char **argv)
     } else if (!strcmp(which, "transpose")) {
         CloverMatrix4 A(128, 256), T(128, 256); // T must be 256 x 128
         A.transpose(T);
+    } else if (!strcmp(which, "m8_mvm")) {      // the same three checks on CloverMatrix8 (check_mvm, check_transpose, check_same_size) ...
+        CloverMatrix8 A(128, 256);
+        CloverVector8 x(128), r(128);           // x must have 256 elements
+        A.mvm(x, r);
+    } else if (!strcmp(which, "m8_mvm32")) {
+        CloverMatrix8 A(128, 256);
+        CloverVector32 x(256), r(256);          // r must have 128 elements
+        A.mvm(x, r);
+    } else if (!strcmp(which, "m8_transpose")) {
+        CloverMatrix8 A(128, 256), T(128, 256); // T must be 256 x 128
+        A.transpose(T);
+    } else if (!strcmp(which, "m8_quantize")) {
+        CloverMatrix32 A32(128, 128);
+        CloverMatrix8 A(128, 256);
+        A.quantize(A32);                        // shapes differ
+    } else if (!strcmp(which, "m16_mvm")) {     // ... and on CloverMatrix16
+        CloverMatrix16 A(128, 256);
+        CloverVector16 x(128), r(128);
+        A.mvm(x, r);
+    } else if (!strcmp(which, "m16_mvm32")) {
+        CloverMatrix16 A(128, 256);
+        CloverVector32 x(256), r(256);
+        A.mvm(x, r);
+    } else if (!strcmp(which, "m16_transpose")) {
+        CloverMatrix16 A(128, 256), T(128, 256);
+        A.transpose(T);
+    } else if (!strcmp(which, "m16_quantize")) {
+        CloverMatrix32 A32(128, 128);
+        CloverMatrix16 A(128, 256);
+        A.quantize(A32);
+    } else if (!strcmp(which, "v16_quantize")) {
+        CloverVector32 x(256);
+        CloverVector16 v(128);
+        v.quantize(x);                          // lengths differ
+    } else if (!strcmp(which, "v16_scaleAndAdd")) {
+        CloverVector16 u(128), v(256);
+        u.scaleAndAdd(v, 0.5f);
     } else if (!strcmp(which, "layout")) {
         // host-side layout contract: padding to 128, zeroed value padding, padding scales 1.0, scales right behind values
         CloverVector4 v(100);
