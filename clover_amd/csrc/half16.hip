@@ -98,6 +98,14 @@ __global__ __launch_bounds__(256) void k_f16_scale_and_add(const h16x8 *u, const
     }
 }
 
+// CloverVector16::clear() on the stream (the first step of clm_f16_iht): a kernel, not a memset, so that a captured call replays it as one
+// more kernel node in stream order
+__global__ __launch_bounds__(256) void k_f16_clear(u32x4 *__restrict__ h, uint64_t ngroups)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += stride) h[g] = u32x4{0u, 0u, 0u, 0u};
+}
+
 // ================================================================================================
 // the 32 chains and their tree
 // ================================================================================================
@@ -162,11 +170,44 @@ __device__ __forceinline__ void f16_mvm_steps(const h16x8 *__restrict__ Ap, cons
     }
 }
 
-template <int WAVES, bool NT, bool XF32>
+// FUSE... = F16Fuse (clm_f16_mvm_scale_and_add, k_f16_mvm_saa below): the CloverVector16::scaleAndAdd that follows this mvm in the IHT / GD loops
+// (CloverVector16.h:309-386), done by the lane that stores the row: v = f16(d); r2[row] = f16(fma(f32(v), a, f32(u[row]))) -- the ROUNDED
+// v widened again, as two separate calls compute.  A row depends on no other row: no workgroup-wide step.  u[row] is requested before the
+// streaming loop.  r (the f16 A x, t of the ABI) may be NULL under FUSE: it is then not stored.
+// The flag is a trailing parameter pack, empty or one F16Fuse, and the kernel itself is the shared template: with the body in an inlined
+// device function the fp32-vector instantiations came out two instructions longer (another base for the unrolled loads); this way every
+// <WAVES, NT, XF32> instantiation keeps its signature and, instruction for instruction, the code it had.
+struct F16Fuse {
+    const uint16_t *u;
+    float a;
+    uint16_t *r2;            // may alias u (the in-place form): a lane reads its element of u before it writes it
+};
+__device__ __forceinline__ uint16_t f16_fuse_load_u(uint64_t) { return 0; }
+__device__ __forceinline__ uint16_t f16_fuse_load_u(uint64_t row, const F16Fuse &f) { return f.u[row]; }
+__device__ __forceinline__ void f16_fuse_store(void *, uint64_t, float, uint16_t) {}
+__device__ __forceinline__ void f16_fuse_store(void *t, uint64_t row, float d, uint16_t ub, const F16Fuse &f)
+{
+    _Float16 v = (_Float16)d, uh;                                        // _mm256_cvtps_ph(.., 0) of the row block (:302-306)
+    uint16_t vb;
+    __builtin_memcpy(&vb, &v, 2);
+    __builtin_memcpy(&uh, &ub, 2);
+    if (t) reinterpret_cast<uint16_t *>(t)[row] = vb;
+    // widening, fma and conversion stay the three instructions of k_f16_scale_and_add -- v_cvt_f32_f16, v_fma_f32, v_cvt_f16_f32 (left
+    // alone, hipcc folds them into v_fma_mixlo_f16 here)
+    float vf = (float)v;
+    asm volatile("" : "+v"(vf));
+    float s = __builtin_fmaf(vf, f.a, (float)uh);
+    asm volatile("" : "+v"(s));
+    f.r2[row] = f16_bits(s);
+}
+
+// fuse.r2 may be fuse.u: the lane that writes r2[row] has read u[row] before the loop.  r (t of the ABI) is apart from x, u and r2.
+template <int WAVES, bool NT, bool XF32, typename... FUSE>
 __global__ __launch_bounds__(64 * WAVES) void k_f16_mvm(const uint16_t *__restrict__ A, uint64_t rows, uint64_t cols, const void *__restrict__ x,
-                                                        void *__restrict__ r)
+                                                        void *__restrict__ r, FUSE... fuse)
 {
     __shared__ __attribute__((aligned(16))) char xs[F16_X_BYTES];
+    constexpr bool FUSED = sizeof...(FUSE) != 0;
     constexpr int THREADS = 64 * WAVES;
     constexpr int XB = XF32 ? 4 : 2;
     constexpr uint32_t CH = F16_X_BYTES / XB;                 // elements of x per chunk
@@ -175,6 +216,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_f16_mvm(const uint16_t *__restri
     const uint64_t row = (uint64_t)blockIdx.x * (16 * WAVES) + rho;
     const h16x8 *Arow = reinterpret_cast<const h16x8 *>(A + (row < rows ? row : rows - 1) * cols);
     float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    uint16_t fuse_u = 0;
+    if (FUSED && p == 0 && row < rows) fuse_u = f16_fuse_load_u(row, fuse...);      // ahead of the streaming loop: the epilogue waits on nothing
 
     for (uint64_t c0 = 0; c0 < cols; c0 += CH) {
         const uint32_t cw = (uint32_t)((cols - c0) < CH ? (cols - c0) : CH);
@@ -197,10 +240,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_f16_mvm(const uint16_t *__restri
     }
     const float d = f16_chain_tree(acc);
     if (p == 0 && row < rows) {
-        if (XF32) reinterpret_cast<float *>(r)[row] = d;
+        if (FUSED) f16_fuse_store(r, row, d, fuse_u, fuse...);
+        else if (XF32) reinterpret_cast<float *>(r)[row] = d;
         else reinterpret_cast<uint16_t *>(r)[row] = f16_bits(d);         // _mm256_cvtps_ph(.., 0) of the row block (:302-306)
     }
 }
+#define k_f16_mvm_saa(WAVES, NT) k_f16_mvm<WAVES, NT, false, F16Fuse>
 
 // ================================================================================================
 // dot  (CloverVector16.h:473-530)
@@ -473,6 +518,60 @@ extern "C" int clm_f16_mvm(const uint16_t *A, uint64_t rows, uint64_t cols, cons
 extern "C" int clm_f16_mvm_f32(const uint16_t *A, uint64_t rows, uint64_t cols, const float *x, float *r, void *stream)
 {
     return f16_mvm<true>("clm_f16_mvm_f32", A, rows, cols, x, r, stream);
+}
+
+#define F16_SAA "clm_f16_mvm_scale_and_add"
+extern "C" int clm_f16_mvm_scale_and_add(const uint16_t *A, uint64_t rows, uint64_t cols, const uint16_t *x, const uint16_t *u, float a, uint16_t *t,
+                                         uint16_t *r, void *stream)
+{
+    CLV_REQUIRE(A && x && u && r, F16_SAA ": null pointer");
+    CLV_REQUIRE(F16_ALIGNED(A) && F16_ALIGNED(x), F16_SAA ": the matrix and x must be 16-byte aligned");
+    CLV_REQUIRE(((uintptr_t)u & 1u) == 0 && ((uintptr_t)t & 1u) == 0 && ((uintptr_t)r & 1u) == 0, F16_SAA ": u, t and r must be 2-byte aligned");
+    CLV_REQUIRE(cols % 128 == 0, F16_SAA ": cols=%llu must be a multiple of 128", (unsigned long long)cols);
+    CLV_REQUIRE(r != x && t != x, F16_SAA ": the results must not alias the vector being multiplied");
+    CLV_REQUIRE(t != r && (!t || t != u), F16_SAA ": t must not alias r or u");
+    CLV_REQUIRE(rows / 16 < 0x7FFFFFFFull, F16_SAA ": matrix too large");
+    if (!rows) return CLV_OK;
+    hipStream_t st = as_stream(stream);
+    const bool streaming = F16_STREAMING(rows * cols * 2);                // the workgroup and nontemporal rules of f16_mvm()
+    const F16Fuse fuse = {u, a, r};
+    if (rows / 64 >= 2 * (uint64_t)clv_cu_count()) {
+        const dim3 grid((unsigned)((rows + 63) / 64)), block(256);
+        if (streaming) hipLaunchKernelGGL((k_f16_mvm_saa(4, true)), grid, block, 0, st, A, rows, cols, (const void *)x, (void *)t, fuse);
+        else hipLaunchKernelGGL((k_f16_mvm_saa(4, false)), grid, block, 0, st, A, rows, cols, (const void *)x, (void *)t, fuse);
+    } else {
+        const dim3 grid((unsigned)((rows + 15) / 16)), block(64);
+        if (streaming) hipLaunchKernelGGL((k_f16_mvm_saa(1, true)), grid, block, 0, st, A, rows, cols, (const void *)x, (void *)t, fuse);
+        else hipLaunchKernelGGL((k_f16_mvm_saa(1, false)), grid, block, 0, st, A, rows, cols, (const void *)x, (void *)t, fuse);
+    }
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+#undef F16_SAA
+
+// Q_IHT / Q_GD (test/performance/01_measure.h:923-946, 999-1021) over a CloverMatrix16 with CloverVector16 vectors
+// (test/performance/02_bit16.cpp:112-117).  One call enqueues all iterations: 3 launches per iteration (2 for GD), nothing copied back.
+extern "C" int clm_f16_iht(const uint16_t *Phi, const uint16_t *PhiT, uint64_t m, uint64_t n, uint16_t *x, uint64_t x_len, const uint16_t *y,
+                           uint16_t *t1, uint16_t *t2, uint16_t *t3, uint64_t iterations, uint64_t K, float mu, int threshold, void *stream)
+{
+    CLV_REQUIRE(Phi && PhiT && x && y && t1 && t2 && t3, "clm_f16_iht: null pointer");
+    CLV_REQUIRE(m % 128 == 0 && n % 128 == 0 && x_len <= n, "clm_f16_iht: m=%llu n=%llu x_len=%llu", (unsigned long long)m, (unsigned long long)n,
+                (unsigned long long)x_len);
+    CLV_REQUIRE(threshold >= 0 && threshold <= 2, "clm_f16_iht: unknown threshold %d", threshold);
+    CLV_REQUIRE(F16_ALIGNED(Phi) && F16_ALIGNED(PhiT) && F16_ALIGNED(x) && F16_ALIGNED(t2), "clm_f16_iht: the matrices, x and t2 must be 16-byte aligned");
+    if (n) {                                                                                             // x.clear()
+        const uint64_t ng = n / 8, want = (ng + 255) / 256;
+        hipLaunchKernelGGL(k_f16_clear, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, as_stream(stream), (u32x4 *)x, ng);
+        CLV_LAUNCH_CHECK();
+    }
+    int rc = CLV_OK;
+    for (uint64_t it = 0; !rc && it < iterations; it++) {
+        rc = clm_f16_mvm_scale_and_add(Phi, m, n, x, y, -1.0f, t1, t2, stream);                          // t1 = Phi x; t2 = y - t1
+        if (!rc) rc = clm_f16_mvm_scale_and_add(PhiT, n, m, t2, x, mu, t3, x, stream);                   // t3 = Phi' t2; x += mu t3
+        if (!rc && threshold)                                                          // keep the K largest (2: the reference's survivor order)
+            rc = clv_f16_threshold_mode(x, x_len, n, K, threshold == 2 ? CLV_THRESHOLD_REFERENCE : CLV_THRESHOLD_FAST, nullptr, stream);
+    }
+    return rc;
 }
 
 extern "C" int clm_f16_transpose(const uint16_t *h, uint64_t rows, uint64_t cols, uint16_t *ht, void *stream)

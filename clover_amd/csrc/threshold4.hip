@@ -551,6 +551,116 @@ __global__ __launch_bounds__(TS_THREADS) void k_thresh8_small(uint32_t *__restri
     }
 }
 
+// ---- single-workgroup path for CloverVector16 (n_pad <= TS_THREADS * TS_MAXW * 2 = 32768): the structure of k_thresh_small -- the
+// thread's W words (two elements each) in registers, bins in TSF_COPIES bank-spread LDS copies chosen by the lane, ONE barrier per radix
+// level, every wave scanning the selection itself, lowest-index ties by a prefix over thread order -- straight over the elements, as
+// k_thresh8_small (binary16 has no blocks to share magnitudes).
+// Keys are ThreshElems<16>::key = f16_abs_key, the fp32 bits of the exact widening, so the kernel orders NaN patterns as
+// threshold_large<16> does (the widening quiets signalling NaNs: the raw 15-bit pattern would order them differently).  Such a key is 0,
+// or has one of the 40 exponents 103 .. 142 with its low 13 mantissa bits clear, or exponent 255: f16_dense_key maps it, order kept and
+// one to one, onto 16 bits -- (exponent - 102) << 10 | 10 mantissa bits, 41 for exponent 255 -- and the select runs in two 8-bit levels
+// over that instead of four over the fp32 pattern.  Same order, same selected set, same tie rule: bit-identical to the large-vector path.
+#define TSF_COPIES 4
+#define TSF_CS 260
+#define TSF_KEY_INF (41u << 10)        // f16_dense_key(0x7F800000)
+__device__ __forceinline__ uint32_t f16_dense_key(uint32_t key)
+{
+    const uint32_t e = key >> 23;
+    const uint32_t ed = e == 0 ? 0u : (e > 142u ? 41u : e - 102u);
+    return (ed << 10) | ((key >> 13) & 0x3FFu);
+}
+
+template <int W>
+__global__ __launch_bounds__(TS_THREADS) void k_f16_thresh_small(uint32_t *__restrict__ q, uint32_t n, uint32_t k)
+{
+    typedef ThreshElems<16> E;
+    __shared__ __attribute__((aligned(16))) uint32_t hist[2 * TSF_COPIES * TSF_CS];
+    __shared__ uint32_t wtot[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t nwords = (n + 1) / 2;
+    const uint32_t w0 = tid * W;
+    uint32_t w[W], ck[W];                                                // ck: the two dense keys of the word, element 0 low
+    uint32_t valid = 0;                                                  // bit 2 j + e: element e of word j exists (index < n)
+#pragma unroll
+    for (int j = 0; j < W; j++) w[j] = q[w0 + j < nwords ? w0 + j : 0];
+#pragma unroll
+    for (int j = 0; j < W; j++) {
+        const uint32_t i = w0 + j;
+        ck[j] = f16_dense_key(E::key(w[j], 0, 0.0f)) | (f16_dense_key(E::key(w[j], 1, 0.0f)) << 16);
+        if (2 * i < n) valid |= 1u << (2 * j);
+        if (2 * i + 1 < n) valid |= 2u << (2 * j);
+    }
+    for (int i = tid; i < 2 * TSF_COPIES * TSF_CS; i += TS_THREADS) hist[i] = 0;
+    __syncthreads();                                                     // bins zero before anybody adds to them
+
+    uint32_t tau = TSF_KEY_INF, keep = 0;                                // k = 0: nothing finite survives, as the large-vector path's state
+    if (k != 0) {
+        uint32_t prefix = 0, need = k;
+#pragma unroll
+        for (int level = 0; level < 2; level++) {
+            const int shift = 8 - 8 * level;
+            uint32_t *h = hist + TSF_COPIES * TSF_CS * level, *hc = h + TSF_CS * (lane & (TSF_COPIES - 1));
+#pragma unroll
+            for (int j = 0; j < W; j++)
+#pragma unroll
+                for (int e = 0; e < 2; e++)
+                    if ((valid >> (2 * j + e)) & 1u) {
+                        const uint32_t c = (ck[j] >> (16 * e)) & 0xFFFFu;
+                        if (level == 0 || (c >> 8) == prefix) atomicAdd(&hc[(c >> shift) & 0xFFu], 1u);
+                    }
+            __syncthreads();
+            // every wave selects for itself: lane l owns bins 255 - 4 l ... 252 - 4 l (from the top), added up over the copies
+            uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+#pragma unroll
+            for (int cpy = 0; cpy < TSF_COPIES; cpy++) {
+                const u32x4 h4 = *reinterpret_cast<const u32x4 *>(h + TSF_CS * cpy + 252 - 4 * lane);
+                t0 += h4.w; t1 += h4.z; t2 += h4.y; t3 += h4.x;
+            }
+            const uint32_t sum = t0 + t1 + t2 + t3;
+            const uint32_t incl = wave_scan_incl(sum);
+            const unsigned long long hit = __ballot(incl >= need && incl - sum < need);
+            const int L = __builtin_ctzll(hit);                          // exactly one lane: the level's total is >= need (k < n)
+            uint32_t above = __shfl(incl - sum, L);
+            const uint32_t T0 = __shfl(t0, L), T1 = __shfl(t1, L), T2 = __shfl(t2, L);
+            uint32_t pick = 0;
+            if (above + T0 < need) { above += T0; pick = 1;
+                if (above + T1 < need) { above += T1; pick = 2;
+                    if (above + T2 < need) { above += T2; pick = 3; } } }
+            prefix = (prefix << 8) | (255u - 4u * (uint32_t)L - pick);
+            need -= above;
+        }
+        tau = prefix;
+        keep = need;
+    }
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < W; j++)
+#pragma unroll
+        for (int e = 0; e < 2; e++) c += ((valid >> (2 * j + e)) & 1u) && ((ck[j] >> (16 * e)) & 0xFFFFu) == tau;
+    // ties in index order: the first `keep` of them survive (one barrier: the 16 wave totals)
+    const uint32_t vinc = wave_scan_incl(c);
+    if (lane == 63) wtot[wave] = vinc;
+    __syncthreads();
+    const uint32_t tot = lane < 16 ? wtot[lane] : 0;
+    const uint32_t inc = wave_scan_incl(tot);
+    uint32_t rank = vinc - c + __shfl(inc - tot, wave);
+#pragma unroll
+    for (int j = 0; j < W; j++) {
+        const uint32_t i = w0 + j;
+        if (i < nwords) {
+            uint32_t outw = 0;
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const uint32_t half = w[j] & E::mask(e), key = (ck[j] >> (16 * e)) & 0xFFFFu;
+                if (!((valid >> (2 * j + e)) & 1u)) { outw |= half; continue; }              // padding is left alone
+                if (key > tau) outw |= half;
+                else if (key == tau) { if (rank < keep) outw |= half; rank++; }
+            }
+            q[i] = outw;
+        }
+    }
+}
+
 // ---- large CloverVector4 vectors: the same weighted-candidate idea as k_thresh_small, across kernels ----------------------------
 // One pass turns every 64-element block into its 9 magnitude counts (8 bytes); the three radix levels then run over these
 // tables (12 bytes per block instead of 36 bytes of elements, 9 weighted histogram updates per block instead of 64), the tie
@@ -1785,7 +1895,8 @@ extern "C" int clv8_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64
 }
 
 // CloverVector16::threshold(K) / threshold_min_heap (CloverVector16.h:612-768): the same selection on |f32(h)|, two elements per word and no
-// scales.  Every n takes the large-vector path (the one-workgroup kernels above are written for the 4- and 8-bit word layouts).
+// scales.  FAST: k_f16_thresh_small up to n_pad = 32768 (one launch, no workspace), the large-vector path beyond -- and at every n with
+// CLV_F16_THRESHOLD_SMALL=0 (read per call: A/B runs flip it); the two give the same bits.
 extern "C" uint64_t clv_f16_threshold_workspace_bytes(uint64_t n_pad)
 {
     const uint64_t blocks = (n_pad / 2 + TH_WORDS_PER_BLOCK - 1) / TH_WORDS_PER_BLOCK;
@@ -1801,6 +1912,18 @@ extern "C" int clv_f16_threshold_mode(uint16_t *h, uint64_t n, uint64_t n_pad, u
     CLV_REQUIRE_WORKSPACE("clv_f16_threshold_mode", workspace);
     if (k >= n || n == 0) return CLV_OK;
     if (mode == CLV_THRESHOLD_REFERENCE) return threshold_reference<16>((uint32_t *)h, nullptr, n, n_pad, k, workspace, as_stream(stream));
+    if (n_pad <= (uint64_t)TS_THREADS * TS_MAXW * 2 && clv_env_int("CLV_F16_THRESHOLD_SMALL", 1)) {
+        const uint64_t w = ((n + 1) / 2 + TS_THREADS - 1) / TS_THREADS;
+#define TF_LAUNCH(W) hipLaunchKernelGGL(k_f16_thresh_small<W>, dim3(1), dim3(TS_THREADS), 0, as_stream(stream), (uint32_t *)h, (uint32_t)n, (uint32_t)k)
+        if (w <= 1) TF_LAUNCH(1);
+        else if (w <= 2) TF_LAUNCH(2);
+        else if (w <= 4) TF_LAUNCH(4);
+        else if (w <= 8) TF_LAUNCH(8);
+        else TF_LAUNCH(16);
+#undef TF_LAUNCH
+        CLV_LAUNCH_CHECK();
+        return CLV_OK;
+    }
     if (!workspace) {
         int rc = clv_internal_workspace(&workspace, clv_f16_threshold_workspace_bytes(n_pad), as_stream(stream));
         if (rc) return rc;

@@ -108,6 +108,8 @@ SIGNATURES = {
     "clm_f16_quantize": (C.c_int, [_vp, _u64, _u64, _vp, _vp]),
     "clm_f16_mvm": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
     "clm_f16_mvm_f32": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm_f16_mvm_scale_and_add": (C.c_int, [_vp, _u64, _u64, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "clm_f16_iht": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
     "clm_f16_transpose": (C.c_int, [_vp, _u64, _u64, _vp, _vp]),
     "clm4_iht": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
                           C.c_float, C.c_int, _vp, _vp]),
@@ -493,6 +495,27 @@ class CloverHip:
         dA, dx, dr = self.to_device(hA), self.to_device(np.ascontiguousarray(x, dtype=np.float32)), self.alloc(max(4 * rows, 4))
         self.check(self.lib.clm_f16_mvm_f32(dA.ptr, rows, cols, dx.ptr, dr.ptr, None))
         return dr.download(np.float32, rows)
+
+    def mf16_mvm_scale_and_add(self, hA, rows, cols, hx, hu, a: float, in_place: bool = False, want_t: bool = True):
+        """(t, r) of clm_f16_mvm_scale_and_add; t is None when want_t is False.  hA may be a DevBuf (a matrix uploaded once)"""
+        dA = hA if isinstance(hA, DevBuf) else self.to_device(hA)
+        dx, du = self.to_device(hx), self.to_device(hu)
+        dt = self.alloc(max(2 * rows, 2)) if want_t else None
+        dr = du if in_place else self.alloc(max(2 * rows, 2))
+        self.check(self.lib.clm_f16_mvm_scale_and_add(dA.ptr, rows, cols, dx.ptr, du.ptr, a, dt.ptr if dt else None, dr.ptr, None))
+        return (dt.download(np.uint16, rows) if want_t else None), dr.download(np.uint16, rows)
+
+    def mf16_iht(self, hPhi, hPhiT, m, n, hy, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None, prefill: int = 0x55):
+        """clm_f16_iht on buffers prefilled with `prefill` bytes: {"x": bits, "t1": ..., "t2": ..., "t3": ...}"""
+        b = [self.to_device(v) for v in (hPhi, hPhiT, hy)]
+        lens = {"x": n, "t1": m, "t2": m, "t3": n}
+        v = {}
+        for name, ln in lens.items():
+            v[name] = self.alloc(2 * ln)
+            self.check(self.lib.clv_memset(v[name].ptr, prefill, v[name].nbytes, None))
+        self.check(self.lib.clm_f16_iht(b[0].ptr, b[1].ptr, m, n, v["x"].ptr, n if x_len is None else x_len, b[2].ptr, v["t1"].ptr, v["t2"].ptr,
+                                        v["t3"].ptr, iterations, K, mu, threshold, None))
+        return {name: v[name].download(np.uint16, ln) for name, ln in lens.items()}
 
     def mf16_transpose(self, h, rows, cols) -> np.ndarray:
         dh, dt = self.to_device(h), self.alloc(max(2 * rows * cols, 2))

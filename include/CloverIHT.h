@@ -13,7 +13,7 @@
 
 #include "CloverMatrix4.h"
 #include "CloverMatrix8.h"       /* Q_IHT<CloverMatrix8, CloverVector8> / Q_GD<...>: the specialisations at the end */
-#include "CloverMatrix16.h"      /* Q_IHT<CloverMatrix16, CloverVector16> / Q_GD<...>: the same templates */
+#include "CloverMatrix16.h"      /* Q_IHT<CloverMatrix16, CloverVector16> / Q_GD<...>: the specialisations at the end */
 #include "CloverVector4.h"
 
 /* Generic forms, for any container pair with the reference's method names (the five steps of 01_measure.h:930-944):
@@ -146,6 +146,24 @@ inline void Q_GD<CloverMatrix8, CloverVector8>(CloverMatrix8 &Phi, CloverMatrix8
         Phi.mvm_scaleAndAdd(x, y, -1.0f, t1, t2);
         PhiT.mvm_scaleAndAdd(t2, x, mu, t3);
     }
+}
+
+/* CloverMatrix16 with CloverVector16 vectors: the half-precision loop the reference measures in test/performance/02_bit16.cpp:112-117.
+ * Explicit specialisations again, so that the explicit and the deduced spelling both reach them, and unconditional: the 16-bit classes
+ * have no stochastic rounding.  The whole loop in one call (CloverMatrix16::iht_loop -> clm_f16_iht): three launches per iteration, two
+ * for Q_GD, the bits of the generic templates' five method calls. */
+template <>
+inline void Q_IHT<CloverMatrix16, CloverVector16>(CloverMatrix16 &Phi, CloverMatrix16 &PhiT, CloverVector16 &x, CloverVector16 &y, CloverVector16 &t1,
+                                                  CloverVector16 &t2, CloverVector16 &t3, const uint64_t iterations, const uint64_t K, const float mu)
+{
+    Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, K, mu, true);
+}
+
+template <>
+inline void Q_GD<CloverMatrix16, CloverVector16>(CloverMatrix16 &Phi, CloverMatrix16 &PhiT, CloverVector16 &x, CloverVector16 &y, CloverVector16 &t1,
+                                                 CloverVector16 &t2, CloverVector16 &t3, const uint64_t iterations, const float mu)
+{
+    Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, 0, mu, false);
 }
 
 #endif

@@ -12,8 +12,11 @@
  *                                           (:98-131: one running fp32 sum per row; for fp32 vectors a double accumulation, :310-319),
  *                                           transpose_scalar (:424-439)
  *
- * Q_IHT<CloverMatrix16, CloverVector16> and Q_GD<...> are the generic templates of CloverIHT.h (which includes this header): every step
- * is a kernel on the device mirrors, nothing is copied back between steps.
+ *   mvm_scaleAndAdd                      -> clm_f16_mvm_scale_and_add  (not in the reference: mvm + the scaleAndAdd behind it, one launch)
+ *   iht_loop                             -> clm_f16_iht        (the whole Q_IHT / Q_GD loop of 01_measure.h:923-946, 999-1021 in one call)
+ *
+ * Q_IHT<CloverMatrix16, CloverVector16> and Q_GD<...> are specialised in CloverIHT.h (which includes this header) and call iht_loop: every
+ * step is a kernel on the device mirrors, nothing is copied back between steps.
  */
 #ifndef CLOVER_MATRIX16_H
 #define CLOVER_MATRIX16_H
@@ -116,6 +119,47 @@ public:
         resultVector.commit();
     }
     void mvm_parallel(const CloverVector16 &productVector, CloverVector16 &resultVector) const { mvm(productVector, resultVector); }
+    /* Not in the reference: t = this * x immediately followed by r = f16(u + a * t), the pair of steps the IHT / GD loops repeat
+     * (01_measure.h:940-941, :942-943), as CloverMatrix8::mvm_scaleAndAdd: one launch, the bits of mvm(x, t); u.scaleAndAdd(t, a, r). */
+    void mvm_scaleAndAdd(const CloverVector16 &x, const CloverVector16 &u, float a, CloverVector16 &t, CloverVector16 &r) const
+    {
+        check_mvm(x, t);
+        if (u.size_pad() != getRows() || r.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        clover_hip::check(clm_f16_mvm_scale_and_add(dev_values(), rows, cols, x.dev_values_ro(), u.dev_values_ro(), a, t.dev_values_wo(),
+                                                    r.dev_values_wo(), nullptr), "CloverMatrix16::mvm_scaleAndAdd");
+        t.commit();
+        r.commit();
+    }
+    /* in place: u = f16(u + a * (this * x)) */
+    void mvm_scaleAndAdd(const CloverVector16 &x, CloverVector16 &u, float a, CloverVector16 &t) const
+    {
+        check_mvm(x, t);
+        if (u.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        uint16_t *du = u.dev_values_rw();
+        clover_hip::check(clm_f16_mvm_scale_and_add(dev_values(), rows, cols, x.dev_values_ro(), du, a, t.dev_values_wo(), du, nullptr),
+                          "CloverMatrix16::mvm_scaleAndAdd");
+        t.commit();
+        u.commit();
+    }
+    /* The WHOLE IHT / GD loop of 01_measure.h:923-946, 999-1021 with this matrix as Phi, in one call (clm_f16_iht): x.clear(), then
+     * `iterations` times t1 = Phi x; t2 = y - t1; t3 = PhiT t2; x += mu t3; [threshold(K)] -- three launches per iteration (two without
+     * threshold), the bits of the five method calls.  The threshold is the one x.threshold_parallel(K) would take under the exactness
+     * switch (default: the reference's survivors). */
+    void iht_loop(const CloverMatrix16 &PhiT, CloverVector16 &x, const CloverVector16 &y, CloverVector16 &t1, CloverVector16 &t2,
+                  CloverVector16 &t3, uint64_t iterations, uint64_t K, float mu, bool with_threshold) const
+    {
+        if (PhiT.getRows() != getCols() || PhiT.getCols() != getRows() || x.size_pad() != getCols() || y.size_pad() != getRows() ||
+            t1.size_pad() != getRows() || t2.size_pad() != getRows() || t3.size_pad() != getCols()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm_f16_iht(dev_values(), PhiT.dev_values(), rows, cols, x.dev_values_wo(), x.size(), y.dev_values_ro(),
+                                      t1.dev_values_wo(), t2.dev_values_wo(), t3.dev_values_wo(), iterations, K, mu, thr, nullptr),
+                          "CloverMatrix16::iht_loop");
+        x.commit();
+        if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
+    }
     /* :98-131: one running fp32 sum of separately rounded products per row, rounded to f16 */
     void mvm_scalar(const CloverVector16 &productVector, CloverVector16 &resultVector) const
     {

@@ -350,7 +350,9 @@ uint64_t clv_f16_dot_workspace_bytes(uint64_t n_pad);
 int  clv_f16_dot(const uint16_t *u, const uint16_t *v, uint64_t n_pad, int mode, float *out_dev, void *workspace, void *stream);
 /* CloverVector16::threshold (CloverVector16.h:612-626) and ::threshold_min_heap (:628-673) on |f32(h)|: CLV_THRESHOLD_FAST keeps the same
  * multiset of magnitudes with lowest-index ties, CLV_THRESHOLD_REFERENCE the reference's survivors index for index (its heap walk);
- * survivors keep their bits, the other elements below n become 0x0000.  Workspace (NULL = the stream's scratch):
+ * survivors keep their bits, the other elements below n become 0x0000.  FAST up to n_pad = 32768 is one launch of a one-workgroup kernel
+ * that uses no workspace (a caller's workspace is validated and left untouched; CLV_F16_THRESHOLD_SMALL=0 in the environment, read per
+ * call, keeps the large-vector path at every n -- same bits).  Workspace (NULL = the stream's scratch):
  * clv_f16_threshold_workspace_bytes(n_pad) for FAST, clv_threshold_reference_workspace_bytes_k(n_pad, k) for REFERENCE and the heap form
  * (heap_dev: k entries {fp32 |value|, uint32 index}, 1 <= k <= n).  16-byte aligned, no initialisation. */
 uint64_t clv_f16_threshold_workspace_bytes(uint64_t n_pad);
@@ -365,6 +367,28 @@ int  clm_f16_mvm(const uint16_t *A, uint64_t rows, uint64_t cols, const uint16_t
 /* CloverMatrix16::mvm(const CloverVector32 &, CloverVector32 &) (CloverMatrix16.h:321-381): the same chains and tree with x as fp32, the
  * row value stored as fp32.  Bit-identical. */
 int  clm_f16_mvm_f32(const uint16_t *A, uint64_t rows, uint64_t cols, const float *x, float *r, void *stream);
+/* clm_f16_mvm immediately followed by clv_f16_scale_and_add on its result (CloverMatrix16.h:230-308, then CloverVector16.h:309-386), one
+ * launch -- the pair of steps the IHT / GD loops repeat (test/performance/01_measure.h:940-943, 1016-1019).  Per row:
+ *   v = f16(row dot), stored to t[row] only if t is given (t may be NULL);  r[row] = f16(fma(f32(v), a, f32(u[row]))),
+ * the fma taking the ROUNDED v widened again: bit-identical to the two calls.  u, t and r have `rows` elements.  r may be u (the in-place
+ * form x += a t); t and r must not alias x or each other, and t must not be u.  cols is a multiple of 128, any row count is accepted (a
+ * row shard at pointer offsets); A and x are 16-byte aligned, u, t and r need only their element alignment.  A violation returns
+ * CLV_ERR_INVALID before any device work.  No workspace and no state: captures into a hipGraph. */
+int  clm_f16_mvm_scale_and_add(const uint16_t *A, uint64_t rows, uint64_t cols, const uint16_t *x, const uint16_t *u, float a,
+                               uint16_t *t, uint16_t *r, void *stream);
+/* Q_IHT / Q_GD (test/performance/01_measure.h:923-946, 999-1021) with CloverMatrix16 and CloverVector16 vectors, the loop the reference
+ * measures in test/performance/02_bit16.cpp:112-117.  Arguments as clm8_iht without scales and generator, Phi (m x n) and PhiT (n x m)
+ * being CloverMatrix16 images: x.clear() over all n elements, then `iterations` times
+ *   t1 = Phi x; t2 = y - t1; t3 = PhiT t2; x += mu t3; x.threshold(K) over the first x_len elements
+ * (threshold: 0 = none, Q_GD; 1 = FAST; 2 = REFERENCE) -- 3 launches per iteration (2 without threshold) instead of the 13 of the method
+ * calls, all on `stream`, nothing copied back, bit-identical to them.  m and n are multiples of 128, x_len <= n; x, t3 have n elements,
+ * y, t1, t2 have m; the six vectors are distinct buffers, 16-byte aligned.  iterations == 0 clears x and touches nothing else.
+ * There is no generator state, so the call captures into a hipGraph whenever its threshold step needs no first-use allocation: GD, and
+ * FAST with n <= 32768 (the one-workgroup kernel, no workspace).  REFERENCE and FAST beyond n = 32768 take the stream's scratch for the
+ * threshold (first call on a stream outside a capture), as clm8_iht does. */
+int  clm_f16_iht(const uint16_t *Phi, const uint16_t *PhiT, uint64_t m, uint64_t n, uint16_t *x, uint64_t x_len,
+                 const uint16_t *y, uint16_t *t1, uint16_t *t2, uint16_t *t3,
+                 uint64_t iterations, uint64_t K, float mu, int threshold, void *stream);
 /* CloverMatrix16::transpose / transpose_parallel (CloverMatrix16.h:424-474): ht(j,i) = h(i,j); h is rows x cols, ht is cols x rows
  * (multiples of 8: a whole matrix has multiples of 128); not in place.  Exact. */
 int  clm_f16_transpose(const uint16_t *h, uint64_t rows, uint64_t cols, uint16_t *ht, void *stream);

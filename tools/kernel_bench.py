@@ -43,11 +43,15 @@ def timeit(fn, reps=10, rounds=5, warm=2):
 res = {}
 
 
-ONLY = os.environ.get("KB_ONLY")      # substring filter: KB_ONLY=scale_and_add python tools/kernel_bench.py
+ONLY = os.environ.get("KB_ONLY")      # substring filter, or several separated by commas: KB_ONLY=scale_and_add python tools/kernel_bench.py
+
+
+def selected(name):
+    return not ONLY or any(o in name for o in ONLY.split(","))
 
 
 def rec(name, nbytes, fn, extra=None, reps=10):
-    if ONLY and ONLY not in name:
+    if not selected(name):
         return
     ms = timeit(fn, reps=reps)
     res[name] = {"ms": round(ms, 5), "GB/s": round(nbytes / ms / 1e6, 1), "frac_of_8TBs": round(nbytes / ms / 1e6 / 8000.0, 4)}
@@ -239,25 +243,29 @@ for N8 in (8192, 16384):
     for row, thr, note in ((f"m8_iht_loop_N{N8}", 1, "threshold with lowest-index ties (-DCLOVER_FAST)"),
                            (f"m8_iht_loop_reference_threshold_N{N8}", 2, "threshold in the reference's tie rule (the headers' default)"),
                            (f"m8_gd_loop_N{N8}", 0, "no threshold (Q_GD)")):
-        if ONLY and ONLY not in row:
+        if not selected(row):
             continue
         rec(row, itb * LOOP_ITERS, lambda thr=thr: iht8_loop(thr), reps=2,
             extra={"note": f"one clm8_iht call of {LOOP_ITERS} iterations, ms per iteration; bytes = the two matrices only; " + note})
         res[row]["ms"] = round(res[row]["ms"] / LOOP_ITERS, 5)
     del P, sP, PT, sPT, vx, svx, vt3, svt3, vy, svy, vt1, svt1, vt2, svt2
 # ---- CloverVector16 / CloverMatrix16: raw binary16, 2 bytes per element, no scales
-if not ONLY or "f16" in ONLY:
-    SLAB = 1 << 28
+# the rows of the fused calls and the one-call loop (the second f16 block below); the first block is skipped when only those are asked for
+F16_FUSED_ROWS = ("f16_mvm_scale_and_add", "f16_threshold_fast_n8192", "f16_q_iht_iteration", "f16_iht_loop", "f16_gd_loop")
+SLAB = 1 << 28
 
-    def f16_fill(dst, count, seed):
-        """count f16 values = quantized random fp32 integers in [-10, 10], through a 1 GiB fp32 slab"""
-        src = hip.alloc(4 * min(SLAB, count))
-        for o in range(0, count, SLAB):
-            c = min(SLAB, count - o)
-            hip.check(lib.clv_fill_random_ints_f32(src.ptr, c, 10, seed, o, None))
-            hip.check(lib.clv_f16_quantize(src.ptr, c, dst.ptr + 2 * o, None))
-        hip.sync()
 
+def f16_fill(dst, count, seed):
+    """count f16 values = quantized random fp32 integers in [-10, 10], through a 1 GiB fp32 slab"""
+    src = hip.alloc(4 * min(SLAB, count))
+    for o in range(0, count, SLAB):
+        c = min(SLAB, count - o)
+        hip.check(lib.clv_fill_random_ints_f32(src.ptr, c, 10, seed, o, None))
+        hip.check(lib.clv_f16_quantize(src.ptr, c, dst.ptr + 2 * o, None))
+    hip.sync()
+
+
+if not ONLY or any("f16" in o and not o.startswith(F16_FUSED_ROWS) for o in ONLY.split(",")):
     for logn in (24, 30):
         n = 1 << logn
         x = hip.alloc(4 * n)
@@ -295,4 +303,76 @@ if not ONLY or "f16" in ONLY:
         rec(f"f16_mvm_{nf}^2", 2 * vals + 4 * nf, lambda: hip.check(lib.clm_f16_mvm(hA.ptr, nf, nf, hx.ptr, hr16.ptr, None)))
         rec(f"f16_mvm_f32_{nf}^2", 2 * vals + 8 * nf, lambda: hip.check(lib.clm_f16_mvm_f32(hA.ptr, nf, nf, xf.ptr, rf.ptr, None)))
         del hA, hx, hr16, xf, rf
+# ---- the half-precision IHT / GD loop: the fused mvm + scaleAndAdd, the one-workgroup threshold, the loop in one call
+if not ONLY or "f16" in ONLY:
+    def with_env(name, value, fn):
+        """fn with the library switch `name` set (the library reads it per call)"""
+        def run():
+            os.environ[name] = value
+            try:
+                fn()
+            finally:
+                os.environ.pop(name, None)
+        return run
+
+    # the mvm of f16_mvm_{n}^2 with the scaleAndAdd behind it in its epilogue: + u read, t and r written
+    for nf in (8192, 32768):
+        if not selected(f"f16_mvm_scale_and_add_{nf}^2"):
+            continue
+        vals = nf * nf
+        hA, hx, hu, ht, hr16 = hip.alloc(2 * vals), hip.alloc(2 * nf), hip.alloc(2 * nf), hip.alloc(2 * nf), hip.alloc(2 * nf)
+        f16_fill(hA, vals, 63)
+        f16_fill(hx, nf, 64)
+        f16_fill(hu, nf, 66)
+        rec(f"f16_mvm_scale_and_add_{nf}^2", 2 * vals + 8 * nf,
+            lambda: hip.check(lib.clm_f16_mvm_scale_and_add(hA.ptr, nf, nf, hx.ptr, hu.ptr, -1.0, ht.ptr, hr16.ptr, None)))
+        del hA, hx, hu, ht, hr16
+    # FAST threshold at n = 8192: the one-workgroup kernel (one launch) and, with CLV_F16_THRESHOLD_SMALL=0, the large-vector radix select
+    # (nine launches) that every n took before
+    n16 = 8192
+    hv = hip.alloc(2 * n16)
+    f16_fill(hv, n16, 67)
+    thr_note = "bytes = the values read and written once; thresholded in place, so calls after the first find the vector already thresholded"
+    rec("f16_threshold_fast_n8192", 4 * n16, lambda: hip.check(lib.clv_f16_threshold_mode(hv.ptr, n16, n16, n16 // 4, THRESHOLD_FAST, None, None)),
+        extra={"note": "k_f16_thresh_small, one launch; " + thr_note})
+    rec("f16_threshold_fast_n8192_large_path",
+        4 * n16, with_env("CLV_F16_THRESHOLD_SMALL", "0", lambda: hip.check(lib.clv_f16_threshold_mode(hv.ptr, n16, n16, n16 // 4, THRESHOLD_FAST, None, None))),
+        extra={"note": "CLV_F16_THRESHOLD_SMALL=0: the large-vector radix select, nine launches; " + thr_note})
+    del hv
+    # one iteration of Q_IHT<CloverMatrix16, CloverVector16> at N = 8192 (Phi m x n with m = N/2, K = N/4, FAST threshold): the method calls
+    # one by one with the large-vector threshold -- the 13 launches of the generic template before clm_f16_iht -- and the same loop as one
+    # call (three launches per iteration, two for GD).  ms of the loop rows is per iteration: a call of LOOP_ITERS iterations, divided.
+    # mu = 2^-24 as in the m8 rows; the kernels' time does not depend on the data
+    N16 = 8192
+    m16, c16, K16 = N16 // 2, N16, N16 // 4
+    if any(selected(r) for r in (f"f16_q_iht_iteration_N{N16}", f"f16_iht_loop_N{N16}", f"f16_gd_loop_N{N16}")):
+        P, PT = hip.alloc(2 * m16 * c16), hip.alloc(2 * m16 * c16)
+        f16_fill(P, m16 * c16, 68)
+        hip.check(lib.clm_f16_transpose(P.ptr, m16, c16, PT.ptr, None))
+        vx, vt3, vy, vt1, vt2 = hip.alloc(2 * c16), hip.alloc(2 * c16), hip.alloc(2 * m16), hip.alloc(2 * m16), hip.alloc(2 * m16)
+        hip.check(lib.clv_memset(vx.ptr, 0, 2 * c16, None))
+        f16_fill(vy, m16, 69)
+        MU16 = 2.0 ** -24
+        LOOP_ITERS = 10
+
+        def f16_iteration():
+            hip.check(lib.clm_f16_mvm(P.ptr, m16, c16, vx.ptr, vt1.ptr, None))
+            hip.check(lib.clv_f16_scale_and_add(vy.ptr, vt1.ptr, -1.0, m16, vt2.ptr, None))
+            hip.check(lib.clm_f16_mvm(PT.ptr, c16, m16, vt2.ptr, vt3.ptr, None))
+            hip.check(lib.clv_f16_scale_and_add(vx.ptr, vt3.ptr, MU16, c16, vx.ptr, None))
+            hip.check(lib.clv_f16_threshold_mode(vx.ptr, c16, c16, K16, THRESHOLD_FAST, None, None))
+
+        def f16_loop(thr):
+            hip.check(lib.clm_f16_iht(P.ptr, PT.ptr, m16, c16, vx.ptr, c16, vy.ptr, vt1.ptr, vt2.ptr, vt3.ptr, LOOP_ITERS, K16, MU16, thr, None))
+        itb16 = 2 * 2 * m16 * c16
+        rec(f"f16_q_iht_iteration_N{N16}", itb16, with_env("CLV_F16_THRESHOLD_SMALL", "0", f16_iteration), reps=5,
+            extra={"note": "the five method calls one by one, threshold on the large-vector path: 13 launches; bytes = the two matrices only"})
+        for row, thr, note in ((f"f16_iht_loop_N{N16}", 1, "FAST threshold (k_f16_thresh_small): three launches per iteration"),
+                               (f"f16_gd_loop_N{N16}", 0, "no threshold (Q_GD): two launches per iteration")):
+            if not selected(row):
+                continue
+            rec(row, itb16 * LOOP_ITERS, lambda thr=thr: f16_loop(thr), reps=2,
+                extra={"note": f"one clm_f16_iht call of {LOOP_ITERS} iterations, ms per iteration; bytes = the two matrices only; " + note})
+            res[row]["ms"] = round(res[row]["ms"] / LOOP_ITERS, 5)
+        del P, PT, vx, vt3, vy, vt1, vt2
 print(json.dumps(res, indent=1))
