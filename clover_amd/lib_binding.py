@@ -97,6 +97,9 @@ SIGNATURES = {
                            C.c_int, _vp, _vp]),
     "clm8_mvm_f32": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "clm8_transpose": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm8_gemm": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "clm8_gemm_i32": (C.c_int, [_vp, _u64, _u64, _vp, _u64, _u64, _u64, _vp, _vp]),
+    "clm4_gemm_m8": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp]),
     "clv_f16_quantize": (C.c_int, [_vp, _u64, _vp, _vp]),
     "clv_f16_restore": (C.c_int, [_vp, _u64, _vp, _vp]),
     "clv_f16_scale_and_add": (C.c_int, [_vp, _vp, C.c_float, _u64, _vp, _vp]),
@@ -566,4 +569,24 @@ class CloverHip:
         b = [self.to_device(a) for a in (qA, sA, qB, sB)]
         c = self.alloc(max(M * N * 4, 4))
         self.check(self.lib.clm4_gemm(b[0].ptr, b[1].ptr, M, K, b[2].ptr, b[3].ptr, N, c.ptr, None))
+        return c.download(np.float32, M * N).reshape(M, N)
+
+    # -- GEMM with 8-bit operands (int8 matrix cores) ------------------------------------------------
+    def m8_gemm(self, qA, sA, M, K, qB, sB, N) -> np.ndarray:
+        b = [self.to_device(a) for a in (qA, sA, qB, sB)]
+        c = self.alloc(max(M * N * 4, 4))
+        self.check(self.lib.clm8_gemm(b[0].ptr, b[1].ptr, M, K, b[2].ptr, b[3].ptr, N, c.ptr, None))
+        return c.download(np.float32, M * N).reshape(M, N)
+
+    def m8_gemm_i32(self, qA, M, K, qB, N, kb_begin=0, kb_count=None) -> np.ndarray:
+        b = [self.to_device(a) for a in (qA, qB)]
+        c = self.alloc(max(M * N * 4, 4))
+        self.check(self.lib.clm8_gemm_i32(b[0].ptr, M, K, b[1].ptr, N, kb_begin, K // 64 - kb_begin if kb_count is None else kb_count, c.ptr, None))
+        return c.download(np.int32, M * N).reshape(M, N)
+
+    def m4_gemm_m8(self, qA4, sA, M, K, qB8, sB, N) -> np.ndarray:
+        """A: CloverMatrix4 image (packed nibbles), B: CloverMatrix8 image"""
+        b = [self.to_device(a) for a in (qA4, sA, qB8, sB)]
+        c = self.alloc(max(M * N * 4, 4))
+        self.check(self.lib.clm4_gemm_m8(b[0].ptr, b[1].ptr, M, K, b[2].ptr, b[3].ptr, N, c.ptr, None))
         return c.download(np.float32, M * N).reshape(M, N)

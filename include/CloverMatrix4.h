@@ -12,6 +12,7 @@
  *                                       dot(), as there), transpose_scalar (:435-502); in the reference mvm == mvm_parallel ==
  *                                       mvm_scalar bit for bit when rounding is disabled, and so here
  *   gemm (new)                       -> clm4_gemm     (the reference has no GEMM; semantics in DESIGN.md)
+ *   gemm (new, CloverMatrix8 operand)-> clm4_gemm_m8  (the pairing of mvm(CloverVector8): 4-bit matrix x 8-bit matrix)
  *
  * As in the reference, values/scales are not exposed (they are `protected` there, :73-75); the matrix
  * lives in HBM once quantized.  transpose and both mixed-precision mvm variants (4-bit x 8-bit with
@@ -26,6 +27,7 @@
 #include <string>
 
 #include "CloverMatrix32.h"
+#include "CloverMatrix8.h"          /* the 8-bit operand of gemm(); CloverMatrix8.h does not include this header */
 #include "CloverVector4.h"
 #include "CloverVector8.h"
 
@@ -421,6 +423,17 @@ public:
                                                  C.device_wo(), nullptr), "CloverMatrix4::gemm");
         else
             clover_hip::check(clm4_gemm(qa, dev_scales(), rows, cols, qb, B.dev_scales(), B.rows, C.device_wo(), nullptr), "CloverMatrix4::gemm");
+    }
+    /* C = this * B^T with an 8-bit B (N x K): the mixed pairing mvm(const CloverVector8 &, ...) offers for vectors, as a GEMM.  One launch
+     * on the int8 matrix cores straight from the nibbles and the bytes: no FP6 image takes part, cacheGemmOperand() has no bearing on it. */
+    void gemm(const CloverMatrix8 &B, CloverMatrix32 &C) const
+    {
+        if (B.cols != cols || C.getRows() != rows || C.getCols() != B.rows) {
+            std::cout << "GEMM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        clover_hip::check(clm4_gemm_m8(dev_values(), dev_scales(), rows, cols, B.dev_values(), B.dev_scales(), B.rows, C.device_wo(), nullptr),
+                          "CloverMatrix4::gemm");
     }
     /* A matrix that is multiplied many times (weights): keep the FP6 image the GEMM kernel streams between gemm() calls instead
      * of re-coding the nibbles on every call (+3/4 of the matrix's size in HBM; 8192^3: 0.41 -> 0.38 ms per call).  The image

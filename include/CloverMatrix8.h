@@ -17,6 +17,7 @@
  *
  *   mvm_scaleAndAdd                    -> clm8_mvm_scale_and_add  (not in the reference: mvm + the scaleAndAdd behind it, one launch)
  *   iht_loop                           -> clm8_iht        (the whole Q_IHT / Q_GD loop of 01_measure.h:923-946, 999-1021 in one call)
+ *   gemm                               -> clm8_gemm       (not in the reference, which has no GEMM; semantics in DESIGN.md 6)
  *
  * Q_IHT<CloverMatrix8, CloverVector8> and Q_GD<...> are specialised in CloverIHT.h (which includes this header): iht_loop when rounding is
  * deterministic, the mvm_scaleAndAdd pairs otherwise; every step is a kernel on the device mirrors, nothing is copied back between steps.
@@ -33,7 +34,10 @@
 #include "CloverVector32.h"
 #include "CloverVector8.h"
 
+class CloverMatrix4;
+
 class CloverMatrix8 {
+    friend class CloverMatrix4;                /* CloverMatrix4::gemm(const CloverMatrix8 &, ...) reads the device image */
 protected:
     const uint64_t rows;
     const uint64_t cols;
@@ -285,6 +289,18 @@ public:
                                          reinterpret_cast<float *>(d + other.value_bytes), nullptr), "CloverMatrix8::transpose");
     }
     void transpose_parallel(CloverMatrix8 &other) const { transpose(other); }
+
+    /* C = this * B^T, fp32: this is M x K, B is N x K, C is M x N (build-defined like CloverMatrix4::gemm).  One launch
+     * on the int8 matrix cores, nothing is re-coded and no scratch is used. */
+    void gemm(const CloverMatrix8 &B, CloverMatrix32 &C) const
+    {
+        if (B.cols != cols || C.getRows() != rows || C.getCols() != B.rows) {
+            std::cout << "GEMM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        clover_hip::check(clm8_gemm(dev_values(), dev_scales(), rows, cols, B.dev_values(), B.dev_scales(), B.rows, C.device_wo(), nullptr),
+                          "CloverMatrix8::gemm");
+    }
     void transpose_scalar(CloverMatrix8 &other) const
     {
         check_transpose(other);

@@ -331,6 +331,26 @@ int  clm8_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols
 /* CloverMatrix8::transpose / transpose_parallel (CloverMatrix8.h:1312-1386): qt(j,i) = q(i,j), the tile scale grid transposed.
  * q is rows x cols, qt is cols x rows; not in place.  Exact. */
 int  clm8_transpose(const int8_t *q, const float *s, uint64_t rows, uint64_t cols, int8_t *qt, float *st, void *stream);
+/* GEMM with 8-bit operands, build-defined like clm4_gemm (the reference has none): A is M x K, B is N x K (both CloverMatrix8
+ * images), C = A * B^T as fp32 M x N row-major; M, N and K are non-zero multiples of 128.  Per element (i, j) and K-block b (64 elements):
+ * S_b = the exact integer sum of the 64 byte products, and C[i][j] is ONE sequential chain over b = 0, 1, 2, ... from C = 0:
+ *     C = fmaf(c_b, (float)S_b, C),    c_b = f32( f32(sA[i>>6][b] * R127) * f32(sB[j>>6][b] * R127) ),    R127 = 1.0f / 127.0f
+ * -- the block factor of clm8_mvm.  (float)S_b is exact for every byte pattern, -128 included: |S_b| <= 64 * 128^2 = 2^20.  The kernel
+ * feeds the bytes to the int8 matrix cores as they are: no scratch, no workspace, no rng -- legal inside a stream capture.  A, B and C
+ * are 16-byte aligned. */
+int  clm8_gemm(const int8_t *A, const float *sA, uint64_t M, uint64_t K,
+               const int8_t *B, const float *sB, uint64_t N, float *C, void *stream);
+/* The exact integer part of clm8_gemm: S[i][j] = sum of S_b over the K-blocks [kb_begin, kb_begin + kb_count), int32, row-major M x N.  The
+ * whole range is the unscaled int8 x int8 -> int32 GEMM, a range of one K-block the sum the fp32 result folds.  The range is non-empty,
+ * lies inside [0, K/64] and holds at most 2047 K-blocks: 2047 * 64 * 2^14 < 2^31, so no byte pattern overflows; anything else is
+ * CLV_ERR_INVALID.  Any begin and any count run on the matrix cores (a range of odd length pads its last stage with zeros). */
+int  clm8_gemm_i32(const int8_t *A, uint64_t M, uint64_t K, const int8_t *B, uint64_t N, uint64_t kb_begin, uint64_t kb_count,
+                   int32_t *S, void *stream);
+/* The mixed pairing the mvm family has as clm4_mvm_v8: A4 is a CloverMatrix4 image (M x K nibbles, values -8 .. 7), B8 a CloverMatrix8
+ * image (N x K bytes).  As clm8_gemm with c_b = f32( f32(sA[i>>6][b] * (1.0f / 7.0f)) * f32(sB[j>>6][b] * R127) ), the factor of
+ * clm4_mvm_v8 (CloverMatrix4.h:1147-1149); |S_b| <= 64 * 8 * 128 = 2^16. */
+int  clm4_gemm_m8(const int8_t *A4, const float *sA, uint64_t M, uint64_t K,
+                  const int8_t *B8, const float *sB, uint64_t N, float *C, void *stream);
 /* ---- CloverVector16 / CloverMatrix16: the half-precision containers ----------------------------- */
 /* Storage (CloverVector16.h:35-66, CloverMatrix16.h:36-66): raw IEEE binary16 bit patterns in uint16_t, no scales.  Vector: n_pad values
  * (multiple of 128, the padding zero); matrix: rows x cols values row-major.  Every pointer is 16-byte aligned.

@@ -5,7 +5,11 @@ Algorithmic bytes per element follow SURVEY 8(d): quantize/restore 4.5625, dot 1
 threshold 1.125 (nibbles + scales read and written once each), transpose 2 x (1/2 + 4/4096), matrix quantize 4.5625;
 CloverMatrix8 (m8_*): quantize 4 + 1 + 4/4096, transpose 2 x (1 + 4/4096), mvm 1 + 4/4096 per matrix element;
 CloverVector16 / CloverMatrix16 (f16_*): 2 bytes per element and no scales -- quantize / restore 4 + 2, scaleAndAdd 2 + 2 + 2, dot 2 + 2,
-threshold 2 + 2 (read once, written once), matrix quantize 4 + 2, transpose 2 + 2, mvm 2 per matrix element + x + r."""
+threshold 2 + 2 (read once, written once), matrix quantize 4 + 2, transpose 2 + 2, mvm 2 per matrix element + x + r.
+
+The GEMM rows with 8-bit operands (m8_gemm_*, m4_gemm_m8_*, and their yardstick m4_gemm_i8_*: clm4_gemm on the int8-MFMA kernel of gemm4.hip)
+are compute rows: ms, TOP/s = 2 M N K / time, and the fraction of the 5 POP/s dense int8 matrix peak (half the FP6 peak DESIGN.md 6 quotes).
+They run first, and a run that asks for nothing else (KB_ONLY naming only GEMM rows) ends after them."""
 import ctypes as C
 import json
 import os
@@ -57,6 +61,61 @@ def rec(name, nbytes, fn, extra=None, reps=10):
     res[name] = {"ms": round(ms, 5), "GB/s": round(nbytes / ms / 1e6, 1), "frac_of_8TBs": round(nbytes / ms / 1e6 / 8000.0, 4)}
     if extra:
         res[name].update(extra)
+
+
+# ---- GEMM with 8-bit operands on the int8 matrix cores (gemm8.hip): compute rows
+INT8_PEAK_OPS = 5.0e15
+GEMM_ROWS = ("m8_gemm_4096^3", "m8_gemm_8192^3", "m4_gemm_m8_8192^3", "m4_gemm_i8_8192^3")
+
+
+def rec_gemm(name, G, fn):
+    ms = timeit(fn, reps=50)
+    ops = 2.0 * G ** 3
+    res[name] = {"ms": round(ms, 5), "TOP/s": round(ops / ms / 1e9, 1), "frac_of_int8_peak": round(ops / (ms * 1e-3) / INT8_PEAK_OPS, 4)}
+
+
+def gemm_operands(G, nibbles):
+    """(values, tile scales) of a G x G operand: random bytes (nibbles in [-7, 7], so no byte is -128) and random scales"""
+    q, s = hip.alloc(G * G // 2 if nibbles else G * G), hip.alloc(4 * (G // 64) ** 2)
+    hip.check(lib.clv_fill_random_nibbles(q.ptr, q.nbytes, 71 + nibbles, 0, None))
+    hip.check(lib.clv_fill_random_scales(s.ptr, (G // 64) ** 2, 73, 0, None))
+    return q, s
+
+
+def yardstick_i8():
+    """clm4_gemm under CLV_GEMM_KERNEL=i8: the library reads that switch once per process, so the row runs in a child process of its own"""
+    import subprocess
+    env = dict(os.environ, CLV_GEMM_KERNEL="i8", KB_ONLY="m4_gemm_i8_8192^3", KB_GEMM_CHILD="1")
+    out = subprocess.run([sys.executable, str(Path(__file__).resolve())], env=env, check=True, capture_output=True, text=True, timeout=600).stdout
+    return json.loads(out)["m4_gemm_i8_8192^3"]
+
+
+if any(selected(r) for r in GEMM_ROWS):
+    if os.environ.get("KB_GEMM_CHILD"):
+        G = 8192
+        (a4, sa4), (b4, sb4), c = gemm_operands(G, True), gemm_operands(G, True), hip.alloc(4 * G * G)
+        rec_gemm("m4_gemm_i8_8192^3", G, lambda: hip.check(lib.clm4_gemm(a4.ptr, sa4.ptr, G, G, b4.ptr, sb4.ptr, G, c.ptr, None)))
+        print(json.dumps(res))
+        sys.exit(0)
+    # the yardstick before and after the new rows: the same box, the same minutes
+    runs = [yardstick_i8()] if selected("m4_gemm_i8_8192^3") else []
+    for G in (4096, 8192):
+        (a8, sa8), (b8, sb8), c = gemm_operands(G, False), gemm_operands(G, False), hip.alloc(4 * G * G)
+        if selected(f"m8_gemm_{G}^3"):
+            rec_gemm(f"m8_gemm_{G}^3", G, lambda: hip.check(lib.clm8_gemm(a8.ptr, sa8.ptr, G, G, b8.ptr, sb8.ptr, G, c.ptr, None)))
+        if G == 8192 and selected("m4_gemm_m8_8192^3"):
+            a4, sa4 = gemm_operands(G, True)
+            rec_gemm("m4_gemm_m8_8192^3", G, lambda: hip.check(lib.clm4_gemm_m8(a4.ptr, sa4.ptr, G, G, b8.ptr, sb8.ptr, G, c.ptr, None)))
+            del a4, sa4
+        del a8, sa8, b8, sb8, c
+    if runs:
+        runs.append(yardstick_i8())
+        res["m4_gemm_i8_8192^3"] = dict(min(runs, key=lambda r: r["ms"]), ms_before_and_after=[r["ms"] for r in runs],
+                                        note="clm4_gemm under CLV_GEMM_KERNEL=i8 (k_m4_gemm_mfma), in a child process before and after the rows "
+                                             "above; the faster of the two runs")
+    if ONLY and all(any(o in r for r in GEMM_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
 
 
 # ---- vector ops at n = 2^30 (4 GiB fp32 source, 512 MiB + 64 MiB quantized) and n = 2^24
