@@ -3,6 +3,7 @@
 // One of the callers either side of the hot path.  With mvm these are the five steps of the reference's quantized IHT / GD
 // iterations (test/performance/01_measure.h:923-946, 999-1021), so x, t1..t3 can stay in HBM across iterations.
 #include "common.h"
+#include "clover_hip_fp32.h"
 #include "thresh_device.h"
 
 #include <type_traits>
@@ -55,6 +56,17 @@ struct ThreshElems {
         const float q = (float)((int)(w << (24 - 8 * e)) >> 24);
         return __float_as_uint(__builtin_fabsf(div127(q * sc)));
     }
+};
+
+// BITS = 32: CloverVector32, one raw fp32 value per word, no scales, |value| = the value with its sign bit cleared.  Specialised beside
+// the packed widths: a word is its one element, so there is no shift to form a mask from.
+template <>
+struct ThreshElems<32> {
+    static constexpr int EPW = 1;
+    static constexpr int WPB = 64;
+    __device__ static __forceinline__ uint32_t mask(int) { return 0xFFFFFFFFu; }
+    __device__ static __forceinline__ float scale(const float *__restrict__, uint64_t) { return 0.0f; }
+    __device__ static __forceinline__ uint32_t key(uint32_t w, int, float) { return w & 0x7FFFFFFFu; }
 };
 
 // level 0: bins = key >> 20 (4096); level 1: key>>20 == prefix, bins = (key >> 8) & 0xFFF; level 2:
@@ -658,6 +670,84 @@ __global__ __launch_bounds__(TS_THREADS) void k_f16_thresh_small(uint32_t *__res
             }
             q[i] = outw;
         }
+    }
+}
+
+// ---- single-workgroup path for CloverVector32 (n_pad <= TS_THREADS * TS_MAXW = 16384): k_f16_thresh_small with one element per word.  The
+// key ThreshElems<32>::key = bits & 0x7FFFFFFF uses all 31 bits (no dense re-coding as for binary16), so the select runs in four 8-bit
+// levels over it, as k_thresh8_small's; the same order, the same selected set and the same tie rule as threshold_large<32>: bit-identical.
+template <int W>
+__global__ __launch_bounds__(TS_THREADS) void k_f32_thresh_small(uint32_t *__restrict__ q, uint32_t n, uint32_t k)
+{
+    typedef ThreshElems<32> E;
+    __shared__ __attribute__((aligned(16))) uint32_t hist[4 * TSF_COPIES * TSF_CS];
+    __shared__ uint32_t wtot[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t w0 = tid * W;
+    uint32_t w[W];
+    uint32_t valid = 0;                                                  // bit j: word j exists (index < n)
+#pragma unroll
+    for (int j = 0; j < W; j++) {
+        w[j] = q[w0 + j < n ? w0 + j : 0];
+        if (w0 + j < n) valid |= 1u << j;
+    }
+    for (int i = tid; i < 4 * TSF_COPIES * TSF_CS; i += TS_THREADS) hist[i] = 0;
+    __syncthreads();                                                     // bins zero before anybody adds to them
+
+    uint32_t tau = 0x7F800000u, keep = 0;                                // k = 0: nothing finite survives, as the large-vector path's state
+    if (k != 0) {
+        uint32_t prefix = 0, need = k;
+#pragma unroll
+        for (int level = 0; level < 4; level++) {
+            const int shift = 24 - 8 * level;
+            uint32_t *h = hist + TSF_COPIES * TSF_CS * level, *hc = h + TSF_CS * (lane & (TSF_COPIES - 1));
+#pragma unroll
+            for (int j = 0; j < W; j++)
+                if ((valid >> j) & 1u) {
+                    const uint32_t key = E::key(w[j], 0, 0.0f);
+                    if (level == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hc[(key >> shift) & 0xFFu], 1u);
+                }
+            __syncthreads();
+            // every wave selects for itself: lane l owns bins 255 - 4 l ... 252 - 4 l (from the top), added up over the copies
+            uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+#pragma unroll
+            for (int cpy = 0; cpy < TSF_COPIES; cpy++) {
+                const u32x4 h4 = *reinterpret_cast<const u32x4 *>(h + TSF_CS * cpy + 252 - 4 * lane);
+                t0 += h4.w; t1 += h4.z; t2 += h4.y; t3 += h4.x;
+            }
+            const uint32_t sum = t0 + t1 + t2 + t3;
+            const uint32_t incl = wave_scan_incl(sum);
+            const unsigned long long hit = __ballot(incl >= need && incl - sum < need);
+            const int L = __builtin_ctzll(hit);                          // exactly one lane: the level's total is >= need (k < n)
+            uint32_t above = __shfl(incl - sum, L);
+            const uint32_t T0 = __shfl(t0, L), T1 = __shfl(t1, L), T2 = __shfl(t2, L);
+            uint32_t pick = 0;
+            if (above + T0 < need) { above += T0; pick = 1;
+                if (above + T1 < need) { above += T1; pick = 2;
+                    if (above + T2 < need) { above += T2; pick = 3; } } }
+            prefix = (prefix << 8) | (255u - 4u * (uint32_t)L - pick);
+            need -= above;
+        }
+        tau = prefix;
+        keep = need;
+    }
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < W; j++) c += ((valid >> j) & 1u) && E::key(w[j], 0, 0.0f) == tau;
+    // ties in index order: the first `keep` of them survive (one barrier: the 16 wave totals)
+    const uint32_t vinc = wave_scan_incl(c);
+    if (lane == 63) wtot[wave] = vinc;
+    __syncthreads();
+    const uint32_t tot = lane < 16 ? wtot[lane] : 0;
+    const uint32_t inc = wave_scan_incl(tot);
+    uint32_t rank = vinc - c + __shfl(inc - tot, wave);
+#pragma unroll
+    for (int j = 0; j < W; j++) {
+        if (!((valid >> j) & 1u)) continue;                              // padding is left alone
+        const uint32_t key = E::key(w[j], 0, 0.0f);
+        bool kept = key > tau;
+        if (key == tau) { kept = rank < keep; rank++; }
+        if (!kept) q[w0 + j] = 0u;
     }
 }
 
@@ -1939,4 +2029,43 @@ extern "C" int clv_f16_threshold_heap(uint16_t *h, uint64_t n, uint64_t n_pad, u
     CLV_REQUIRE(k >= 1 && k <= n, "clv_f16_threshold_heap: k=%llu must lie in 1 .. n=%llu", (unsigned long long)k, (unsigned long long)n);
     CLV_REQUIRE_WORKSPACE("clv_f16_threshold_heap", workspace);
     return threshold_reference<16>((uint32_t *)h, nullptr, n, n_pad, k, workspace, as_stream(stream), (uint2 *)heap_dev);
+}
+
+// CloverVector32::threshold(K) (CloverVector32.h:549-600): the same selection on |x|, one element per word and no scales.  FAST:
+// k_f32_thresh_small up to n_pad = TS_THREADS * TS_MAXW = 16384 (one launch, no workspace), the large-vector path beyond -- and at every n
+// with CLV_F32_THRESHOLD_SMALL=0 (read per call: A/B runs flip it); the two give the same bits.  NaN patterns have keys above infinity's:
+// FAST keeps them first (include/clover_hip_fp32.h).
+extern "C" uint64_t clv_f32_threshold_workspace_bytes(uint64_t n_pad)
+{
+    const uint64_t blocks = (n_pad + TH_WORDS_PER_BLOCK - 1) / TH_WORDS_PER_BLOCK;
+    return 4096 * sizeof(uint32_t) + 256 + blocks * sizeof(uint32_t) + 256;
+}
+
+extern "C" int clv_f32_threshold_mode(float *x, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream)
+{
+    CLV_REQUIRE(mode == CLV_THRESHOLD_FAST || mode == CLV_THRESHOLD_REFERENCE, "clv_f32_threshold_mode: unknown mode %d", mode);
+    CLV_REQUIRE(x, "clv_f32_threshold_mode: null pointer");
+    CLV_REQUIRE(((uintptr_t)x & 15u) == 0, "clv_f32_threshold_mode: x must be 16-byte aligned");
+    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv_f32_threshold_mode: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
+    CLV_REQUIRE(n < (1ull << 32), "clv_f32_threshold_mode: vectors of 2^32 or more elements are not supported");
+    CLV_REQUIRE_WORKSPACE("clv_f32_threshold_mode", workspace);
+    if (k >= n || n == 0) return CLV_OK;
+    if (mode == CLV_THRESHOLD_REFERENCE) return threshold_reference<32>((uint32_t *)x, nullptr, n, n_pad, k, workspace, as_stream(stream));
+    if (n_pad <= (uint64_t)TS_THREADS * TS_MAXW && clv_env_int("CLV_F32_THRESHOLD_SMALL", 1)) {
+        const uint64_t w = (n + TS_THREADS - 1) / TS_THREADS;
+#define T32_LAUNCH(W) hipLaunchKernelGGL(k_f32_thresh_small<W>, dim3(1), dim3(TS_THREADS), 0, as_stream(stream), (uint32_t *)x, (uint32_t)n, (uint32_t)k)
+        if (w <= 1) T32_LAUNCH(1);
+        else if (w <= 2) T32_LAUNCH(2);
+        else if (w <= 4) T32_LAUNCH(4);
+        else if (w <= 8) T32_LAUNCH(8);
+        else T32_LAUNCH(16);
+#undef T32_LAUNCH
+        CLV_LAUNCH_CHECK();
+        return CLV_OK;
+    }
+    if (!workspace) {
+        int rc = clv_internal_workspace(&workspace, clv_f32_threshold_workspace_bytes(n_pad), as_stream(stream));
+        if (rc) return rc;
+    }
+    return threshold_large<32>((uint32_t *)x, nullptr, n, k, workspace, as_stream(stream));
 }

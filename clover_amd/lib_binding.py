@@ -143,6 +143,19 @@ SIGNATURES = {
     "clv_fill_random_ints_f32": (C.c_int, [_vp, _u64, C.c_int, _u64, _u64, _vp]),
 }
 
+# name -> (restype, argtypes); everything include/clover_hip_fp32.h declares (CloverVector32 / CloverMatrix32 on the device)
+SIGNATURES_FP32 = {
+    "clv_f32_scale_and_add": (C.c_int, [_vp, _vp, C.c_float, _u64, _vp, _vp]),
+    "clv_f32_dot_workspace_bytes": (_u64, [_u64]),
+    "clv_f32_dot": (C.c_int, [_vp, _vp, _u64, C.c_int, _vp, _vp, _vp]),
+    "clv_f32_threshold_workspace_bytes": (_u64, [_u64]),
+    "clv_f32_threshold_mode": (C.c_int, [_vp, _u64, _u64, _u64, C.c_int, _vp, _vp]),
+    "clm_f32_mvm": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm_f32_mvm_scale_and_add": (C.c_int, [_vp, _u64, _u64, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "clm_f32_transpose": (C.c_int, [_vp, _u64, _u64, _vp, _vp]),
+    "clm_f32_iht": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
+}
+
 
 class CloverHipError(RuntimeError):
     pass
@@ -157,7 +170,7 @@ def load_library(path: str | Path | None = None, allow_probe: bool = False) -> C
             f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = C.CDLL(str(p))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -524,6 +537,59 @@ class CloverHip:
         dh, dt = self.to_device(h), self.alloc(max(2 * rows * cols, 2))
         self.check(self.lib.clm_f16_transpose(dh.ptr, rows, cols, dt.ptr, None))
         return dt.download(np.uint16, rows * cols)
+
+    # -- CloverVector32 / CloverMatrix32 (plain fp32; every operand a numpy array or a DevBuf, so that a matrix is uploaded once) ----
+    def _f32_dev(self, a) -> DevBuf:
+        return a if isinstance(a, DevBuf) else self.to_device(np.ascontiguousarray(a, dtype=np.float32))
+
+    def f32_scale_and_add(self, u, v, a: float, n_pad: int | None = None, in_place: bool = False) -> np.ndarray:
+        du, dv = self._f32_dev(u), self._f32_dev(v)
+        n = du.nbytes // 4 if n_pad is None else n_pad
+        dr = du if in_place else self.alloc(max(4 * n, 4))
+        self.check(self.lib.clv_f32_scale_and_add(du.ptr, dv.ptr, a, n, dr.ptr, None))
+        return dr.download(np.float32, n)
+
+    def f32_dot(self, u, v, mode: int = DOT_EXACT, n_pad: int | None = None) -> np.float32:
+        du, dv, out = self._f32_dev(u), self._f32_dev(v), self.alloc(4)
+        self.check(self.lib.clv_f32_dot(du.ptr, dv.ptr, du.nbytes // 4 if n_pad is None else n_pad, mode, out.ptr, None, None))
+        return out.download(np.float32, 1)[0]
+
+    def f32_threshold(self, x, n: int, k: int, mode: int = THRESHOLD_FAST, n_pad: int | None = None) -> np.ndarray:
+        """thresholds in place: a DevBuf given as x holds the result afterwards"""
+        dx = self._f32_dev(x)
+        n_pad = dx.nbytes // 4 if n_pad is None else n_pad
+        self.check(self.lib.clv_f32_threshold_mode(dx.ptr, n, n_pad, k, mode, None, None))
+        return dx.download(np.float32, n_pad)
+
+    def f32_mvm(self, A, rows, cols, x) -> np.ndarray:
+        dA, dx, dr = self._f32_dev(A), self._f32_dev(x), self.alloc(max(4 * rows, 4))
+        self.check(self.lib.clm_f32_mvm(dA.ptr, rows, cols, dx.ptr, dr.ptr, None))
+        return dr.download(np.float32, rows)
+
+    def f32_mvm_scale_and_add(self, A, rows, cols, x, u, a: float, in_place: bool = False, want_t: bool = True):
+        """(t, r2) of clm_f32_mvm_scale_and_add; t is None when want_t is False"""
+        dA, dx, du = self._f32_dev(A), self._f32_dev(x), self._f32_dev(u)
+        dt = self.alloc(max(4 * rows, 4)) if want_t else None
+        dr = du if in_place else self.alloc(max(4 * rows, 4))
+        self.check(self.lib.clm_f32_mvm_scale_and_add(dA.ptr, rows, cols, dx.ptr, du.ptr, a, dt.ptr if dt else None, dr.ptr, None))
+        return (dt.download(np.float32, rows) if want_t else None), dr.download(np.float32, rows)
+
+    def f32_transpose(self, A, rows, cols) -> np.ndarray:
+        dA, dt = self._f32_dev(A), self.alloc(max(4 * rows * cols, 4))
+        self.check(self.lib.clm_f32_transpose(dA.ptr, rows, cols, dt.ptr, None))
+        return dt.download(np.float32, rows * cols)
+
+    def f32_iht(self, Phi, PhiT, m, n, y, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None, prefill: int = 0x55):
+        """clm_f32_iht on buffers prefilled with `prefill` bytes: {"x": fp32[n], "t1": fp32[m], "t2": fp32[m], "t3": fp32[n]}"""
+        b = [self._f32_dev(v) for v in (Phi, PhiT, y)]
+        lens = {"x": n, "t1": m, "t2": m, "t3": n}
+        v = {}
+        for name, ln in lens.items():
+            v[name] = self.alloc(4 * ln)
+            self.check(self.lib.clv_memset(v[name].ptr, prefill, v[name].nbytes, None))
+        self.check(self.lib.clm_f32_iht(b[0].ptr, b[1].ptr, m, n, v["x"].ptr, n if x_len is None else x_len, b[2].ptr, v["t1"].ptr, v["t2"].ptr,
+                                        v["t3"].ptr, iterations, K, mu, threshold, None))
+        return {name: v[name].download(np.float32, ln) for name, ln in lens.items()}
 
     def m4_gemm_i32(self, qA, M, K, qB, N, kb_begin=0, kb_count=None) -> np.ndarray:
         b = [self.to_device(a) for a in (qA, qB)]

@@ -166,4 +166,22 @@ inline void Q_GD<CloverMatrix16, CloverVector16>(CloverMatrix16 &Phi, CloverMatr
     Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, 0, mu, false);
 }
 
+#ifdef CLOVER_FP32_ON_DEVICE
+/* CloverMatrix32 with CloverVector32 vectors under -DCLOVER_FP32_ON_DEVICE: the fp32 baseline of every table of the reference, on the
+ * device.  The whole loop in one call (CloverMatrix32::iht_loop -> clm_f32_iht): three launches per iteration, two for Q_GD, the bits of
+ * the generic templates' five method calls.  Without the switch the generic templates run the host methods, as before. */
+template <>
+inline void Q_IHT<CloverMatrix32, CloverVector32>(CloverMatrix32 &Phi, CloverMatrix32 &PhiT, CloverVector32 &x, CloverVector32 &y, CloverVector32 &t1,
+                                                  CloverVector32 &t2, CloverVector32 &t3, const uint64_t iterations, const uint64_t K, const float mu)
+{
+    Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, K, mu, true);
+}
+template <>
+inline void Q_GD<CloverMatrix32, CloverVector32>(CloverMatrix32 &Phi, CloverMatrix32 &PhiT, CloverVector32 &x, CloverVector32 &y, CloverVector32 &t1,
+                                                 CloverVector32 &t2, CloverVector32 &t3, const uint64_t iterations, const float mu)
+{
+    Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, 0, mu, false);
+}
+#endif
+
 #endif

@@ -4,8 +4,10 @@
  * every 4-bit result with the 32-bit one, its experiments run Q_IHT / Q_GD on <CloverMatrix32, CloverVector32> as the baseline --
  * compiles and runs unchanged against these headers.
  *
- * This is NOT the hot path and nothing here runs on the GPU: the 32-bit classes are the callers' data format on either side of
- * the 4-bit path, their arithmetic is the comparison baseline.  Plain loops, written from the definitions:
+ * This is NOT the hot path and nothing in this file runs on the GPU: the 32-bit classes are the callers' data format on either side of
+ * the 4-bit path, their arithmetic is the comparison baseline.  These functions are also the DEFINITION of what the device
+ * path of the fp32 classes computes (clover_hip_fp32.h, clover_amd/csrc/fp32.hip; the headers take it under -DCLOVER_FP32_ON_DEVICE): it
+ * equals them bit for bit.  Plain loops, written from the definitions:
  *
  *   dot          32 sequential fma chains (chain = element index mod 32), then (a1 + a2) + (a3 + a4) per lane and the tree of
  *                CloverBase.h:149-157 -- the order of the reference's AVX2 dot (CloverVector32.h:406-451), so the float is the same;

@@ -5,7 +5,9 @@ Algorithmic bytes per element follow SURVEY 8(d): quantize/restore 4.5625, dot 1
 threshold 1.125 (nibbles + scales read and written once each), transpose 2 x (1/2 + 4/4096), matrix quantize 4.5625;
 CloverMatrix8 (m8_*): quantize 4 + 1 + 4/4096, transpose 2 x (1 + 4/4096), mvm 1 + 4/4096 per matrix element;
 CloverVector16 / CloverMatrix16 (f16_*): 2 bytes per element and no scales -- quantize / restore 4 + 2, scaleAndAdd 2 + 2 + 2, dot 2 + 2,
-threshold 2 + 2 (read once, written once), matrix quantize 4 + 2, transpose 2 + 2, mvm 2 per matrix element + x + r.
+threshold 2 + 2 (read once, written once), matrix quantize 4 + 2, transpose 2 + 2, mvm 2 per matrix element + x + r;
+CloverVector32 / CloverMatrix32 (f32_*): 4 bytes per element -- scaleAndAdd 4 + 4 + 4, dot 4 + 4, threshold 4 + 4, transpose 4 + 4, mvm 4 per
+matrix element + x + r (+ u, t, r2 for the fused form).
 
 The GEMM rows with 8-bit operands (m8_gemm_*, m4_gemm_m8_*, and their yardstick m4_gemm_i8_*: clm4_gemm on the int8-MFMA kernel of gemm4.hip)
 are compute rows: ms, TOP/s = 2 M N K / time, and the fraction of the 5 POP/s dense int8 matrix peak (half the FP6 peak DESIGN.md 6 quotes).
@@ -433,5 +435,96 @@ if not ONLY or "f16" in ONLY:
             rec(row, itb16 * LOOP_ITERS, lambda thr=thr: f16_loop(thr), reps=2,
                 extra={"note": f"one clm_f16_iht call of {LOOP_ITERS} iterations, ms per iteration; bytes = the two matrices only; " + note})
             res[row]["ms"] = round(res[row]["ms"] / LOOP_ITERS, 5)
+        del P, PT, vx, vt3, vy, vt1, vt2
+
+# ---- CloverVector32 / CloverMatrix32 on the device (fp32.hip): the rows of the f16 blocks above at 4 bytes per element
+if not ONLY or "f32" in ONLY:
+    def f32_with_env(name, value, fn):
+        """fn with the library switch `name` set (the library reads it per call)"""
+        def run():
+            os.environ[name] = value
+            try:
+                fn()
+            finally:
+                os.environ.pop(name, None)
+        return run
+
+    for logn in (24, 30):
+        if not any(selected(f"f32_{r}_n2^{logn}") for r in ("scale_and_add", "dot_fast", "dot_exact", "threshold_fast_k25pct")):
+            continue
+        n = 1 << logn
+        fu, fv, fr, out = hip.alloc(4 * n), hip.alloc(4 * n), hip.alloc(4 * n), hip.alloc(8)
+        hip.check(lib.clv_fill_random_ints_f32(fu.ptr, n, 10, 81, 0, None))
+        hip.check(lib.clv_fill_random_ints_f32(fv.ptr, n, 10, 82, 0, None))
+        rec(f"f32_scale_and_add_n2^{logn}", 12 * n, lambda: hip.check(lib.clv_f32_scale_and_add(fu.ptr, fv.ptr, 0.5, n, fr.ptr, None)))
+        rec(f"f32_dot_fast_n2^{logn}", 8 * n, lambda: hip.check(lib.clv_f32_dot(fu.ptr, fv.ptr, n, DOT_FAST, out.ptr, None, None)))
+        rec(f"f32_dot_exact_n2^{logn}", 8 * n, lambda: hip.check(lib.clv_f32_dot(fu.ptr, fv.ptr, n, DOT_EXACT, out.ptr, None, None)), reps=1,
+            extra={"note": "32 sequential fma chains of n / 32 steps: latency-bound by definition"})
+        rec(f"f32_threshold_fast_k25pct_n2^{logn}", 8 * n, lambda: hip.check(lib.clv_f32_threshold_mode(fr.ptr, n, n, n // 4, THRESHOLD_FAST, None, None)),
+            reps=3, extra={"note": "the large-vector radix select (nine launches, four passes over the values); bytes = the values read and "
+                                   "written once; thresholded in place, so calls after the first find the vector already thresholded"})
+        del fu, fv, fr
+    for nf in (8192, 32768, 65536):
+        if not any(selected(f"f32_{r}_{nf}^2") for r in ("transpose", "mvm", "mvm_scale_and_add")):
+            continue
+        vals = nf * nf
+        fA = hip.alloc(4 * vals)
+        hip.check(lib.clv_fill_random_ints_f32(fA.ptr, vals, 10, 83, 0, None))
+        if selected(f"f32_transpose_{nf}^2"):
+            fT = hip.alloc(4 * vals)
+            rec(f"f32_transpose_{nf}^2", 8 * vals, lambda: hip.check(lib.clm_f32_transpose(fA.ptr, nf, nf, fT.ptr, None)), reps=3)
+            del fT
+        fx, fu, ft, fr = hip.alloc(4 * nf), hip.alloc(4 * nf), hip.alloc(4 * nf), hip.alloc(4 * nf)
+        hip.check(lib.clv_fill_random_ints_f32(fx.ptr, nf, 10, 84, 0, None))
+        hip.check(lib.clv_fill_random_ints_f32(fu.ptr, nf, 10, 85, 0, None))
+        rec(f"f32_mvm_{nf}^2", 4 * vals + 8 * nf, lambda: hip.check(lib.clm_f32_mvm(fA.ptr, nf, nf, fx.ptr, fr.ptr, None)))
+        rec(f"f32_mvm_scale_and_add_{nf}^2", 4 * vals + 16 * nf,
+            lambda: hip.check(lib.clm_f32_mvm_scale_and_add(fA.ptr, nf, nf, fx.ptr, fu.ptr, -1.0, ft.ptr, fr.ptr, None)))
+        del fA, fx, fu, ft, fr
+    # FAST threshold at n = 8192: the one-workgroup kernel (one launch) and, with CLV_F32_THRESHOLD_SMALL=0, the large-vector radix select
+    n32 = 8192
+    fv = hip.alloc(4 * n32)
+    hip.check(lib.clv_fill_random_ints_f32(fv.ptr, n32, 10, 86, 0, None))
+    thr_note32 = "bytes = the values read and written once; thresholded in place, so calls after the first find the vector already thresholded"
+    rec("f32_threshold_fast_n8192", 8 * n32, lambda: hip.check(lib.clv_f32_threshold_mode(fv.ptr, n32, n32, n32 // 4, THRESHOLD_FAST, None, None)),
+        extra={"note": "k_f32_thresh_small, one launch; " + thr_note32})
+    rec("f32_threshold_fast_n8192_large_path", 8 * n32,
+        f32_with_env("CLV_F32_THRESHOLD_SMALL", "0", lambda: hip.check(lib.clv_f32_threshold_mode(fv.ptr, n32, n32, n32 // 4, THRESHOLD_FAST, None, None))),
+        extra={"note": "CLV_F32_THRESHOLD_SMALL=0: the large-vector radix select, nine launches; " + thr_note32})
+    del fv
+    # one iteration of Q_IHT<CloverMatrix32, CloverVector32> at N = 8192 (Phi m x n with m = N/2, K = N/4, FAST threshold): the five method
+    # calls one by one with the threshold on the large-vector path, and the same loop as one clm_f32_iht call (three launches per
+    # iteration, two for GD).  ms of the loop rows is per iteration.  mu = 2^-24 as in the other widths' rows
+    N32 = 8192
+    m32, c32, K32 = N32 // 2, N32, N32 // 4
+    if any(selected(r) for r in (f"f32_q_iht_iteration_N{N32}", f"f32_iht_loop_N{N32}", f"f32_gd_loop_N{N32}")):
+        P, PT = hip.alloc(4 * m32 * c32), hip.alloc(4 * m32 * c32)
+        hip.check(lib.clv_fill_random_ints_f32(P.ptr, m32 * c32, 10, 87, 0, None))
+        hip.check(lib.clm_f32_transpose(P.ptr, m32, c32, PT.ptr, None))
+        vx, vt3, vy, vt1, vt2 = hip.alloc(4 * c32), hip.alloc(4 * c32), hip.alloc(4 * m32), hip.alloc(4 * m32), hip.alloc(4 * m32)
+        hip.check(lib.clv_memset(vx.ptr, 0, 4 * c32, None))
+        hip.check(lib.clv_fill_random_ints_f32(vy.ptr, m32, 10, 88, 0, None))
+        MU32 = 2.0 ** -24
+        LOOP_ITERS32 = 10
+
+        def f32_iteration():
+            hip.check(lib.clm_f32_mvm(P.ptr, m32, c32, vx.ptr, vt1.ptr, None))
+            hip.check(lib.clv_f32_scale_and_add(vy.ptr, vt1.ptr, -1.0, m32, vt2.ptr, None))
+            hip.check(lib.clm_f32_mvm(PT.ptr, c32, m32, vt2.ptr, vt3.ptr, None))
+            hip.check(lib.clv_f32_scale_and_add(vx.ptr, vt3.ptr, MU32, c32, vx.ptr, None))
+            hip.check(lib.clv_f32_threshold_mode(vx.ptr, c32, c32, K32, THRESHOLD_FAST, None, None))
+
+        def f32_loop(thr):
+            hip.check(lib.clm_f32_iht(P.ptr, PT.ptr, m32, c32, vx.ptr, c32, vy.ptr, vt1.ptr, vt2.ptr, vt3.ptr, LOOP_ITERS32, K32, MU32, thr, None))
+        itb32 = 2 * 4 * m32 * c32
+        rec(f"f32_q_iht_iteration_N{N32}", itb32, f32_with_env("CLV_F32_THRESHOLD_SMALL", "0", f32_iteration), reps=5,
+            extra={"note": "the five method calls one by one, threshold on the large-vector path: 13 launches; bytes = the two matrices only"})
+        for row, thr, note in ((f"f32_iht_loop_N{N32}", 1, "FAST threshold (k_f32_thresh_small): three launches per iteration"),
+                               (f"f32_gd_loop_N{N32}", 0, "no threshold (Q_GD): two launches per iteration")):
+            if not selected(row):
+                continue
+            rec(row, itb32 * LOOP_ITERS32, lambda thr=thr: f32_loop(thr), reps=2,
+                extra={"note": f"one clm_f32_iht call of {LOOP_ITERS32} iterations, ms per iteration; bytes = the two matrices only; " + note})
+            res[row]["ms"] = round(res[row]["ms"] / LOOP_ITERS32, 5)
         del P, PT, vx, vt3, vy, vt1, vt2
 print(json.dumps(res, indent=1))
