@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <vector>
+
 #include "clover_hip.h"
 
 // ---- error plumbing ---------------------------------------------------------------------------
@@ -79,6 +81,26 @@ int clv_internal_dot_chain(const void *X, uint64_t blocks_padded, float *out_dev
 int clv_internal_v8_clear(int8_t *x, float *sx, uint64_t n_pad, hipStream_t st);
 // zero-initialised hand-over slots per (device, stream), <= 64 KiB; every user leaves them zero again (runtime.hip)
 int clv_internal_sync_slots(void **ptr, uint64_t bytes, hipStream_t stream);
+
+// the batch calls (mvm_batch4.hip, threshold4.hip, iht4.hip) take host arrays of device pointers: no output range may overlap an input
+// range of ANY vector of the call (another workgroup may still be reading it) and no two outputs may overlap.  One exception the caller
+// expresses by leaving the input out: an in-place result, which IS its input.  Empty ranges never overlap anything.
+struct ClvRange {
+    uintptr_t begin, end;
+    bool output;
+    uint64_t vec;
+    const char *name;
+};
+static inline ClvRange clv_range(const void *p, uint64_t bytes, bool output, uint64_t vec, const char *name)
+{
+    return ClvRange{(uintptr_t)p, (uintptr_t)p + bytes, output, vec, name};
+}
+// mvm_batch4.hip: the launches of clm4_mvm_batch (qu == NULL) / clm4_mvm_scale_and_add_batch on CHECKED arguments, rounding disabled;
+// r / sr NULL: the mvm result is not stored (fused form only)
+int clv_internal_mvm_batch_run(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
+                               const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
+                               float a, int8_t *const *r2, float *const *sr2, void *stream);
+int clv_internal_check_ranges(const char *fn, std::vector<ClvRange> &ranges);      // sorts `ranges`; CLV_OK or CLV_ERR_INVALID with the message set
 
 // ---- device helpers ---------------------------------------------------------------------------
 #define CLV_RCP49 (1.0f / 49.0f)   // 0x3CA72F05, the reference's clover_mm256_rcp_49_ps (CloverBase.h:88)

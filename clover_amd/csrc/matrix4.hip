@@ -3,6 +3,7 @@
 // HBM layout = the reference's (CloverMatrix4.h:77-93, 123-139): row-major nibbles (rows*cols/2 bytes),
 // then one fp32 scale per 64x64 tile in a row-major (rows/64) x (cols/64) grid.
 #include "rng_device.h"
+#include "mvm_device.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -24,24 +25,6 @@
 
 #define MVM_CHUNK 65536u   // columns staged in LDS per pass
 
-template <int U, bool NT>
-__device__ __forceinline__ void mvm_steps(const u32x4 *__restrict__ Ap, const u32x4 *xs, const float *cs, int q,
-                                          uint32_t t0, float &a0, float &a1, float &a2, float &a3)
-{
-    u32x4 a[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) a[u] = NT ? __builtin_nontemporal_load(&Ap[4 * (t0 + u) + q]) : Ap[4 * (t0 + u) + q];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const u32x4 xv = xs[4 * (t0 + u) + q];
-        const float c = cs[2 * (t0 + u) + (q >> 1)];
-        a0 = __builtin_fmaf(c, (float)sdot8(a[u].x, xv.x, 0), a0);
-        a1 = __builtin_fmaf(c, (float)sdot8(a[u].y, xv.y, 0), a1);
-        a2 = __builtin_fmaf(c, (float)sdot8(a[u].z, xv.z, 0), a2);
-        a3 = __builtin_fmaf(c, (float)sdot8(a[u].w, xv.w, 0), a3);
-    }
-}
-
 // 8 lanes per row (lane e owns chains 2e, 2e+1 and loads 8 bytes per step): twice the waves per workgroup, for
 // matrices with too few 64-row groups to fill the chip with 4-wave workgroups
 template <int U, bool NT>
@@ -59,37 +42,6 @@ __device__ __forceinline__ void mvm_steps8(const u32x2 *__restrict__ Ap, const u
         a1 = __builtin_fmaf(c, (float)sdot8(a[u].y, xv.y, 0), a1);
     }
 }
-
-// re-quantise 64 values held one per lane of a full wave (CloverMatrix4.h:919-1080); returns this lane's nibble value,
-// *scale = the block maximum.  r_words / sr may be NULL (result not stored).
-__device__ __forceinline__ int requantize_wave(float d, float noise, uint32_t *r_words, float *sr, float *scale)
-{
-    const int lane = threadIdx.x & 63;
-    float m = wave_max(__builtin_fabsf(d));
-    m = fix_zero_max(m);
-    const float k = 7.0f / m;
-    const int qv = quant1(d, k, noise);
-    if (r_words) {
-        uint32_t w = ((uint32_t)qv & 0xFu) << nib_shift(lane & 7);
-        w |= __shfl_xor(w, 1);
-        w |= __shfl_xor(w, 2);
-        w |= __shfl_xor(w, 4);
-        if ((lane & 7) == 0) r_words[lane >> 3] = w;
-        if (lane == 0) *sr = m;
-    }
-    *scale = m;
-    return qv;
-}
-
-// FUSE: the scaleAndAdd that follows mvm in the IHT / GD loops (t2 = y - Phi x;  x += mu Phi' t2), done on the row
-// group while it is still in the wave:  r2 = quantize(u + a * quantize(A x))  (CloverVector4.h:1196-1478).
-struct MvmFuse {
-    const uint32_t *qu;      // u, one 64-element block per row group
-    const float *su;
-    float a;
-    uint32_t *r2;            // may alias qu (the in-place overload)
-    float *sr2;
-};
 
 // ST: stochastic re-quantisation fused into the epilogue (CloverMatrix4.h:919-1080 with the rnd_* branch).  Row group
 // rb consumes draws 2rb, 2rb+1 of the stream; the dots sit pre-transposed in the reference's block_values, so noise
@@ -179,16 +131,7 @@ __global__ __launch_bounds__(64 * L) void k_m4_mvm64(const uint8_t *__restrict__
         }
     }
 
-    // chain (4q+i): accumulator a = q>>1, AVX lane w = 4(q&1)+i.  Fixed tree of CloverBase.h:149-157:
-    const float v0 = a0 + __shfl_xor(a0, 2);     // acc[0][w] + acc[1][w]
-    const float v1 = a1 + __shfl_xor(a1, 2);
-    const float v2 = a2 + __shfl_xor(a2, 2);
-    const float v3 = a3 + __shfl_xor(a3, 2);
-    const float x0 = v0 + __shfl_xor(v0, 1);     // v[i+4] + v[i]
-    const float x1 = v1 + __shfl_xor(v1, 1);
-    const float x2 = v2 + __shfl_xor(v2, 1);
-    const float x3 = v3 + __shfl_xor(v3, 1);
-    float dot = (x0 + x2) + (x1 + x3);
+    float dot = mvm_tree(a0, a1, a2, a3);
     if constexpr (L == 8) {
         // chain 2q+i: accumulator a = q>>2, AVX lane w = 2(q&3)+i.  Same tree: acc[0][w]+acc[1][w] (lanes q, q^4), then
         // v[w]+v[w+4] (q, q^2) gives x[2(q&1)+i], then (x0+x2)+(x1+x3) (q, q^1)
@@ -452,7 +395,7 @@ extern "C" int clvx_mvm_variant(int variant, const int8_t *A, const float *sA, u
 }
 #endif      // CLV_EXPERIMENTS
 
-static int check_mvm_args(const char *fn, const void *A, const void *sA, uint64_t rows, uint64_t cols, const void *x, const void *sx)
+int check_mvm_args(const char *fn, const void *A, const void *sA, uint64_t rows, uint64_t cols, const void *x, const void *sx)
 {
     CLV_REQUIRE(A && sA && x && sx, "%s: null pointer", fn);
     // a whole CloverMatrix4 has rows % 128 == 0 (CloverMatrix.h:48-53); a multiple of 64 is a row shard of one -- the unit

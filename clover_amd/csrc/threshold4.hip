@@ -314,8 +314,9 @@ __device__ __forceinline__ unsigned long long th4_count_full_block(const uint32_
 #define TS4_COPIES 4           // 1 / 2 / 4 / 8 copies: n = 131072 33.9 / 30.4 / 28.7 / 29.1 us, n = 32768 10.6 / 9.8 / 9.5 / 10.3, n = 8192 6.1 / 6.4 / 6.0 / 6.5 (r6, same box)
 #endif
 #define TS4_CS (TS4_COPIES == 1 ? 256 : 260)
+// the body of k_thresh_small and of k_thresh_small_batch (one workgroup = one vector in both)
 template <int W>
-__global__ __launch_bounds__(TS_THREADS) void k_thresh_small(uint32_t *__restrict__ q, const float *__restrict__ s, uint32_t n, uint32_t k)
+__device__ __forceinline__ void thresh_small_body(uint32_t *__restrict__ q, const float *__restrict__ s, uint32_t n, uint32_t k)
 {
     constexpr int MAXB = TS_THREADS * TS_MAXW / 8;                       // 2048 blocks at most
     constexpr int NC = (9 * W + 7) / 8 + 1;                              // candidates per thread at most
@@ -452,6 +453,25 @@ __global__ __launch_bounds__(TS_THREADS) void k_thresh_small(uint32_t *__restric
             q[i] = w[j] & swap_nibbles(full);
         }
     }
+}
+
+template <int W>
+__global__ __launch_bounds__(TS_THREADS) void k_thresh_small(uint32_t *__restrict__ q, const float *__restrict__ s, uint32_t n, uint32_t k)
+{
+    thresh_small_body<W>(q, s, n, k);
+}
+
+// clv4_threshold_batch: workgroup j runs the body above on vector j.  The pointers travel by value in the kernel arguments (no table in
+// device memory, nothing to allocate, captures into a graph); a call with more vectors than the struct holds runs in groups.
+#define TS_BATCH_GROUP 64
+struct ThreshBatchArgs {
+    uint32_t *q[TS_BATCH_GROUP];
+    const float *s[TS_BATCH_GROUP];
+};
+template <int W>
+__global__ __launch_bounds__(TS_THREADS) void k_thresh_small_batch(ThreshBatchArgs args, uint32_t n, uint32_t k)
+{
+    thresh_small_body<W>(args.q[blockIdx.x], args.s[blockIdx.x], n, k);
 }
 
 // ---- single-workgroup path for CloverVector8 (n_pad <= 32768): element keys live in registers (8 words = 32 elements per
@@ -1922,6 +1942,57 @@ extern "C" int clv4_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64
     CLV_REQUIRE_WORKSPACE("clv4_threshold_mode", workspace);
     if (k >= n || n == 0) return CLV_OK;
     return threshold_reference<4>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream));
+}
+
+// CloverVector4::threshold on nvec vectors of one size.  q / s: HOST arrays of nvec device pointers.  FAST up to the one-workgroup limit:
+// one launch, workgroup j = k_thresh_small's body on vector j; otherwise the sequence of single calls.  Bit-identical to that sequence.
+extern "C" int clv4_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode,
+                                    void *stream)
+{
+    const char *fn = "clv4_threshold_batch";
+    CLV_REQUIRE(mode == CLV_THRESHOLD_FAST || mode == CLV_THRESHOLD_REFERENCE, "%s: unknown mode %d", fn, mode);
+    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "%s: n=%llu n_pad=%llu", fn, (unsigned long long)n, (unsigned long long)n_pad);
+    CLV_REQUIRE(n < (1ull << 32), "%s: vectors of 2^32 or more elements are not supported", fn);
+    if (!nvec) return CLV_OK;
+    CLV_REQUIRE(q && s, "%s: null pointer array", fn);
+    for (uint64_t j = 0; j < nvec; j++) CLV_REQUIRE(q[j] && s[j], "%s: null pointer in vector %llu", fn, (unsigned long long)j);
+    {
+        std::vector<ClvRange> rg;
+        rg.reserve(2 * nvec);
+        for (uint64_t j = 0; j < nvec; j++) {
+            rg.push_back(clv_range(q[j], n_pad / 2, true, j, "q"));
+            rg.push_back(clv_range(s[j], n_pad / 64 * sizeof(float), false, j, "s"));
+        }
+        int rc = clv_internal_check_ranges(fn, rg);
+        if (rc) return rc;
+    }
+    if (k >= n || n == 0) return CLV_OK;                       // everything survives
+    if (nvec == 1 || mode != CLV_THRESHOLD_FAST || n_pad > (uint64_t)TS_THREADS * TS_MAXW * 8) {
+        for (uint64_t j = 0; j < nvec; j++) {
+            int rc = clv4_threshold_mode(q[j], s[j], n, n_pad, k, mode, nullptr, stream);
+            if (rc) return rc;
+        }
+        return CLV_OK;
+    }
+    hipStream_t st = as_stream(stream);
+    const uint64_t wpt = ((n + 7) / 8 + TS_THREADS - 1) / TS_THREADS;         // words per thread, as clv4_threshold
+    for (uint64_t j0 = 0; j0 < nvec; j0 += TS_BATCH_GROUP) {
+        const uint64_t g = nvec - j0 < TS_BATCH_GROUP ? nvec - j0 : TS_BATCH_GROUP;
+        ThreshBatchArgs args;
+        for (uint64_t j = 0; j < TS_BATCH_GROUP; j++) {
+            args.q[j] = j < g ? (uint32_t *)q[j0 + j] : nullptr;
+            args.s[j] = j < g ? s[j0 + j] : nullptr;
+        }
+#define T4_LAUNCH(W) hipLaunchKernelGGL(k_thresh_small_batch<W>, dim3((unsigned)g), dim3(TS_THREADS), 0, st, args, (uint32_t)n, (uint32_t)k)
+        if (wpt <= 1) T4_LAUNCH(1);
+        else if (wpt <= 2) T4_LAUNCH(2);
+        else if (wpt <= 4) T4_LAUNCH(4);
+        else if (wpt <= 8) T4_LAUNCH(8);
+        else T4_LAUNCH(16);
+#undef T4_LAUNCH
+        CLV_LAUNCH_CHECK();
+    }
+    return CLV_OK;
 }
 
 // threshold_min_heap (CloverVector4.h:1929-1970, CloverVector8.h:1696-1737): the REFERENCE walk, and the K-entry heap as the walk leaves it

@@ -116,6 +116,12 @@ SIGNATURES = {
     "clm_f16_transpose": (C.c_int, [_vp, _u64, _u64, _vp, _vp]),
     "clm4_iht": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
                           C.c_float, C.c_int, _vp, _vp]),
+    # the batch calls: pointer arrays are HOST arrays (ctypes arrays of c_void_p) of device pointers
+    "clm4_mvm_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm4_mvm_scale_and_add_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clv4_threshold_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _u64, C.c_int, _vp]),
+    "clm4_iht_batch": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
+                                C.c_float, C.c_int, _vp, _vp]),
     "clm4_shard_partition": (C.c_int, [_u64, C.c_int, C.c_int, C.POINTER(_u64), C.POINTER(_u64)]),
     "clm4_sharded_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(C.c_int), _u64, _u64]),
     "clm4_sharded_destroy": (C.c_int, [_vp]),
@@ -338,6 +344,71 @@ class CloverHip:
                                                    rng.ptr if rng else None, None))
         t = (dt.download(np.uint8, rows // 2), dst.download(np.float32, rows // 64)) if want_t else (None, None)
         return t[0], t[1], dr.download(np.uint8, rows // 2), dsr.download(np.float32, rows // 64)
+
+    # -- several vectors with one CloverMatrix4 (host arrays of device pointers; lists in, lists out) ------------------------------
+    @staticmethod
+    def ptr_array(ptrs):
+        """a host array of device pointers for the batch calls, from DevBufs / addresses; None stays NULL"""
+        if ptrs is None:
+            return None
+        return (_vp * len(ptrs))(*[p.ptr if isinstance(p, DevBuf) else p for p in ptrs])
+
+    def m4_mvm_batch(self, qA, sA, rows, cols, xs, rng: DevBuf | None = None):
+        """xs: list of (qx, sx); returns the list of (r, sr) of clm4_mvm_batch.  qA may be a DevBuf (a matrix uploaded once)"""
+        dA, dsA = (qA, sA) if isinstance(qA, DevBuf) else (self.to_device(qA), self.to_device(sA))
+        dx = [(self.to_device(q), self.to_device(s)) for q, s in xs]
+        dr = [(self.alloc(max(rows // 2, 1)), self.alloc(max(rows // 16, 4))) for _ in xs]
+        pa = self.ptr_array
+        self.check(self.lib.clm4_mvm_batch(dA.ptr, dsA.ptr, rows, cols, len(xs), pa([d[0] for d in dx]), pa([d[1] for d in dx]),
+                                           pa([d[0] for d in dr]), pa([d[1] for d in dr]), rng.ptr if rng else None, None))
+        return [(r.download(np.uint8, rows // 2), sr.download(np.float32, rows // 64)) for r, sr in dr]
+
+    def m4_mvm_scale_and_add_batch(self, qA, sA, rows, cols, xs, us, a: float, rng: DevBuf | None = None, in_place: bool = False,
+                                   want_t: bool = True):
+        """xs, us: lists of (q, s); returns the list of (t, st, r, sr) of clm4_mvm_scale_and_add_batch; t/st are None when want_t is False"""
+        dA, dsA = (qA, sA) if isinstance(qA, DevBuf) else (self.to_device(qA), self.to_device(sA))
+        dx = [(self.to_device(q), self.to_device(s)) for q, s in xs]
+        du = [(self.to_device(q), self.to_device(s)) for q, s in us]
+        dt = [(self.alloc(rows // 2), self.alloc(rows // 16)) for _ in xs] if want_t else None
+        dr = du if in_place else [(self.alloc(rows // 2), self.alloc(rows // 16)) for _ in xs]
+        pa = self.ptr_array
+        self.check(self.lib.clm4_mvm_scale_and_add_batch(
+            dA.ptr, dsA.ptr, rows, cols, len(xs), pa([d[0] for d in dx]), pa([d[1] for d in dx]), pa([d[0] for d in du]), pa([d[1] for d in du]), a,
+            pa([d[0] for d in dt]) if dt else None, pa([d[1] for d in dt]) if dt else None, pa([d[0] for d in dr]), pa([d[1] for d in dr]),
+            rng.ptr if rng else None, None))
+        out = []
+        for j in range(len(xs)):
+            t = (dt[j][0].download(np.uint8, rows // 2), dt[j][1].download(np.float32, rows // 64)) if want_t else (None, None)
+            out.append((t[0], t[1], dr[j][0].download(np.uint8, rows // 2), dr[j][1].download(np.float32, rows // 64)))
+        return out
+
+    def v4_threshold_batch(self, vs, n: int, k: int, mode: int = THRESHOLD_FAST):
+        """vs: list of (q, s) of one padded size; returns the list of thresholded q"""
+        dv = [(self.to_device(q), self.to_device(s)) for q, s in vs]
+        pa = self.ptr_array
+        self.check(self.lib.clv4_threshold_batch(pa([d[0] for d in dv]), pa([d[1] for d in dv]), len(vs), n, vs[0][0].size * 2 if vs else 0, k,
+                                                 mode, None))
+        return [d[0].download(np.uint8, q.size) for d, (q, _) in zip(dv, vs)]
+
+    def m4_iht_batch(self, qPhi, sPhi, qPhiT, sPhiT, m, n, ys, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+                     rng: DevBuf | None = None, prefill: int = 0x55):
+        """clm4_iht_batch on buffers prefilled with `prefill` bytes; ys: list of (qy, sy); returns per vector
+        {"x": (q, s), "t1": ..., "t2": ..., "t3": ...}"""
+        b = [self.to_device(v) for v in (qPhi, sPhi, qPhiT, sPhiT)]
+        dy = [(self.to_device(q), self.to_device(s)) for q, s in ys]
+        lens = {"x": n, "t1": m, "t2": m, "t3": n}
+        v = {name: [(self.alloc(ln // 2), self.alloc(ln // 16)) for _ in ys] for name, ln in lens.items()}
+        for bufs in v.values():
+            for pair in bufs:
+                for d in pair:
+                    self.check(self.lib.clv_memset(d.ptr, prefill, d.nbytes, None))
+        pa = self.ptr_array
+        arr = {name: (pa([d[0] for d in bufs]), pa([d[1] for d in bufs])) for name, bufs in v.items()}
+        self.check(self.lib.clm4_iht_batch(b[0].ptr, b[1].ptr, b[2].ptr, b[3].ptr, m, n, len(ys), arr["x"][0], arr["x"][1], n if x_len is None else x_len,
+                                           pa([d[0] for d in dy]), pa([d[1] for d in dy]), arr["t1"][0], arr["t1"][1], arr["t2"][0], arr["t2"][1],
+                                           arr["t3"][0], arr["t3"][1], iterations, K, mu, threshold, rng.ptr if rng else None, None))
+        return [{name: (v[name][j][0].download(np.uint8, ln // 2), v[name][j][1].download(np.float32, ln // 64)) for name, ln in lens.items()}
+                for j in range(len(ys))]
 
     # -- mixed precision (CloverVector8) ----------------------------------------------------------
     def v8_quantize(self, x: np.ndarray, rng: DevBuf | None = None):

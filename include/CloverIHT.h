@@ -80,6 +80,31 @@ inline void Q_GD(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 &x, Clov
 }
 
 
+/* Not in the reference: Q_IHT / Q_GD for `count` signals with ONE Phi (CloverMatrix4::iht_loop_batch -> clm4_iht_batch): per iteration two
+ * passes over Phi / PhiT for every group of CLM4_MVM_BATCH_MAX signals instead of two per signal.  x[j], t1[j], t2[j], t3[j] end as
+ * Q_IHT(Phi, PhiT, *x[j], *y[j], *t1[j], *t2[j], *t3[j], ...) leaves them, bit for bit; with stochastic rounding enabled that IS what runs. */
+inline void Q_IHT_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 *const *x, CloverVector4 *const *y, CloverVector4 *const *t1,
+                        CloverVector4 *const *t2, CloverVector4 *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
+                        const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, K, mu, true);
+#else
+    for (uint64_t j = 0; j < count; j++) Q_IHT(Phi, PhiT, *x[j], *y[j], *t1[j], *t2[j], *t3[j], iterations, K, mu);
+#endif
+}
+
+inline void Q_GD_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 *const *x, CloverVector4 *const *y, CloverVector4 *const *t1,
+                       CloverVector4 *const *t2, CloverVector4 *const *t3, const uint64_t count, const uint64_t iterations, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#else
+    for (uint64_t j = 0; j < count; j++) Q_GD(Phi, PhiT, *x[j], *y[j], *t1[j], *t2[j], *t3[j], iterations, mu);
+#endif
+}
+
+
 /* CloverMatrix4 with CloverVector8 vectors: the configuration the reference measures and publishes as the 4-bit IHT / GD
  * (test/performance/02_bit04.cpp:140; "the 4-bit version uses the mixed precision MVM", doc/results/performance.txt:597-606) */
 inline void Q_IHT(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector8 &x, CloverVector8 &y, CloverVector8 &t1, CloverVector8 &t2,

@@ -21,6 +21,7 @@
 #ifndef CLOVER_MATRIX4_H
 #define CLOVER_MATRIX4_H
 
+#include <vector>
 #include <cmath>
 #include <iomanip>
 #include <sstream>
@@ -186,6 +187,128 @@ public:
     {
         if (x.size() != getCols() || t.size_pad() != getRows()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
         if (u.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+    }
+    /* Not in the reference: this * x[j] for `count` vectors in ONE pass over the matrix per group of CLM4_MVM_BATCH_MAX (clm4_mvm_batch);
+     * r[j] equals what mvm(*x[j], *r[j]) gives, bit for bit.  The x[j] may repeat; the r[j] are distinct vectors, none of them an x.
+     * With stochastic rounding enabled the calls draw from the matrix's generator one after another: the single calls, in order. */
+    void mvm_batch(const CloverVector4 *const *x, CloverVector4 *const *r, uint64_t count)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        std::vector<const int8_t *> px(count);
+        std::vector<const float *> psx(count);
+        std::vector<int8_t *> pr(count);
+        std::vector<float *> psr(count);
+        for (uint64_t j = 0; j < count; j++) {
+            if (x[j]->size() != getCols() || r[j]->size_pad() != getRows()) {
+                std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+                exit(1);
+            }
+            px[j] = x[j]->dev_values_ro();
+            psx[j] = x[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) { pr[j] = r[j]->dev_values_wo(); psr[j] = r[j]->dev_scales_wo(); }
+        clover_hip::check(clm4_mvm_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), nullptr, nullptr),
+                          "CloverMatrix4::mvm_batch");
+        for (uint64_t j = 0; j < count; j++) r[j]->commit();
+#else
+        for (uint64_t j = 0; j < count; j++) mvm(*x[j], *r[j]);
+#endif
+    }
+    /* mvm_scaleAndAdd for `count` vectors (clm4_mvm_scale_and_add_batch): t[j] = this * x[j], r[j] = quantize(u[j] + a * t[j]) */
+    void mvm_scaleAndAdd_batch(const CloverVector4 *const *x, const CloverVector4 *const *u, float a, CloverVector4 *const *t, CloverVector4 *const *r,
+                               uint64_t count)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        std::vector<const int8_t *> px(count), pu(count);
+        std::vector<const float *> psx(count), psu(count);
+        std::vector<int8_t *> pt(count), pr(count);
+        std::vector<float *> pst(count), psr(count);
+        for (uint64_t j = 0; j < count; j++) {
+            check_fused(*x[j], *u[j], *t[j]);
+            if (r[j]->size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+            px[j] = x[j]->dev_values_ro();
+            psx[j] = x[j]->dev_scales_ro();
+            pu[j] = u[j]->dev_values_ro();
+            psu[j] = u[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) {
+            pt[j] = t[j]->dev_values_wo();
+            pst[j] = t[j]->dev_scales_wo();
+            pr[j] = r[j]->dev_values_wo();
+            psr[j] = r[j]->dev_scales_wo();
+        }
+        clover_hip::check(clm4_mvm_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(), psu.data(), a,
+                                                       pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
+                          "CloverMatrix4::mvm_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
+#else
+        for (uint64_t j = 0; j < count; j++) mvm_scaleAndAdd(*x[j], *u[j], a, *t[j], *r[j]);
+#endif
+    }
+    /* in place: u[j] = quantize(u[j] + a * (this * x[j])) */
+    void mvm_scaleAndAdd_batch(const CloverVector4 *const *x, CloverVector4 *const *u, float a, CloverVector4 *const *t, uint64_t count)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        std::vector<const int8_t *> px(count), pu(count);
+        std::vector<const float *> psx(count), psu(count);
+        std::vector<int8_t *> pt(count), pr(count);
+        std::vector<float *> pst(count), psr(count);
+        for (uint64_t j = 0; j < count; j++) {
+            check_fused(*x[j], *u[j], *t[j]);
+            px[j] = x[j]->dev_values_ro();
+            psx[j] = x[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) {
+            pu[j] = pr[j] = u[j]->dev_values_rw();
+            psu[j] = psr[j] = u[j]->dev_scales_rw();
+            pt[j] = t[j]->dev_values_wo();
+            pst[j] = t[j]->dev_scales_wo();
+        }
+        clover_hip::check(clm4_mvm_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(), psu.data(), a,
+                                                       pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
+                          "CloverMatrix4::mvm_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
+#else
+        for (uint64_t j = 0; j < count; j++) mvm_scaleAndAdd(*x[j], *u[j], a, *t[j]);
+#endif
+    }
+    /* iht_loop for `count` signals with this matrix as Phi (clm4_iht_batch): per iteration every step runs once for a group of signals;
+     * x[j], t1[j], t2[j], t3[j] end as iht_loop(PhiT, *x[j], *y[j], ...) leaves them.  Deterministic rounding only, as iht_loop. */
+    void iht_loop_batch(CloverMatrix4 &PhiT, CloverVector4 *const *x, const CloverVector4 *const *y, CloverVector4 *const *t1, CloverVector4 *const *t2,
+                        CloverVector4 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    {
+        std::vector<const int8_t *> py(count);
+        std::vector<const float *> psy(count);
+        std::vector<int8_t *> px(count), p1(count), p2(count), p3(count);
+        std::vector<float *> psx(count), ps1(count), ps2(count), ps3(count);
+        for (uint64_t j = 0; j < count; j++) {
+            if (PhiT.getRows() != getCols() || PhiT.getCols() != getRows() || x[j]->size_pad() != getCols() || y[j]->size_pad() != getRows() ||
+                t1[j]->size_pad() != getRows() || t2[j]->size_pad() != getRows() || t3[j]->size_pad() != getCols() || x[j]->size() != x[0]->size()) {
+                std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+                exit(1);
+            }
+            py[j] = y[j]->dev_values_ro();
+            psy[j] = y[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) {
+            px[j] = x[j]->dev_values_wo();
+            psx[j] = x[j]->dev_scales_wo();
+            p1[j] = t1[j]->dev_values_wo();
+            ps1[j] = t1[j]->dev_scales_wo();
+            p2[j] = t2[j]->dev_values_wo();
+            ps2[j] = t2[j]->dev_scales_wo();
+            p3[j] = t3[j]->dev_values_wo();
+            ps3[j] = t3[j]->dev_scales_wo();
+        }
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm4_iht_batch(dev_values(), dev_scales(), PhiT.dev_values(), PhiT.dev_scales(), rows, cols, count, px.data(), psx.data(),
+                                         count ? x[0]->size() : 0, py.data(), psy.data(), p1.data(), ps1.data(), p2.data(), ps2.data(), p3.data(),
+                                         ps3.data(), iterations, K, mu, thr, nullptr, nullptr),
+                          "CloverMatrix4::iht_loop_batch");
+        for (uint64_t j = 0; j < count; j++) {
+            x[j]->commit();
+            if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }
+        }
     }
     /* The reference's mvm_scalar (:311-392): every row wrapped in a non-owning CloverVector4 view over the matrix's own memory and
      * multiplied with dot() (the SIMD order, here the exact-order kernel), then 64 results at a time quantised by scalar code.  An

@@ -24,6 +24,7 @@
 #define CLOVER_VECTOR4_H
 
 #include <bitset>
+#include <vector>
 
 #include "CloverVector32.h"
 #include "clover_scalar.h"
@@ -252,6 +253,21 @@ public:
         commit();
     }
     void threshold_parallel(uint64_t k) { threshold(k); }
+    /* threshold(k) on `count` vectors of one size (clv4_threshold_batch): with the fast tie rule and vectors of up to 131072 elements
+     * ONE launch, else the single calls in order; every v[j] ends as v[j]->threshold(k) leaves it.  Honours the exactness switch. */
+    static void threshold_batch(CloverVector4 *const *v, uint64_t count, uint64_t k)
+    {
+        std::vector<int8_t *> pq(count);
+        std::vector<const float *> ps(count);
+        for (uint64_t j = 0; j < count; j++) {
+            if (v[j]->length != v[0]->length) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+            pq[j] = v[j]->dev_values_rw();
+            ps[j] = v[j]->dev_scales_ro();
+        }
+        clover_hip::check(clv4_threshold_batch(pq.data(), ps.data(), count, count ? v[0]->length : 0, count ? v[0]->length_pad : 0, k,
+                                               clover_hip::threshold_mode(), nullptr), "CloverVector4::threshold_batch");
+        for (uint64_t j = 0; j < count; j++) v[j]->commit();
+    }
     /* threshold with the caller's own heap memory (CloverVector4.h:1929-1970, 1975-2057): ALWAYS the reference's walk, whatever the
      * exactness switch says -- the caller keeps the heap, so it gets the reference's: min_heap[i] = {|value|, bits, idx} of the K
      * survivors in the reference's array order.  k <= size().  _parallel: the reference merges per-thread heaps, which keeps the same K

@@ -422,6 +422,47 @@ int  clm4_iht(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const fl
               int8_t *t2, float *st2, int8_t *t3, float *st3, uint64_t iterations, uint64_t K, float mu, int threshold,
               uint64_t *rng_state_dev, void *stream);
 
+/* ---- several right-hand sides with one matrix: one pass over the matrix for up to CLM4_MVM_BATCH_MAX vectors ----------------
+ * A NEW KIND OF ARGUMENT: the pointer arrays of these four calls (x, sx, r, sr, qu, su, t, st, q, s, y, sy, t1 .. st3) are HOST arrays of
+ * `nvec` DEVICE pointers.  The library reads the arrays during the call and keeps nothing of them: the device pointers travel by value
+ * in the kernel arguments, no table is copied to the device, nothing is allocated, and a deterministic call captures into a hipGraph
+ * (the graph holds the device pointers, not the arrays).
+ * CONTRACT: each call is bit-identical to the corresponding single call made for vector 0, then 1, ... on the same stream -- clm4_mvm,
+ * clm4_mvm_scale_and_add, clv4_threshold_mode with a NULL workspace, clm4_iht -- including what is left in t1 .. t3 and, with an rng,
+ * the XORShift state left behind.
+ *  - nvec may be any number: groups of at most CLM4_MVM_BATCH_MAX vectors run one matrix pass each; nvec == 1 forwards to the single
+ *    call; nvec == 0 or rows == 0 returns CLV_OK and does nothing.  The launcher takes the batched kernel only where it was measured
+ *    faster than the single launches and forwards to them elsewhere: same bits either way.
+ *  - rng_state_dev != NULL: the call RUNS AS THE SEQUENCE OF SINGLE CALLS -- vector j's draws follow vector j - 1's in the stream, and
+ *    for clm4_iht_batch that is all iterations of vector 0 first.  The stream order of the draws allows nothing else; it is not a
+ *    defect.  The rules for stochastic calls above apply.
+ *  - clv4_threshold_batch: FAST with n_pad <= 131072 (the one-workgroup kernel) is ONE launch, workgroup j thresholding vector j;
+ *    REFERENCE mode and larger vectors run as the sequence of single calls (and use the stream's scratch as those do).
+ *  - clm4_iht_batch without an rng: every x[j] cleared, then per iteration and group two clm4_mvm_scale_and_add_batch launches and,
+ *    if threshold != 0, one clv4_threshold_batch (threshold, x_len, K, mu as clm4_iht).  Where a single clm4_iht takes the persistent
+ *    kernel (m, n <= 8192, threshold FAST or none) only full groups of CLM4_MVM_BATCH_MAX run this way -- the one group size at which it
+ *    was measured faster than that kernel -- and a smaller group runs as single calls; those do not capture into a hipGraph (clm4_iht).
+ *  - CLV_MVM_BATCH in the environment (read per call; for tests and measurements): 1 = every group of two or more vectors runs
+ *    batched, 0 = every call forwards to the single calls.
+ *  - checked before any device work (CLV_ERR_INVALID, the message names the call and the vector index): the size rules of the
+ *    single calls; no NULL array and no NULL entry (t and st: both arrays given or both NULL = t is not stored); no output range may
+ *    overlap an input range of ANY vector of the call -- another workgroup may still be reading it -- nor the matrix; no two outputs
+ *    may overlap.  One exception: r[j] / sr[j] may be exactly qu[j] / su[j], the in-place form.  Repeated INPUT pointers are allowed. */
+#define CLM4_MVM_BATCH_MAX 8
+int  clm4_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
+                    const int8_t *const *x, const float *const *sx, int8_t *const *r, float *const *sr,
+                    uint64_t *rng_state_dev, void *stream);
+int  clm4_mvm_scale_and_add_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
+                    const int8_t *const *x, const float *const *sx, const int8_t *const *qu, const float *const *su, float a,
+                    int8_t *const *t, float *const *st,      /* both arrays NULL: t is not stored */
+                    int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, void *stream);
+int  clv4_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k,
+                    int mode, void *stream);
+int  clm4_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, uint64_t nvec,
+                    int8_t *const *x, float *const *sx, uint64_t x_len, const int8_t *const *y, const float *const *sy,
+                    int8_t *const *t1, float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
+                    uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream);
+
 /* ---- multi-GPU: row-sharded mvm on the GPUs of one node (one process, RCCL over xGMI) --------------- */
 /* MI355X counterpart of mvm_parallel's contiguous split of 64-row blocks over threads
  * (CloverMatrix4.h:1700-1705): shard `part` owns a contiguous multiple of 64 rows, x is replicated, the

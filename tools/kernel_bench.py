@@ -120,6 +120,125 @@ if any(selected(r) for r in GEMM_ROWS):
         sys.exit(0)
 
 
+# ---- several vectors with one CloverMatrix4 (mvm_batch4.hip): every row pairs the batch call, on the batched kernel (CLV_MVM_BATCH=1),
+# with the same vectors issued as single calls in the same session.  A run that names only these rows (KB_ONLY=mvm_batch,mvm_saa_batch,
+# iht_batch) ends after them.
+BATCH_ROWS = ("mvm_batch2_32768^2", "mvm_batch4_32768^2", "mvm_batch8_32768^2", "mvm_batch2_65536^2", "mvm_batch4_65536^2", "mvm_batch8_65536^2",
+              "mvm_saa_batch2_8192x4096", "mvm_saa_batch4_8192x4096", "mvm_saa_batch8_8192x4096", "iht_batch8_N8192")
+
+
+def rounds_of(fn, reps=10, rounds=5, warm=2):
+    """the five round values of timeit (ms per call), not only their median"""
+    for _ in range(warm):
+        fn()
+    hip.sync()
+    a, b = vp(), vp()
+    hip.check(lib.clv_event_create(C.byref(a)))
+    hip.check(lib.clv_event_create(C.byref(b)))
+    ts = []
+    for _ in range(rounds):
+        hip.check(lib.clv_event_record(a, None))
+        for _ in range(reps):
+            fn()
+        hip.check(lib.clv_event_record(b, None))
+        hip.check(lib.clv_event_sync(b))
+        ms = C.c_float()
+        hip.check(lib.clv_event_elapsed_ms(a, b, C.byref(ms)))
+        ts.append(ms.value / reps)
+    return sorted(ts)
+
+
+def rec_pair(name, nbytes_single, g, single, batch, reps=10, per=1):
+    """single: the g single calls; batch: the one batch call.  per: divides both (iterations of a loop call)"""
+    if not selected(name):
+        return
+    os.environ.pop("CLV_MVM_BATCH", None)
+    one = [t / per for t in rounds_of(single, reps=reps)]
+    os.environ["CLV_MVM_BATCH"] = "1"
+    try:
+        many = [t / per for t in rounds_of(batch, reps=reps)]
+    finally:
+        os.environ.pop("CLV_MVM_BATCH", None)
+    o, m, spread = one[len(one) // 2], many[len(many) // 2], one[-1] - one[0]
+    res[name] = {"vectors": g, "batch_ms": round(m, 5), "single_calls_ms": round(o, 5), "single_calls_rounds_ms": [round(t, 5) for t in one],
+                 "batch_rounds_ms": [round(t, 5) for t in many], "single_calls_spread_ms": round(spread, 5), "speedup": round(o / m, 3),
+                 "batch_faster_by_more_than_the_spread": bool(o - m > spread),
+                 "GB/s_per_vector_batch": round(g * nbytes_single / m / 1e6, 1), "GB/s_single_calls": round(g * nbytes_single / o / 1e6, 1)}
+
+
+def ptrs(bufs):
+    return (vp * len(bufs))(*[b.ptr for b in bufs])
+
+
+def vec_set(count, n, seed):
+    out = []
+    for j in range(count):
+        q, s = hip.alloc(n // 2), hip.alloc(n // 16)
+        hip.check(lib.clv_fill_random_nibbles(q.ptr, q.nbytes, seed + 2 * j, 0, None))
+        hip.check(lib.clv_fill_random_scales(s.ptr, s.nbytes // 4, seed + 2 * j + 1, 0, None))
+        out.append((q, s))
+    return out
+
+
+if any(selected(r) for r in BATCH_ROWS):
+    for nb in (32768, 65536):
+        if not any(selected(f"mvm_batch{g}_{nb}^2") for g in (2, 4, 8)):
+            continue
+        bA, bsA = hip.alloc(nb * nb // 2), hip.alloc((nb // 64) ** 2 * 4)
+        hip.check(lib.clv_fill_random_nibbles(bA.ptr, bA.nbytes, 41, 0, None))
+        hip.check(lib.clv_fill_random_scales(bsA.ptr, bsA.nbytes // 4, 42, 0, None))
+        bx, br = vec_set(8, nb, 300), vec_set(8, nb, 400)
+        one_b = nb * nb // 2 + 4 * (nb // 64) ** 2 + 2 * (nb // 2 + nb // 16)
+        for g in (2, 4, 8):
+            ax, asx, ar, asr = ptrs([v[0] for v in bx[:g]]), ptrs([v[1] for v in bx[:g]]), ptrs([v[0] for v in br[:g]]), ptrs([v[1] for v in br[:g]])
+
+            def singles(g=g):
+                for j in range(g):
+                    hip.check(lib.clm4_mvm(bA.ptr, bsA.ptr, nb, nb, bx[j][0].ptr, bx[j][1].ptr, br[j][0].ptr, br[j][1].ptr, None, None))
+            rec_pair(f"mvm_batch{g}_{nb}^2", one_b, g, singles,
+                     lambda g=g, a=(ax, asx, ar, asr): hip.check(lib.clm4_mvm_batch(bA.ptr, bsA.ptr, nb, nb, g, a[0], a[1], a[2], a[3], None, None)),
+                     reps=10 if nb == 32768 else 4)
+        del bA, bsA, bx, br
+    # the IHT shape (N = 8192: Phi 4096 x 8192, cache-resident): the x += mu Phi' t2 step for 8 signals, and the whole loop
+    im, inn, ig, iters = 4096, 8192, 8, 20
+    if any(selected(r) for r in BATCH_ROWS[6:]):
+        P, sP, PT, sPT = hip.alloc(im * inn // 2), hip.alloc(4 * (im // 64) * (inn // 64)), hip.alloc(im * inn // 2), hip.alloc(4 * (im // 64) * (inn // 64))
+        hip.check(lib.clv_fill_random_nibbles(P.ptr, P.nbytes, 51, 0, None))
+        hip.check(lib.clv_fill_random_scales(sP.ptr, sP.nbytes // 4, 52, 0, None))
+        hip.check(lib.clm4_transpose(P.ptr, sP.ptr, im, inn, PT.ptr, sPT.ptr, None))
+        vy, vx, vt1, vt2, vt3 = vec_set(ig, im, 500), vec_set(ig, inn, 600), vec_set(ig, im, 700), vec_set(ig, im, 800), vec_set(ig, inn, 900)
+        A = {k: (ptrs([p[0] for p in v]), ptrs([p[1] for p in v])) for k, v in dict(y=vy, x=vx, t1=vt1, t2=vt2, t3=vt3).items()}
+        vr = vec_set(ig, inn, 1000)
+        Ar = (ptrs([p[0] for p in vr]), ptrs([p[1] for p in vr]))
+        saa_b = im * inn // 2 + 4 * (im // 64) * (inn // 64) + (im // 2 + im // 16) + 3 * (inn // 2 + inn // 16)
+
+        for sg in (2, 4, 8):
+            def saa_singles(sg=sg):
+                for j in range(sg):
+                    hip.check(lib.clm4_mvm_scale_and_add(PT.ptr, sPT.ptr, inn, im, vt2[j][0].ptr, vt2[j][1].ptr, vx[j][0].ptr, vx[j][1].ptr, 0.002,
+                                                         vt3[j][0].ptr, vt3[j][1].ptr, vr[j][0].ptr, vr[j][1].ptr, None, None))
+            rec_pair(f"mvm_saa_batch{sg}_8192x4096", saa_b, sg, saa_singles,
+                     lambda sg=sg: hip.check(lib.clm4_mvm_scale_and_add_batch(PT.ptr, sPT.ptr, inn, im, sg, A["t2"][0], A["t2"][1], A["x"][0], A["x"][1], 0.002,
+                                                                              A["t3"][0], A["t3"][1], Ar[0], Ar[1], None, None)), reps=20)
+
+        def iht_singles():
+            for j in range(ig):
+                hip.check(lib.clm4_iht(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, vx[j][0].ptr, vx[j][1].ptr, inn, vy[j][0].ptr, vy[j][1].ptr,
+                                       vt1[j][0].ptr, vt1[j][1].ptr, vt2[j][0].ptr, vt2[j][1].ptr, vt3[j][0].ptr, vt3[j][1].ptr, iters, im // 4, 0.002, 1,
+                                       None, None))
+        rec_pair("iht_batch8_N8192", 2 * (im * inn // 2), ig, iht_singles,
+                 lambda: hip.check(lib.clm4_iht_batch(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, ig, A["x"][0], A["x"][1], inn, A["y"][0], A["y"][1],
+                                                      A["t1"][0], A["t1"][1], A["t2"][0], A["t2"][1], A["t3"][0], A["t3"][1], iters, im // 4, 0.002, 1,
+                                                      None, None)), reps=2, per=iters)
+        if "iht_batch8_N8192" in res:
+            res["iht_batch8_N8192"]["note"] = (f"ms per iteration for all 8 signals, calls of {iters} iterations, K = m / 4, FAST threshold; the single calls are "
+                                               "8 x clm4_iht as the library runs it (the persistent kernel at this size)")
+        del P, sP, PT, sPT, vy, vx, vt1, vt2, vt3, vr
+    if ONLY and all(any(o in r for r in BATCH_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
+
+
 # ---- vector ops at n = 2^30 (4 GiB fp32 source, 512 MiB + 64 MiB quantized) and n = 2^24
 for logn in (24, 30):
     n = 1 << logn
