@@ -95,11 +95,18 @@ static inline ClvRange clv_range(const void *p, uint64_t bytes, bool output, uin
 {
     return ClvRange{(uintptr_t)p, (uintptr_t)p + bytes, output, vec, name};
 }
-// mvm_batch4.hip: the launches of clm4_mvm_batch (qu == NULL) / clm4_mvm_scale_and_add_batch on CHECKED arguments, rounding disabled;
-// r / sr NULL: the mvm result is not stored (fused form only)
+// mvm_batch4.hip: the launches of clm4_mvm_batch (qu == NULL) / clm4_mvm_scale_and_add_batch on CHECKED arguments; r / sr NULL: the mvm
+// result is not stored (fused form only).  rng != NULL: stochastic, the groups in stream order from the state the call finds.
 int clv_internal_mvm_batch_run(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
                                const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
-                               float a, int8_t *const *r2, float *const *sr2, void *stream);
+                               float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, void *stream);
+// the same, ALWAYS on the batched kernel, with vector j's draws draw_base + j * draw_stride behind the state the call finds and the state
+// advanced by commit_draws at the end (0: left as it is); the positions have passed clv_internal_first_bad_window
+int clv_internal_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
+                              const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
+                              float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, uint64_t draw_base, uint64_t draw_stride,
+                              uint64_t commit_draws, void *stream);
+uint64_t clv_internal_first_bad_window(uint64_t nvec, uint64_t draw_base, uint64_t draw_stride, uint64_t window);
 int clv_internal_check_ranges(const char *fn, std::vector<ClvRange> &ranges);      // sorts `ranges`; CLV_OK or CLV_ERR_INVALID with the message set
 
 // ---- device helpers ---------------------------------------------------------------------------

@@ -107,15 +107,21 @@ extern "C" int clm4_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t
     // iteration and signal at N = 8192: against it the batched loop was measured for a full group of 8 only (64.2 us per iteration for 8 signals
     // against 75.5), so smaller groups of that class run as single calls (not measured: by the mvm rows a group of 2 would lose).
     // Elsewhere the single call is the launch-per-step loop with the same three launches per iteration per SIGNAL, and the batched mvm was
-    // faster at every group size.  CLV_MVM_BATCH (mvm_batch4.hip) = 1 / 0 forces one or the other.  With an rng: the stream order of the draws,
-    // all iterations of vector 0 first.
+    // faster at every group size.  CLV_MVM_BATCH (mvm_batch4.hip) = 1 / 0 forces one or the other.
+    // With an rng the same rule: the full group of 8 beat the stochastic persistent kernel too (80.2 us per iteration for 8 signals against
+    // 94.7, profiles/mvm_batch_st_kernel_bench.json), and the stochastic fused mvm was faster than the single launches at 2, 4 and 8 vectors
+    // (DESIGN.md 3).  The draws keep the order of the single calls, all iterations of vector 0 first: one iteration draws
+    // P = 4 (m / 64) + 4 (n / 64), so vector j of a group has its Phi window of iteration `it` at (j * iterations + it) * P and its PhiT
+    // window 4 (m / 64) further on; only the group's last launch commits, all g * iterations * P.
     const char *e = clv_env("CLV_MVM_BATCH");
     const int force = e && *e ? (atoi(e) != 0) : -1;
     const bool persistent_class = threshold <= 1 && iterations && m <= 8192 && n <= 8192 && clv_env_int("CLV_IHT_PERSISTENT", 1) != 0;
+    const uint64_t P = 4 * (m / 64) + 4 * (n / 64);
     hipStream_t st = as_stream(stream);
     for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
         const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        const bool batched = !rng_state_dev && g >= 2 && force != 0 && (force == 1 || !persistent_class || g == CLM4_MVM_BATCH_MAX);
+        bool batched = g >= 2 && force != 0 && (force == 1 || !persistent_class || g == CLM4_MVM_BATCH_MAX);
+        if (rng_state_dev && iterations > ((1ull << 55) - 1) / (g * P)) batched = false;      // positions beyond the jump-ahead tables
         if (!batched) {
             for (uint64_t j = j0; j < j0 + g; j++) {
                 int rc = clm4_iht(Phi, sPhi, PhiT, sPhiT, m, n, x[j], sx[j], x_len, y[j], sy[j], t1[j], st1[j], t2[j], st2[j], t3[j], st3[j], iterations, K,
@@ -127,10 +133,15 @@ extern "C" int clm4_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t
         for (uint64_t j = j0; j < j0 + g; j++)
             hipLaunchKernelGGL(k_v4_clear, dim3(64), dim3(256), 0, st, (uint32_t *)x[j], sx[j], n / 8, n / 64);   // x.clear()
         CLV_LAUNCH_CHECK();
+        const uint64_t stride = iterations * P;
         for (uint64_t it = 0; it < iterations; it++) {
             // t1 = Phi * x, t2 = y - t1;  t3 = Phi' * t2, x += mu * t3;  keep the K largest: three launches for the group
-            int rc = clv_internal_mvm_batch_run(Phi, sPhi, m, n, g, x + j0, sx + j0, t1 + j0, st1 + j0, y + j0, sy + j0, -1.0f, t2 + j0, st2 + j0, stream);
-            if (!rc) rc = clv_internal_mvm_batch_run(PhiT, sPhiT, n, m, g, t2 + j0, st2 + j0, t3 + j0, st3 + j0, x + j0, sx + j0, mu, x + j0, sx + j0, stream);
+            const uint64_t commit = it + 1 == iterations ? g * stride : 0;
+            int rc = clv_internal_mvm_batch_at(Phi, sPhi, m, n, g, x + j0, sx + j0, t1 + j0, st1 + j0, y + j0, sy + j0, -1.0f, t2 + j0, st2 + j0,
+                                               rng_state_dev, it * P, stride, 0, stream);
+            if (!rc)
+                rc = clv_internal_mvm_batch_at(PhiT, sPhiT, n, m, g, t2 + j0, st2 + j0, t3 + j0, st3 + j0, x + j0, sx + j0, mu, x + j0, sx + j0,
+                                               rng_state_dev, it * P + 4 * (m / 64), stride, commit, stream);
             if (!rc && threshold)
                 rc = clv4_threshold_batch(x + j0, sx + j0, g, x_len, n, K, threshold == 2 ? CLV_THRESHOLD_REFERENCE : CLV_THRESHOLD_FAST, stream);
             if (rc) return rc;

@@ -4,9 +4,11 @@
 // of many signals with one Phi) pays them once per vector.  Here a workgroup loads each 16 matrix bytes once and runs the chain
 // arithmetic of every vector of the group on them.  The chains of different vectors are independent and each vector's instruction
 // sequence is the one of mvm_device.h, so the results equal the single calls bit for bit.
+#include "rng_device.h"
 #include "mvm_device.h"
 
 #include <algorithm>
+#include <atomic>
 #include <stdlib.h>
 #include <string.h>
 
@@ -34,16 +36,76 @@ struct MvmBatchFuse {        // see MvmFuse
     float a;
 };
 
-#define MVMB_LDS_BYTES(NV) ((NV) * (MVMB_CHUNK / 2 + (MVMB_CHUNK / 64) * sizeof(float) + 64 * sizeof(float)))
+// ST: where the draws of the launch lie in the XORShift stream, counted in draws (one draw = one step of the 4-lane generator) from the
+// state the launch reads.  Slot v's window begins at draw_base + v * draw_stride: row group rb uses draws 2 rb, 2 rb + 1 of it for the mvm
+// and, with FUSE, 2 G + 2 rb, 2 G + 2 rb + 1 for the scaleAndAdd (G = row groups), as k_m4_mvm64 does from position 0.  commit_draws == 0:
+// the launch leaves the state as it is (no slot, no stamp written); otherwise workgroup 0 writes the state advanced by commit_draws.
+struct MvmBatchRng {
+    uint64_t *state;
+    uint64_t seq;
+    const uint64_t *pow_rows;
+    uint64_t draw_base, draw_stride, commit_draws;
+};
+
+#define MVMB_X_BYTES(NV) ((NV) * (MVMB_CHUNK / 2 + (MVMB_CHUNK / 64) * sizeof(float) + 64 * sizeof(float)))
+// ST: behind the row dots, per vector and window the start of each of the 4 generator lanes (32 B): 512 B at NV = 8 fused, 39 424 B in all
+#define MVMB_LDS_BYTES(NV, ST, FUSE) (MVMB_X_BYTES(NV) + ((ST) ? (NV) * ((FUSE) ? 2 : 1) * 4 * sizeof(uint64_t) : 0))
+
+// T^(e[i])(v0) for NE wave-uniform exponents at once (wave_pow_apply for one).  The rows of a table level are the same for every exponent:
+// one memory round trip per 8 bits of the LARGEST exponent serves all of them, and the NE chains of ballots are independent of each other,
+// so they overlap instead of queueing behind NE x (round trip + chain).  Powers of one matrix commute: any order of the levels.
+template <int NE>
+__device__ __forceinline__ void wave_pow_apply_many(const uint64_t *__restrict__ pow_rows, uint64_t v0, uint64_t *e, uint64_t *v)
+{
+    const uint64_t *row = pow_rows + (threadIdx.x & 63);
+    uint64_t any = 0;
+    v0 = uniform64(v0);
+#pragma unroll
+    for (int i = 0; i < NE; i++) {
+        e[i] = uniform64(e[i]);
+        v[i] = v0;
+        any |= e[i];
+    }
+    while (any) {
+        uint64_t R[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) R[k] = ((any >> k) & 1ull) ? row[64 * k] : 0ull;
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+#pragma unroll
+            for (int i = 0; i < NE; i++)
+                if ((e[i] >> k) & 1ull) v[i] = wave_matvec(R[k], v[i]);
+#pragma unroll
+        for (int i = 0; i < NE; i++) e[i] >>= 8;
+        any >>= 8;
+        row += 8 * 64;
+    }
+}
+
+// the noise of epilogue lane `lane` from the window whose four lane starts are base[0..3]: the window's two draws are generated in the
+// lane itself (gen_blocks on generator lane j >> 1; every lane of an AVX lane pair repeats them, which costs a wave nothing), then the
+// word and byte k_m4_mvm64 reads from its raw[]: group grp of AVX lane j is draw grp >> 2, dword j of the draw's eight, byte grp & 3
+__device__ __forceinline__ float mvmb_noise(const uint64_t *base, int grp, int j)
+{
+    uint64_t raw[8];
+    gen_blocks(base[j >> 1], 1, raw, 0);                       // raw[0], raw[4]: this generator lane's output of draw 0, draw 1
+    const uint64_t o = (grp >> 2) ? raw[4] : raw[0];
+    return noise_of((j & 1) ? (uint32_t)(o >> 32) : (uint32_t)o, grp & 3);
+}
 
 // Registers: the single-vector kernel runs four waves per SIMD (123 VGPRs, 36 KiB of LDS: four workgroups per CU), which is what hides
 // the HBM latency.  amdgpu_waves_per_eu(4, 4) holds every instantiation to the same 128 registers; U (matrix loads in flight per lane)
 // is chosen per NV so that they fit without scratch: MVMB_U below, figures in DESIGN.md 3.
 // Mapping of k_m4_mvm64: workgroup = one 64-row block, lane = (row rho = tid >> 2, quarter q = tid & 3) owning chains 4q..4q+3 of its row;
 // per vector 4 accumulators.  Vector v's epilogue (tree result -> re-quantise [-> scaleAndAdd]) runs on wave v & 3.
-template <int NV, int U, bool NT, bool FUSE>
+// ST (stochastic re-quantisation, the epilogue of k_m4_mvm64<., ., true, FUSE>): the jump-ahead runs in the PROLOGUE, before x is staged --
+// wave k owns generator lane k and applies T^e for every vector and window to the state it read, in one walk (NV = 8 fused: two) over the table
+// levels (wave_pow_apply_many: up to 16 exponents for NV = 8 fused, plus the committed state in workgroup 0), leaving the starts in LDS;
+// nothing of it lives in registers across the column loop.  Workgroup 0 stamps the committed state behind the last barrier.
+template <int NV, int U, bool NT, bool FUSE, bool ST>
 __global__ __launch_bounds__(MVMB_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_m4_mvm_batch(
-    const uint8_t *__restrict__ A, const float *__restrict__ sA, uint64_t cols, int nv, MvmBatchArgs<NV> arg, MvmBatchFuse<NV> fuse)
+    const uint8_t *__restrict__ A, const float *__restrict__ sA, uint64_t cols, int nv, MvmBatchArgs<NV> arg, MvmBatchFuse<NV> fuse,
+    MvmBatchRng rs)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr uint32_t XS = MVMB_CHUNK / 32, CS = MVMB_CHUNK / 64;          // per vector: u32x4 of x, factors
@@ -51,9 +113,43 @@ __global__ __launch_bounds__(MVMB_THREADS) __attribute__((amdgpu_waves_per_eu(4,
     float *cs = reinterpret_cast<float *>(smem + NV * (MVMB_CHUNK / 2));    // NV x MVMB_CHUNK / 64 factors c[b] = (sA[b] * 1/49) * sx[b]
     float *dsh = cs + NV * CS;                                              // NV x 64 row dots
     static_assert(XS == MVMB_THREADS && 2 * CS == MVMB_THREADS, "one u32x4 of x per thread and vector, one factor per thread of the first two waves");
+    constexpr int NW = FUSE ? 2 : 1;                                        // windows per vector: the mvm's draws, the scaleAndAdd's
+    uint64_t *sbase = reinterpret_cast<uint64_t *>(dsh + NV * 64);          // ST: [NV][NW][4] lane starts
 
     const uint64_t rb = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint64_t st_seq = 0;
+    uint64_t *st_next = nullptr;
+    if constexpr (ST) {
+        st_seq = rng_effective_seq(rs.state, rs.seq);
+        const int slot = rng_read_slot(rs.state, st_seq);
+        const uint64_t a0 = rs.state[slot * RNG_SLOT_WORDS + 4 + wave];
+        // exponent NV * NW: the committed state, workgroup 0 only (what rng_commit writes; the stamp follows the last barrier)
+        const bool commits = rs.commit_draws && rb == 0;
+        uint64_t e[NV * NW + 1], b[NV * NW + 1];
+#pragma unroll
+        for (int v = 0; v < NV; v++)
+#pragma unroll
+            for (int w = 0; w < NW; w++)
+                e[v * NW + w] = v < nv ? rs.draw_base + (uint64_t)v * rs.draw_stride + 2 * (rb + (uint64_t)w * gridDim.x) : 0;
+        e[NV * NW] = commits ? rs.commit_draws - 1 : 0;
+        // at most 9 exponents per walk: the values and exponents live in SGPR pairs, and 17 of each spill
+        constexpr int NE = NV * NW + 1, H = NE <= 9 ? NE : NE / 2;
+        wave_pow_apply_many<H>(rs.pow_rows, a0, e, b);
+        if constexpr (H < NE) wave_pow_apply_many<NE - H>(rs.pow_rows, a0, e + H, b + H);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < NV * NW; i++) sbase[i * 4 + wave] = b[i];      // read in the epilogue, barriers in between
+        }
+        if (commits) {
+            st_next = rs.state + (slot ^ 1) * RNG_SLOT_WORDS;
+            if (lane == 0) {
+                st_next[wave] = b[NV * NW];
+                st_next[4 + wave] = xs_T(b[NV * NW]);
+            }
+        }
+    }
+
     const int q = tid & 3, rho = tid >> 2;
     const uint64_t row = rb * 64 + rho;
     const u32x4 *Arow = reinterpret_cast<const u32x4 *>(A + row * (cols / 2));
@@ -126,17 +222,25 @@ __global__ __launch_bounds__(MVMB_THREADS) __attribute__((amdgpu_waves_per_eu(4,
             if (q == 0) dsh[v * 64 + rho] = dot;
         }
     __syncthreads();
+    if constexpr (ST) {
+        if (st_next && tid == 0) {                                           // every wave's part of the new state was written before the barrier
+            __threadfence();
+            st_next[RNG_STAMP_WORD] = st_seq;
+        }
+    }
 #pragma unroll
     for (int v = 0; v < NV; v++)
         if (v < nv && wave == (v & 3)) {
             uint32_t *r = arg.r[v];
-            float m;
-            const int qv = requantize_wave(dsh[v * 64 + lane], 0.0f, r ? r + rb * 8 : nullptr, r ? arg.sr[v] + rb : nullptr, &m);
+            float m, noise = 0.0f;
+            if constexpr (ST) noise = mvmb_noise(sbase + (v * NW) * 4, lane & 7, lane >> 3);
+            const int qv = requantize_wave(dsh[v * 64 + lane], noise, r ? r + rb * 8 : nullptr, r ? arg.sr[v] + rb : nullptr, &m);
             if (FUSE) {
                 const float su7 = div7(fuse_s[v >> 2]), sv7 = div7(m * fuse.a);
                 const float val = __builtin_fmaf((float)qv, sv7, (float)unpack1(fuse_w[v >> 2], lane & 7) * su7);
-                float m2;
-                requantize_wave(val, 0.0f, fuse.r2[v] + rb * 8, fuse.sr2[v] + rb, &m2);
+                float m2, noise2 = 0.0f;
+                if constexpr (ST) noise2 = mvmb_noise(sbase + (v * NW + 1) * 4, (lane & 7) ^ 1, lane >> 3);
+                requantize_wave(val, noise2, fuse.r2[v] + rb * 8, fuse.sr2[v] + rb, &m2);
             }
         }
 }
@@ -171,21 +275,33 @@ int clv_internal_check_ranges(const char *fn, std::vector<ClvRange> &ranges)
 // ---- dispatch ----------------------------------------------------------------------------------------------------------------
 // Whether a group of g vectors runs as one batched launch or as g single launches.  CLV_MVM_BATCH (read on every call, as
 // CLV_IHT_PERSISTENT: the tests and tools/kernel_bench.py flip it inside one process): 1 = always batched, 0 = never; unset = the rule
-// measured on the MI355X (profiles/mvm_batch_kernel_bench.json).
-static bool mvm_batch_selected(uint64_t rows, uint64_t cols, uint64_t g)
+// measured on the MI355X (profiles/mvm_batch_kernel_bench.json; stochastic: profiles/mvm_batch_st_kernel_bench.json).
+// With an rng, CLV_MVM_BATCH=1 also puts a remainder group of ONE vector (nvec = 9, 17, ...) on the batched kernel: a forced call then hands
+// the state from batched launch to batched launch throughout, which is what the tests of that hand-over need.
+static bool mvm_batch_selected(uint64_t rows, uint64_t cols, uint64_t g, bool stochastic)
 {
-    if (g < 2) return false;
+    if (g < 2 && !stochastic) return false;
     const char *e = clv_env("CLV_MVM_BATCH");
     if (e && *e) return atoi(e) != 0;
+    if (g < 2) return false;
     (void)rows;
     (void)cols;
     return true;
 }
 
+static std::atomic<uint64_t> g_mvm_batch_launches{0};
+extern "C" uint64_t clv_mvm_batch_launches(void) { return g_mvm_batch_launches.load(std::memory_order_relaxed); }
+
+// the draws of a batched launch on the host side: rng == NULL = rounding disabled
+struct MvmBatchDraws {
+    uint64_t *rng;
+    uint64_t base, stride, commit;
+};
+
 template <int NV>
 static int launch_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t g, const int8_t *const *x,
                             const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
-                            float a, int8_t *const *r2, float *const *sr2, hipStream_t st)
+                            float a, int8_t *const *r2, float *const *sr2, const MvmBatchDraws &dr, hipStream_t st)
 {
     MvmBatchArgs<NV> arg;
     MvmBatchFuse<NV> fuse;
@@ -201,44 +317,96 @@ static int launch_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uin
         fuse.sr2[v] = in && qu ? sr2[v] : nullptr;
     }
     fuse.a = a;
+    MvmBatchRng rs = {nullptr, 0, nullptr, 0, 0, 0};
+    if (dr.rng) {
+        RngTables T = {nullptr, nullptr, nullptr};
+        int rc = clv_rng_tables(&T);
+        if (rc) return rc;
+        // every launch takes a number of its own, committing or not: it is what picks the slot to read
+        rs = MvmBatchRng{dr.rng, clv_rng_seq_for(dr.rng, st), T.pow_rows, dr.base, dr.stride, dr.commit};
+    }
     const dim3 grid((unsigned)(rows / 64)), block(MVMB_THREADS);
-    const size_t lds = MVMB_LDS_BYTES(NV);
     // nontemporal loads by the rule of launch_mvm: once the matrix cannot live in the 256 MiB Infinity Cache
     const bool streaming = rows * (cols / 2) > (256ull << 20);
-#define MVMB_LAUNCH(NT, FUSE) \
-    hipLaunchKernelGGL((k_m4_mvm_batch<NV, MVMB_U(NV), NT, FUSE>), grid, block, lds, st, (const uint8_t *)A, sA, cols, (int)g, arg, fuse)
-    if (streaming) { if (qu) MVMB_LAUNCH(true, true); else MVMB_LAUNCH(true, false); }
-    else { if (qu) MVMB_LAUNCH(false, true); else MVMB_LAUNCH(false, false); }
+#define MVMB_LAUNCH(NT, FUSE, ST)                                                                                                       \
+    hipLaunchKernelGGL((k_m4_mvm_batch<NV, MVMB_U(NV), NT, FUSE, ST>), grid, block, MVMB_LDS_BYTES(NV, ST, FUSE), st, (const uint8_t *)A, sA, \
+                       cols, (int)g, arg, fuse, rs)
+#define MVMB_LAUNCH_R(NT, FUSE) do { if (dr.rng) MVMB_LAUNCH(NT, FUSE, true); else MVMB_LAUNCH(NT, FUSE, false); } while (0)
+    if (streaming) { if (qu) MVMB_LAUNCH_R(true, true); else MVMB_LAUNCH_R(true, false); }
+    else { if (qu) MVMB_LAUNCH_R(false, true); else MVMB_LAUNCH_R(false, false); }
+#undef MVMB_LAUNCH_R
 #undef MVMB_LAUNCH
     CLV_LAUNCH_CHECK();
+    g_mvm_batch_launches.fetch_add(1, std::memory_order_relaxed);
     return CLV_OK;
 }
 
+static int launch_group(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t j0, uint64_t g, const int8_t *const *x,
+                        const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su, float a,
+                        int8_t *const *r2, float *const *sr2, const MvmBatchDraws &dr, hipStream_t st)
+{
+#define MVMB_GROUP(NV) \
+    launch_mvm_batch<NV>(A, sA, rows, cols, g, x + j0, sx + j0, r ? r + j0 : nullptr, r ? sr + j0 : nullptr, qu ? qu + j0 : nullptr, \
+                         qu ? su + j0 : nullptr, a, qu ? r2 + j0 : nullptr, qu ? sr2 + j0 : nullptr, dr, st)
+    return g <= 2 ? MVMB_GROUP(2) : g <= 4 ? MVMB_GROUP(4) : MVMB_GROUP(8);
+#undef MVMB_GROUP
+}
+
 // the checked arguments of clm4_mvm_batch (qu == NULL) / clm4_mvm_scale_and_add_batch on the stream, group by group; r / sr NULL: the mvm
-// result is not stored (fused form only).  Also the two mvm steps of clm4_iht_batch (iht4.hip).
+// result is not stored (fused form only).  With an rng every group starts at the state the group before it left: a batched group's windows
+// lie 2 G (fused: 4 G) draws apart from position 0 and its launch commits all of them, a forwarded group's single calls advance the state
+// themselves -- so the two kinds mix freely.
 int clv_internal_mvm_batch_run(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
                                const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
-                               float a, int8_t *const *r2, float *const *sr2, void *stream)
+                               float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, void *stream)
 {
     hipStream_t st = as_stream(stream);
+    const uint64_t per_vector = (qu ? 4ull : 2ull) * (rows / 64);
     for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
         const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
         int rc = CLV_OK;
-        if (!mvm_batch_selected(rows, cols, g)) {
+        if (!mvm_batch_selected(rows, cols, g, rng != nullptr)) {
             for (uint64_t j = j0; j < j0 + g && !rc; j++)
                 rc = qu ? clm4_mvm_scale_and_add(A, sA, rows, cols, x[j], sx[j], qu[j], su[j], a, r ? r[j] : nullptr, r ? sr[j] : nullptr, r2[j],
-                                                 sr2[j], nullptr, stream)
-                        : clm4_mvm(A, sA, rows, cols, x[j], sx[j], r[j], sr[j], nullptr, stream);
+                                                 sr2[j], rng, stream)
+                        : clm4_mvm(A, sA, rows, cols, x[j], sx[j], r[j], sr[j], rng, stream);
         } else {
-#define MVMB_GROUP(NV) \
-    launch_mvm_batch<NV>(A, sA, rows, cols, g, x + j0, sx + j0, r ? r + j0 : nullptr, r ? sr + j0 : nullptr, qu ? qu + j0 : nullptr, \
-                         qu ? su + j0 : nullptr, a, qu ? r2 + j0 : nullptr, qu ? sr2 + j0 : nullptr, st)
-            rc = g <= 2 ? MVMB_GROUP(2) : g <= 4 ? MVMB_GROUP(4) : MVMB_GROUP(8);
-#undef MVMB_GROUP
+            rc = launch_group(A, sA, rows, cols, j0, g, x, sx, r, sr, qu, su, a, r2, sr2, MvmBatchDraws{rng, 0, per_vector, g * per_vector}, st);
         }
         if (rc) return rc;
     }
     return CLV_OK;
+}
+
+// The positioned form: vector j's window begins draw_base + j * draw_stride draws behind the state the call finds, across groups too;
+// only the last group's launch commits.  Always the batched kernel (a window that is not where a single call would draw cannot be
+// forwarded).  rng == NULL: the deterministic kernel, the positions unused.  The caller has checked the positions (clv_internal_first_bad_window).
+int clv_internal_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
+                              const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
+                              float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, uint64_t draw_base, uint64_t draw_stride,
+                              uint64_t commit_draws, void *stream)
+{
+    hipStream_t st = as_stream(stream);
+    for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
+        const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
+        const bool last = j0 + g == nvec;
+        int rc = launch_group(A, sA, rows, cols, j0, g, x, sx, r, sr, qu, su, a, r2, sr2,
+                              MvmBatchDraws{rng, draw_base + j0 * draw_stride, draw_stride, last ? commit_draws : 0}, st);
+        if (rc) return rc;
+    }
+    return CLV_OK;
+}
+
+// the first of nvec windows of `window` draws each that does not end at or below 2^55, the exponents wave_pow_apply has table levels
+// for; nvec if there is none
+uint64_t clv_internal_first_bad_window(uint64_t nvec, uint64_t draw_base, uint64_t draw_stride, uint64_t window)
+{
+    const unsigned __int128 lim = (unsigned __int128)1 << (RNG_POW_LEVELS - 1);
+    for (uint64_t j = 0; j < nvec; j++) {
+        if ((unsigned __int128)draw_base + (unsigned __int128)j * draw_stride + window > lim) return j;
+        if (!draw_stride) break;
+    }
+    return nvec;
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------------
@@ -288,11 +456,25 @@ extern "C" int clm4_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, u
     int rc = check_batch_args("clm4_mvm_batch", A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
     if (rc) return rc;
     if (!nvec || !rows) return CLV_OK;
-    if (rng_state_dev || nvec == 1) {          // the draws of vector j follow those of vector j - 1 in the stream: the single calls, in order
-        for (uint64_t j = 0; j < nvec && !rc; j++) rc = clm4_mvm(A, sA, rows, cols, x[j], sx[j], r[j], sr[j], rng_state_dev, stream);
-        return rc;
-    }
-    return clv_internal_mvm_batch_run(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr, stream);
+    if (nvec == 1) return clm4_mvm(A, sA, rows, cols, x[0], sx[0], r[0], sr[0], rng_state_dev, stream);
+    return clv_internal_mvm_batch_run(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr, rng_state_dev, stream);
+}
+
+extern "C" int clm4_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
+                                 const float *const *sx, int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, uint64_t draw_base,
+                                 uint64_t draw_stride, uint64_t commit_draws, void *stream)
+{
+    const char *fn = "clm4_mvm_batch_at";
+    int rc = check_batch_args(fn, A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
+    if (rc) return rc;
+    if (!rng_state_dev) return clm4_mvm_batch(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, stream);
+    CLV_REQUIRE(commit_draws < (1ull << (RNG_POW_LEVELS - 1)), "%s: commit_draws=%llu must stay below 2^55", fn, (unsigned long long)commit_draws);
+    const uint64_t bad = clv_internal_first_bad_window(nvec, draw_base, draw_stride, 2 * (rows / 64));
+    CLV_REQUIRE(bad == nvec, "%s: the draws of vector %llu (draw_base=%llu, draw_stride=%llu) do not stay below 2^55", fn, (unsigned long long)bad,
+                (unsigned long long)draw_base, (unsigned long long)draw_stride);
+    if (!nvec || !rows) return CLV_OK;
+    return clv_internal_mvm_batch_at(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr, rng_state_dev, draw_base,
+                                     draw_stride, commit_draws, stream);
 }
 
 extern "C" int clm4_mvm_scale_and_add_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
@@ -303,11 +485,8 @@ extern "C" int clm4_mvm_scale_and_add_batch(const int8_t *A, const float *sA, ui
     int rc = check_batch_args("clm4_mvm_scale_and_add_batch", A, sA, rows, cols, nvec, x, sx, qu, su, t, st_, r, sr, true);
     if (rc) return rc;
     if (!nvec || !rows) return CLV_OK;
-    if (rng_state_dev || nvec == 1) {
-        for (uint64_t j = 0; j < nvec && !rc; j++)
-            rc = clm4_mvm_scale_and_add(A, sA, rows, cols, x[j], sx[j], qu[j], su[j], a, t ? t[j] : nullptr, t ? st_[j] : nullptr, r[j], sr[j],
-                                        rng_state_dev, stream);
-        return rc;
-    }
-    return clv_internal_mvm_batch_run(A, sA, rows, cols, nvec, x, sx, t, st_, qu, su, a, r, sr, stream);
+    if (nvec == 1)
+        return clm4_mvm_scale_and_add(A, sA, rows, cols, x[0], sx[0], qu[0], su[0], a, t ? t[0] : nullptr, t ? st_[0] : nullptr, r[0], sr[0],
+                                      rng_state_dev, stream);
+    return clv_internal_mvm_batch_run(A, sA, rows, cols, nvec, x, sx, t, st_, qu, su, a, r, sr, rng_state_dev, stream);
 }

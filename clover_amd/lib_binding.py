@@ -118,6 +118,8 @@ SIGNATURES = {
                           C.c_float, C.c_int, _vp, _vp]),
     # the batch calls: pointer arrays are HOST arrays (ctypes arrays of c_void_p) of device pointers
     "clm4_mvm_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm4_mvm_batch_at": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp]),
+    "clv_mvm_batch_launches": (_u64, []),
     "clm4_mvm_scale_and_add_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     "clv4_threshold_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _u64, C.c_int, _vp]),
     "clm4_iht_batch": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,

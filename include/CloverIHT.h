@@ -80,9 +80,32 @@ inline void Q_GD(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 &x, Clov
 }
 
 
-/* Not in the reference: Q_IHT / Q_GD for `count` signals with ONE Phi (CloverMatrix4::iht_loop_batch -> clm4_iht_batch): per iteration two
- * passes over Phi / PhiT for every group of CLM4_MVM_BATCH_MAX signals instead of two per signal.  x[j], t1[j], t2[j], t3[j] end as
- * Q_IHT(Phi, PhiT, *x[j], *y[j], *t1[j], *t2[j], *t3[j], ...) leaves them, bit for bit; with stochastic rounding enabled that IS what runs. */
+/* Not in the reference: Q_IHT / Q_GD for `count` signals with ONE Phi: per iteration two passes over Phi / PhiT for every group of
+ * CLM4_MVM_BATCH_MAX signals instead of two per signal.  x[j], t1[j], t2[j], t3[j] end as
+ * Q_IHT(Phi, PhiT, *x[j], *y[j], *t1[j], *t2[j], *t3[j], ...) called for signal 0, then 1, ... leaves them, bit for bit, and so do the
+ * generators of Phi and PhiT.  Rounding disabled: CloverMatrix4::iht_loop_batch -> clm4_iht_batch.  Stochastic: in that order of calls Phi's
+ * generator serves all iterations of signal 0 first, 2 (m / 64) draws per mvm, so signal j's mvm of iteration `it` draws at
+ * (j * iterations + it) * 2 (m / 64) -- which is where CloverMatrix4::mvm_batch_at places it while the loop below runs iteration by
+ * iteration for all signals; the last iteration advances the generator by everything.  The scaleAndAdd steps draw from y[j]'s and x[j]'s
+ * own generators and stay single calls. */
+namespace clover_hip {
+inline void q_iht_batch_stochastic(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 *const *x, CloverVector4 *const *y, CloverVector4 *const *t1,
+                                   CloverVector4 *const *t2, CloverVector4 *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
+                                   const float mu, const bool with_threshold)
+{
+    for (uint64_t j = 0; j < count; j++) x[j]->clear();
+    const uint64_t dm = 2 * (Phi.getRows() >> 6), dn = 2 * (PhiT.getRows() >> 6);       /* draws of one mvm with Phi, with PhiT */
+    for (uint64_t it = 0; it < iterations; it++) {
+        const bool last = it + 1 == iterations;
+        Phi.mvm_batch_at(x, t1, count, it * dm, iterations * dm, last ? count * iterations * dm : 0);
+        for (uint64_t j = 0; j < count; j++) y[j]->scaleAndAdd_parallel(*t1[j], -1.0f, *t2[j]);
+        PhiT.mvm_batch_at(t2, t3, count, it * dn, iterations * dn, last ? count * iterations * dn : 0);
+        for (uint64_t j = 0; j < count; j++) x[j]->scaleAndAdd_parallel(*t3[j], mu);
+        if (with_threshold) CloverVector4::threshold_batch(x, count, K);
+    }
+}
+}
+
 inline void Q_IHT_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 *const *x, CloverVector4 *const *y, CloverVector4 *const *t1,
                         CloverVector4 *const *t2, CloverVector4 *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
                         const float mu)
@@ -90,7 +113,7 @@ inline void Q_IHT_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 *
 #ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
     Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, K, mu, true);
 #else
-    for (uint64_t j = 0; j < count; j++) Q_IHT(Phi, PhiT, *x[j], *y[j], *t1[j], *t2[j], *t3[j], iterations, K, mu);
+    clover_hip::q_iht_batch_stochastic(Phi, PhiT, x, y, t1, t2, t3, count, iterations, K, mu, true);
 #endif
 }
 
@@ -100,7 +123,7 @@ inline void Q_GD_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 *c
 #ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
     Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
 #else
-    for (uint64_t j = 0; j < count; j++) Q_GD(Phi, PhiT, *x[j], *y[j], *t1[j], *t2[j], *t3[j], iterations, mu);
+    clover_hip::q_iht_batch_stochastic(Phi, PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
 #endif
 }
 

@@ -105,6 +105,8 @@ public:
     void setRandomKeys(__m256i key1, __m256i key2) { clover_hip::set_keys_m256(random, key1, key2); }   /* CloverRandom.h:90-94 */
 #endif
     void seedRandomKeys(uint64_t key1, uint64_t key2) { random.seed(key1, key2); }
+    /* the keys as they stand now (clv_rng_get): what setRandomKeys would have to be given to continue the stream from here */
+    void getRandomKeys(uint64_t key1[4], uint64_t key2[4]) const { random.get(key1, key2); }
 
     void quantize(const CloverMatrix32 &m)
     {
@@ -190,10 +192,26 @@ public:
     }
     /* Not in the reference: this * x[j] for `count` vectors in ONE pass over the matrix per group of CLM4_MVM_BATCH_MAX (clm4_mvm_batch);
      * r[j] equals what mvm(*x[j], *r[j]) gives, bit for bit.  The x[j] may repeat; the r[j] are distinct vectors, none of them an x.
-     * With stochastic rounding enabled the calls draw from the matrix's generator one after another: the single calls, in order. */
+     * With stochastic rounding enabled the vectors draw from the matrix's generator one after another, as the single calls in order do --
+     * still one pass: the kernel jumps to every vector's place in the stream -- and the generator ends where those calls leave it. */
     void mvm_batch(const CloverVector4 *const *x, CloverVector4 *const *r, uint64_t count)
     {
-#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        mvm_batch_at(x, r, count, 0, 2 * (rows >> 6), count * 2 * (rows >> 6), false);
+    }
+    /* mvm_batch with the place of every vector's draws chosen by the caller (clm4_mvm_batch_at), counted in draws -- mvm consumes
+     * 2 (rows / 64) -- from where the matrix's generator stands: vector j draws from draw_base + j * draw_stride on, and the generator
+     * is advanced by commit_draws afterwards (0: left as it is).  For callers whose stream order is not vector after vector
+     * (Q_IHT_batch, CloverIHT.h).  With rounding disabled the three numbers are ignored. */
+    void mvm_batch_at(const CloverVector4 *const *x, CloverVector4 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
+                      uint64_t commit_draws)
+    {
+        mvm_batch_at(x, r, count, draw_base, draw_stride, commit_draws, true);
+    }
+
+private:
+    void mvm_batch_at(const CloverVector4 *const *x, CloverVector4 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
+                      uint64_t commit_draws, bool positioned)
+    {
         std::vector<const int8_t *> px(count);
         std::vector<const float *> psx(count);
         std::vector<int8_t *> pr(count);
@@ -207,14 +225,20 @@ public:
             psx[j] = x[j]->dev_scales_ro();
         }
         for (uint64_t j = 0; j < count; j++) { pr[j] = r[j]->dev_values_wo(); psr[j] = r[j]->dev_scales_wo(); }
-        clover_hip::check(clm4_mvm_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), nullptr, nullptr),
-                          "CloverMatrix4::mvm_batch");
+        uint64_t *rng = clover_hip::rng_or_null(random);
+        if (positioned)
+            clover_hip::check(clm4_mvm_batch_at(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng,
+                                                draw_base, draw_stride, commit_draws, nullptr), "CloverMatrix4::mvm_batch_at");
+        else      /* the launcher may forward groups to the single calls where those were measured faster */
+            clover_hip::check(clm4_mvm_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng, nullptr),
+                              "CloverMatrix4::mvm_batch");
         for (uint64_t j = 0; j < count; j++) r[j]->commit();
-#else
-        for (uint64_t j = 0; j < count; j++) mvm(*x[j], *r[j]);
-#endif
     }
-    /* mvm_scaleAndAdd for `count` vectors (clm4_mvm_scale_and_add_batch): t[j] = this * x[j], r[j] = quantize(u[j] + a * t[j]) */
+
+public:
+    /* mvm_scaleAndAdd for `count` vectors: t[j] = this * x[j], r[j] = quantize(u[j] + a * t[j]).  Rounding disabled: one launch per group
+     * (clm4_mvm_scale_and_add_batch).  Stochastic: the mvm draws from the matrix's generator and every scaleAndAdd from its u[j]'s own, so
+     * it is one mvm_batch and the scaleAndAdd calls -- the bits of the loop of mvm_scaleAndAdd, the matrix read once per group. */
     void mvm_scaleAndAdd_batch(const CloverVector4 *const *x, const CloverVector4 *const *u, float a, CloverVector4 *const *t, CloverVector4 *const *r,
                                uint64_t count)
     {
@@ -242,7 +266,9 @@ public:
                           "CloverMatrix4::mvm_scaleAndAdd_batch");
         for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
 #else
-        for (uint64_t j = 0; j < count; j++) mvm_scaleAndAdd(*x[j], *u[j], a, *t[j], *r[j]);
+        for (uint64_t j = 0; j < count; j++) check_fused(*x[j], *u[j], *t[j]);
+        mvm_batch(x, t, count);
+        for (uint64_t j = 0; j < count; j++) const_cast<CloverVector4 *>(u[j])->scaleAndAdd(*t[j], a, *r[j]);
 #endif
     }
     /* in place: u[j] = quantize(u[j] + a * (this * x[j])) */
@@ -269,7 +295,9 @@ public:
                           "CloverMatrix4::mvm_scaleAndAdd_batch");
         for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
 #else
-        for (uint64_t j = 0; j < count; j++) mvm_scaleAndAdd(*x[j], *u[j], a, *t[j]);
+        for (uint64_t j = 0; j < count; j++) check_fused(*x[j], *u[j], *t[j]);
+        mvm_batch(x, t, count);
+        for (uint64_t j = 0; j < count; j++) u[j]->scaleAndAdd(*t[j], a);
 #endif
     }
     /* iht_loop for `count` signals with this matrix as Phi (clm4_iht_batch): per iteration every step runs once for a group of signals;

@@ -433,12 +433,15 @@ int  clm4_iht(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const fl
  *  - nvec may be any number: groups of at most CLM4_MVM_BATCH_MAX vectors run one matrix pass each; nvec == 1 forwards to the single
  *    call; nvec == 0 or rows == 0 returns CLV_OK and does nothing.  The launcher takes the batched kernel only where it was measured
  *    faster than the single launches and forwards to them elsewhere: same bits either way.
- *  - rng_state_dev != NULL: the call RUNS AS THE SEQUENCE OF SINGLE CALLS -- vector j's draws follow vector j - 1's in the stream, and
- *    for clm4_iht_batch that is all iterations of vector 0 first.  The stream order of the draws allows nothing else; it is not a
- *    defect.  The rules for stochastic calls above apply.
+ *  - rng_state_dev != NULL: the same one pass per group, with the draws where the sequence of single calls has them.  Vector j's draws
+ *    follow vector j - 1's in the stream (clm4_mvm draws 2 (rows/64), clm4_mvm_scale_and_add 4 (rows/64)); XORShift128+ is linear, so every
+ *    workgroup of the batched kernel jumps from the state the launch finds to each vector's position itself, and the launch leaves the
+ *    state advanced by all of them.  Groups that run batched and groups that forward to single calls mix within one call.  For
+ *    clm4_iht_batch the order is all iterations of vector 0 first: a batched group places vector j's iteration `it` accordingly and
+ *    only its last launch advances the state.  The rules for stochastic calls above apply (graph capture: clv_rng_graph_mode).
  *  - clv4_threshold_batch: FAST with n_pad <= 131072 (the one-workgroup kernel) is ONE launch, workgroup j thresholding vector j;
  *    REFERENCE mode and larger vectors run as the sequence of single calls (and use the stream's scratch as those do).
- *  - clm4_iht_batch without an rng: every x[j] cleared, then per iteration and group two clm4_mvm_scale_and_add_batch launches and,
+ *  - clm4_iht_batch: every x[j] cleared, then per iteration and group two clm4_mvm_scale_and_add_batch launches and,
  *    if threshold != 0, one clv4_threshold_batch (threshold, x_len, K, mu as clm4_iht).  Where a single clm4_iht takes the persistent
  *    kernel (m, n <= 8192, threshold FAST or none) only full groups of CLM4_MVM_BATCH_MAX run this way -- the one group size at which it
  *    was measured faster than that kernel -- and a smaller group runs as single calls; those do not capture into a hipGraph (clm4_iht).
@@ -452,6 +455,23 @@ int  clm4_iht(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const fl
 int  clm4_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
                     const int8_t *const *x, const float *const *sx, int8_t *const *r, float *const *sr,
                     uint64_t *rng_state_dev, void *stream);
+/* clm4_mvm_batch with the position of every vector's draws chosen by the caller, counted in draws (one draw = one step of the 4-lane
+ * generator, what clm4_mvm consumes two of per 64 rows) from the state the call finds: vector j re-quantises with the 2 (rows/64) draws
+ * that begin at draw_base + j * draw_stride -- across the groups of CLM4_MVM_BATCH_MAX too -- exactly as clm4_mvm would with the state
+ * advanced that far.  Afterwards the state is advanced by commit_draws, or untouched when commit_draws == 0.  Any stride is legal, 0
+ * included (every vector uses the same draws); (0, 2 (rows/64), nvec * 2 (rows/64)) is clm4_mvm_batch.  It is what a caller needs whose
+ * stream order is not "vector after vector": the IHT loop over several signals (include/CloverIHT.h).
+ * With an rng this call ALWAYS runs the batched kernel, for nvec == 1 and under CLV_MVM_BATCH=0 too: a window that is not where the next
+ * single call would draw cannot be forwarded to single calls.  rng_state_dev == NULL: the three position numbers are ignored, the call is
+ * clm4_mvm_batch.  Checks as clm4_mvm_batch; in addition every position (the end of every vector's window) and commit_draws must stay
+ * below 2^55, else CLV_ERR_INVALID before any device work. */
+int  clm4_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
+                    const int8_t *const *x, const float *const *sx, int8_t *const *r, float *const *sr,
+                    uint64_t *rng_state_dev, uint64_t draw_base, uint64_t draw_stride, uint64_t commit_draws, void *stream);
+/* diagnostic: the number of batched-kernel launches (one matrix pass for a group of vectors, either rounding) this process has enqueued --
+ * the counterpart of clv_iht_persistent_launches: what a test or a benchmark reads to know that the one-pass kernel ran, not the forwarding
+ * to single calls. */
+uint64_t clv_mvm_batch_launches(void);
 int  clm4_mvm_scale_and_add_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
                     const int8_t *const *x, const float *const *sx, const int8_t *const *qu, const float *const *su, float a,
                     int8_t *const *t, float *const *st,      /* both arrays NULL: t is not stored */

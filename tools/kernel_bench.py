@@ -122,9 +122,12 @@ if any(selected(r) for r in GEMM_ROWS):
 
 # ---- several vectors with one CloverMatrix4 (mvm_batch4.hip): every row pairs the batch call, on the batched kernel (CLV_MVM_BATCH=1),
 # with the same vectors issued as single calls in the same session.  A run that names only these rows (KB_ONLY=mvm_batch,mvm_saa_batch,
-# iht_batch) ends after them.
+# iht_batch) ends after them.  The *_st_* rows are the same pairs with a generator (stochastic rounding): the batch call on the stochastic
+# batched kernel against the g single stochastic calls, same session, same vectors, one state (KB_ONLY=_st_ runs only them).
 BATCH_ROWS = ("mvm_batch2_32768^2", "mvm_batch4_32768^2", "mvm_batch8_32768^2", "mvm_batch2_65536^2", "mvm_batch4_65536^2", "mvm_batch8_65536^2",
               "mvm_saa_batch2_8192x4096", "mvm_saa_batch4_8192x4096", "mvm_saa_batch8_8192x4096", "iht_batch8_N8192")
+IHT_SHAPE_ROWS = BATCH_ROWS[6:] + tuple(r.replace("batch2_", "batch2_st_").replace("batch4_", "batch4_st_").replace("batch8_", "batch8_st_") for r in BATCH_ROWS[6:])
+BATCH_ROWS = BATCH_ROWS + tuple(r.replace("batch2_", "batch2_st_").replace("batch4_", "batch4_st_").replace("batch8_", "batch8_st_") for r in BATCH_ROWS)
 
 
 def rounds_of(fn, reps=10, rounds=5, warm=2):
@@ -182,7 +185,7 @@ def vec_set(count, n, seed):
 
 if any(selected(r) for r in BATCH_ROWS):
     for nb in (32768, 65536):
-        if not any(selected(f"mvm_batch{g}_{nb}^2") for g in (2, 4, 8)):
+        if not any(selected(f"mvm_batch{g}_{t}{nb}^2") for g in (2, 4, 8) for t in ("", "st_")):
             continue
         bA, bsA = hip.alloc(nb * nb // 2), hip.alloc((nb // 64) ** 2 * 4)
         hip.check(lib.clv_fill_random_nibbles(bA.ptr, bA.nbytes, 41, 0, None))
@@ -198,10 +201,18 @@ if any(selected(r) for r in BATCH_ROWS):
             rec_pair(f"mvm_batch{g}_{nb}^2", one_b, g, singles,
                      lambda g=g, a=(ax, asx, ar, asr): hip.check(lib.clm4_mvm_batch(bA.ptr, bsA.ptr, nb, nb, g, a[0], a[1], a[2], a[3], None, None)),
                      reps=10 if nb == 32768 else 4)
+            st = hip.new_rng(1, 2)
+
+            def singles_st(g=g, st=st):
+                for j in range(g):
+                    hip.check(lib.clm4_mvm(bA.ptr, bsA.ptr, nb, nb, bx[j][0].ptr, bx[j][1].ptr, br[j][0].ptr, br[j][1].ptr, st.ptr, None))
+            rec_pair(f"mvm_batch{g}_st_{nb}^2", one_b, g, singles_st,
+                     lambda g=g, a=(ax, asx, ar, asr), st=st: hip.check(lib.clm4_mvm_batch(bA.ptr, bsA.ptr, nb, nb, g, a[0], a[1], a[2], a[3], st.ptr, None)),
+                     reps=10 if nb == 32768 else 4)
         del bA, bsA, bx, br
     # the IHT shape (N = 8192: Phi 4096 x 8192, cache-resident): the x += mu Phi' t2 step for 8 signals, and the whole loop
     im, inn, ig, iters = 4096, 8192, 8, 20
-    if any(selected(r) for r in BATCH_ROWS[6:]):
+    if any(selected(r) for r in IHT_SHAPE_ROWS):
         P, sP, PT, sPT = hip.alloc(im * inn // 2), hip.alloc(4 * (im // 64) * (inn // 64)), hip.alloc(im * inn // 2), hip.alloc(4 * (im // 64) * (inn // 64))
         hip.check(lib.clv_fill_random_nibbles(P.ptr, P.nbytes, 51, 0, None))
         hip.check(lib.clv_fill_random_scales(sP.ptr, sP.nbytes // 4, 52, 0, None))
@@ -220,6 +231,15 @@ if any(selected(r) for r in BATCH_ROWS):
             rec_pair(f"mvm_saa_batch{sg}_8192x4096", saa_b, sg, saa_singles,
                      lambda sg=sg: hip.check(lib.clm4_mvm_scale_and_add_batch(PT.ptr, sPT.ptr, inn, im, sg, A["t2"][0], A["t2"][1], A["x"][0], A["x"][1], 0.002,
                                                                               A["t3"][0], A["t3"][1], Ar[0], Ar[1], None, None)), reps=20)
+            st = hip.new_rng(1, 2)
+
+            def saa_singles_st(sg=sg, st=st):
+                for j in range(sg):
+                    hip.check(lib.clm4_mvm_scale_and_add(PT.ptr, sPT.ptr, inn, im, vt2[j][0].ptr, vt2[j][1].ptr, vx[j][0].ptr, vx[j][1].ptr, 0.002,
+                                                         vt3[j][0].ptr, vt3[j][1].ptr, vr[j][0].ptr, vr[j][1].ptr, st.ptr, None))
+            rec_pair(f"mvm_saa_batch{sg}_st_8192x4096", saa_b, sg, saa_singles_st,
+                     lambda sg=sg, st=st: hip.check(lib.clm4_mvm_scale_and_add_batch(PT.ptr, sPT.ptr, inn, im, sg, A["t2"][0], A["t2"][1], A["x"][0], A["x"][1],
+                                                                                     0.002, A["t3"][0], A["t3"][1], Ar[0], Ar[1], st.ptr, None)), reps=20)
 
         def iht_singles():
             for j in range(ig):
@@ -233,6 +253,20 @@ if any(selected(r) for r in BATCH_ROWS):
         if "iht_batch8_N8192" in res:
             res["iht_batch8_N8192"]["note"] = (f"ms per iteration for all 8 signals, calls of {iters} iterations, K = m / 4, FAST threshold; the single calls are "
                                                "8 x clm4_iht as the library runs it (the persistent kernel at this size)")
+        ist = hip.new_rng(1, 2)
+
+        def iht_singles_st():
+            for j in range(ig):
+                hip.check(lib.clm4_iht(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, vx[j][0].ptr, vx[j][1].ptr, inn, vy[j][0].ptr, vy[j][1].ptr,
+                                       vt1[j][0].ptr, vt1[j][1].ptr, vt2[j][0].ptr, vt2[j][1].ptr, vt3[j][0].ptr, vt3[j][1].ptr, iters, im // 4, 0.002, 1,
+                                       ist.ptr, None))
+        rec_pair("iht_batch8_st_N8192", 2 * (im * inn // 2), ig, iht_singles_st,
+                 lambda: hip.check(lib.clm4_iht_batch(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, ig, A["x"][0], A["x"][1], inn, A["y"][0], A["y"][1],
+                                                      A["t1"][0], A["t1"][1], A["t2"][0], A["t2"][1], A["t3"][0], A["t3"][1], iters, im // 4, 0.002, 1,
+                                                      ist.ptr, None)), reps=2, per=iters)
+        if "iht_batch8_st_N8192" in res:
+            res["iht_batch8_st_N8192"]["note"] = (f"ms per iteration for all 8 signals, calls of {iters} iterations, K = m / 4, FAST threshold, one generator; the "
+                                                  "single calls are 8 x clm4_iht with that generator as the library runs it (the stochastic persistent kernel)")
         del P, sP, PT, sPT, vy, vx, vt1, vt2, vt3, vr
     if ONLY and all(any(o in r for r in BATCH_ROWS) for o in ONLY.split(",")):
         print(json.dumps(res, indent=1))
