@@ -33,9 +33,8 @@ __device__ __forceinline__ void saa_values(uint32_t wu, uint32_t wv, float su7, 
 // iteration, all 2 U loads requested before the first value is computed.  Round 5 measured U = 1 / 2 / 4 on one box at n = 2^30
 // (tools/build_variant.py, profiles/r05_weak_kernels_ab.txt): 0.3442 / 0.3430 / 0.3377 ms -- the loads in flight are not what bounds
 // this 2-reads-1-write stream (5.3 TB/s, in family with the chip's copy-shaped kernels), so the plain U = 1 form stays.
-#ifndef SAA_U
-#define SAA_U 1
-#endif
+// Since the block kernel below took over from n = 2^18, this one only runs on vectors far inside the Infinity Cache: <false, 1> is its
+// one instantiation (the template parameters stay for the kernel's symbol name).
 template <bool NT, int U>
 __global__ __launch_bounds__(256) void k_v4_scale_and_add(const u32x4 *qu, const float *su, const u32x4 *qv,
                                                           const float *sv, float a, u32x4 *r, float *sr,
@@ -436,12 +435,9 @@ extern "C" int clv4_scale_and_add(const int8_t *qu, const float *su, const int8_
         const uint64_t nquads = nwords / 4;
         const uint64_t want = (nquads + 255) / 256, cap = (uint64_t)clv_cu_count() * 8;
         const dim3 grid((unsigned)(want < cap ? want : cap));
-        if (3 * (n_pad / 2) > (256ull << 20))           // operands + result exceed the Infinity Cache: stream past it
-            hipLaunchKernelGGL((k_v4_scale_and_add<true, SAA_U>), grid, dim3(256), 0, st, (const u32x4 *)qu, su, (const u32x4 *)qv, sv, a,
-                               (u32x4 *)r, sr, nquads);
-        else
-            hipLaunchKernelGGL((k_v4_scale_and_add<false, 1>), grid, dim3(256), 0, st, (const u32x4 *)qu, su, (const u32x4 *)qv, sv, a,
-                               (u32x4 *)r, sr, nquads);
+        // n_pad < 2^18 here: 3 n_pad / 2 bytes are far below the 256 MiB of the streaming rule, so there is no nontemporal form
+        hipLaunchKernelGGL((k_v4_scale_and_add<false, 1>), grid, dim3(256), 0, st, (const u32x4 *)qu, su, (const u32x4 *)qv, sv, a, (u32x4 *)r, sr,
+                           nquads);
         CLV_LAUNCH_CHECK();
         return CLV_OK;
     }
