@@ -106,6 +106,14 @@ int clv_internal_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, u
                               const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
                               float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, uint64_t draw_base, uint64_t draw_stride,
                               uint64_t commit_draws, void *stream);
+// mvm_batch8.hip: the same for CloverVector8 vectors (clm4_mvm_v8_batch_at / the fused form), always on the batched kernel
+int clv_internal_mvm_v8_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
+                                 const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
+                                 float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, uint64_t draw_base, uint64_t draw_stride,
+                                 uint64_t commit_draws, void *stream);
+void clv_internal_mvm_batch_count(void);      // mvm_batch4.hip: one more batched launch, of either vector type (clv_mvm_batch_launches)
+// iht_persist.hip: whether a single clm4_iht_v8 with these arguments takes the persistent kernel k_iht8_persist
+bool clm4_iht_v8_persistent_eligible(uint64_t m, uint64_t n, uint64_t iterations, int threshold, bool stochastic);
 uint64_t clv_internal_first_bad_window(uint64_t nvec, uint64_t draw_base, uint64_t draw_stride, uint64_t window);
 int clv_internal_check_ranges(const char *fn, std::vector<ClvRange> &ranges);      // sorts `ranges`; CLV_OK or CLV_ERR_INVALID with the message set
 

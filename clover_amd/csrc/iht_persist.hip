@@ -1302,28 +1302,48 @@ int clm4_iht_persistent(const int8_t *Phi, const float *sPhi, const int8_t *PhiT
     return 1;
 }
 
+// Whether a single clm4_iht_v8 takes k_iht8_persist: CLV_IHT_PERSISTENT (read per call), the loop's limits and what the layout needs of the
+// device.  `shape` (optional) receives the row counts per workgroup, the LDS layout and the grid.  clm4_iht_v8_batch asks it too.
+struct Ihtp8Shape {
+    uint32_t R1, R2, grid;
+    Ihtp8Layout L;
+};
+static bool ihtp8_eligible(uint64_t m, uint64_t n, uint64_t iterations, int threshold, bool stochastic, Ihtp8Shape *shape)
+{
+    const int mode = (int)clv_env_int("CLV_IHT_PERSISTENT", 1);
+    if (!mode || threshold < 0 || threshold > 1 || !iterations || iterations >= 0x7FFFFFFFull) return false;
+    if (stochastic && (m + n) / 64 * 4 < 32) return false;
+    if (m > IHTP_MAXLEN || n > IHTP_MAXLEN || m % 128 || n % 128 || !m || !n) return false;
+    const int cus = clv_cu_count();
+    uint32_t R1 = pow2_ceil((uint32_t)((m + cus - 1) / cus)), R2 = pow2_ceil((uint32_t)((n + cus - 1) / cus));
+    if (R1 < 16) R1 = 16;
+    if (R2 < 16) R2 = 16;
+    if (R1 > 64 || R2 > 64) return false;
+    const Ihtp8Layout L = ihtp8_layout((uint32_t)m, (uint32_t)n, R1, R2);
+    if (L.total > 160u * 1024u) return false;
+    if (L.GB1 * R1 > 512u || L.GB2 * R2 > 512u) return false;               // the row dots deal a chain over 128 / R lanes, 4 groups each at most
+    // stochastic: the raw draws overlay LDS regions that are dead while they are needed (ihtp8_layout); a shape whose draws do not fit there
+    // (the first phase's where m > 0.75 n: gradient descent's 1.5 : 1 systems) runs the launch-per-step loop
+    if (stochastic && (L.raw1_bytes > L.raw1_room || L.raw2_bytes > L.raw2_room)) return false;
+    const uint32_t grid = (uint32_t)((m / R1 > n / R2) ? m / R1 : n / R2);
+    if ((int)grid > cus) return false;
+    if (shape) *shape = Ihtp8Shape{R1, R2, grid, L};
+    return true;
+}
+bool clm4_iht_v8_persistent_eligible(uint64_t m, uint64_t n, uint64_t iterations, int threshold, bool stochastic)
+{
+    return ihtp8_eligible(m, n, iterations, threshold, stochastic, nullptr);
+}
+
 // the CloverVector8 loop (clm4_iht_v8): 1 = launched, 0 = does not qualify, < 0 = error
 int clm4_iht_v8_persistent(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, int8_t *x, float *sx,
                            uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3, float *st3,
                            uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng, hipStream_t st)
 {
-    const int mode = (int)clv_env_int("CLV_IHT_PERSISTENT", 1);
-    if (!mode || threshold < 0 || threshold > 1 || !iterations || iterations >= 0x7FFFFFFFull) return 0;
-    if (rng && (m + n) / 64 * 4 < 32) return 0;
-    if (m > IHTP_MAXLEN || n > IHTP_MAXLEN || m % 128 || n % 128 || !m || !n) return 0;
-    const int cus = clv_cu_count();
-    uint32_t R1 = pow2_ceil((uint32_t)((m + cus - 1) / cus)), R2 = pow2_ceil((uint32_t)((n + cus - 1) / cus));
-    if (R1 < 16) R1 = 16;
-    if (R2 < 16) R2 = 16;
-    if (R1 > 64 || R2 > 64) return 0;
-    const Ihtp8Layout L = ihtp8_layout((uint32_t)m, (uint32_t)n, R1, R2);
-    if (L.total > 160u * 1024u) return 0;
-    if (L.GB1 * R1 > 512u || L.GB2 * R2 > 512u) return 0;               // the row dots deal a chain over 128 / R lanes, 4 groups each at most
-    // stochastic: the raw draws overlay LDS regions that are dead while they are needed (ihtp8_layout); a shape whose draws do not fit there
-    // (the first phase's where m > 0.75 n: gradient descent's 1.5 : 1 systems) runs the launch-per-step loop
-    if (rng && (L.raw1_bytes > L.raw1_room || L.raw2_bytes > L.raw2_room)) return 0;
-    const uint32_t grid = (uint32_t)((m / R1 > n / R2) ? m / R1 : n / R2);
-    if ((int)grid > cus) return 0;
+    Ihtp8Shape shape;
+    if (!ihtp8_eligible(m, n, iterations, threshold, rng != nullptr, &shape)) return 0;
+    const uint32_t R1 = shape.R1, R2 = shape.R2, grid = shape.grid;
+    const Ihtp8Layout L = shape.L;
     static std::mutex attr_mutex;
     static bool attr_set[64];
     int dev = 0;

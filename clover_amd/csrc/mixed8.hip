@@ -3,6 +3,7 @@
 // 64 elements, value = q * scale / 127.  Here: its quantize / restore and CloverMatrix4::mvm(CloverVector8, CloverVector8)
 // (CloverMatrix4.h:1093-1441), bit-exact in the reference's SIMD order.
 #include "rng_device.h"
+#include "mvm8_device.h"
 
 #include <stdlib.h>
 
@@ -364,39 +365,8 @@ __global__ __launch_bounds__(256) void k_v8_scale_and_add_st(const u32x4 *qu, co
 // =================================================================================================
 #define MVM8_CHUNK 32768u
 
-// 8 nibbles of a dword (elements e0..e7) -> int8 dwords {e0..e3} and {e4..e7}, each value times 16
-__device__ __forceinline__ void widen8(uint32_t w, uint32_t &d03, uint32_t &d47)
-{
-    const uint32_t lo = w & 0xF0F0F0F0u;                 // bytes [e0, e2, e4, e6] * 16
-    const uint32_t hi = (w << 4) & 0xF0F0F0F0u;          // bytes [e1, e3, e5, e7] * 16
-    d03 = __builtin_amdgcn_perm(hi, lo, 0x05010400u);    // [lo.b0, hi.b0, lo.b1, hi.b1]
-    d47 = __builtin_amdgcn_perm(hi, lo, 0x07030602u);    // [lo.b2, hi.b2, lo.b3, hi.b3]
-}
-
-__device__ __forceinline__ int sdot4(uint32_t a, uint32_t b, int c) { return __builtin_amdgcn_sdot4((int)a, (int)b, c, false); }
-
-// one block (64 columns) for lane m: w_first = word m, w_second = word 4+m of the block, xb = the block's 64 int8 in LDS
-__device__ __forceinline__ void mvm8_block(uint32_t w_first, uint32_t w_second, const u32x2 *xb, int m, float c, float &a_even, float &a_odd)
-{
-    uint32_t f03, f47, s03, s47;
-    widen8(w_first, f03, f47);
-    widen8(w_second, s03, s47);
-    const u32x2 x0 = xb[m], x1 = xb[4 + m];          // elements 8m..8m+7 and 32+8m..32+8m+7
-    const int ie = sdot4(s03, x1.x, sdot4(f03, x0.x, 0)) >> 4;      // chain 2m   (exact: the sum is a multiple of 16)
-    const int io = sdot4(s47, x1.y, sdot4(f47, x0.y, 0)) >> 4;      // chain 2m+1
-    a_even = __builtin_fmaf(c, (float)ie, a_even);
-    a_odd = __builtin_fmaf(c, (float)io, a_odd);
-}
-
-// FUSE: the CloverVector8::scaleAndAdd that follows this mvm in the IHT / GD loops, done on the row group while it is still in
-// the wave: r2 = quantize8(u + a * quantize8(A x)); its draws follow ALL the mvm draws in the stream, as in two separate calls.
-struct Mvm8Fuse {
-    const int8_t *qu;        // u, one 64-element block per row group
-    const float *su;
-    float a;
-    int8_t *r2;              // may alias qu (the in-place overload)
-    float *sr2;
-};
+// widen8, sdot4, mvm8_block (= mvm8_widen + mvm8_dot), mvm8_tree, Mvm8Fuse and the re-quantisation of a row group: mvm8_device.h, shared
+// with the batched kernel (mvm_batch8.hip)
 
 // LDS tail shared by the two mvm kernels: 64 row dots, then the generator bases and raw draws (ST)
 struct Mvm8Tail {
@@ -439,29 +409,15 @@ __device__ __forceinline__ void mvm8_epilogue(const Mvm8Tail &t, uint64_t rb, in
     }
     __syncthreads();
     if ((r || FUSE) && tid < 64) {
-        const float d = t.dsh[tid];
-        float noise = 0.0f;
+        float noise = 0.0f, noise2 = 0.0f;
         if (ST) {
             const int g = tid >> 3, j = tid & 7;
             noise = noise_of(reinterpret_cast<const uint32_t *>(t.raw + (size_t)(g >> 2) * 4)[j], g & 3);
+            // the scaleAndAdd's element l: draw l>>5, byte l&3, word (l&31)>>2
+            if (FUSE) noise2 = noise_of(reinterpret_cast<const uint32_t *>(t.raw2 + (size_t)(tid >> 5) * 4)[(tid & 31) >> 2], tid & 3);
         }
-        float mx = wave_max(__builtin_fabsf(d));
-        mx = fix_zero_max(mx);
-        const int qv = quant1(d, 127.0f / mx, noise);
-        if (r) {
-            r[rb * 64 + tid] = (int8_t)qv;
-            if (tid == 0) sr[rb] = mx;
-        }
-        if (FUSE) {
-            // CloverVector8::scaleAndAdd on this block (CloverVector8.h:1089-1358); element l: draw l>>5, byte l&3, word (l&31)>>2
-            const float val = __builtin_fmaf((float)qv, div127(mx * fuse.a), (float)fuse_q * div127(fuse_s));
-            float noise2 = 0.0f;
-            if (ST) noise2 = noise_of(reinterpret_cast<const uint32_t *>(t.raw2 + (size_t)(tid >> 5) * 4)[(tid & 31) >> 2], tid & 3);
-            float m2 = wave_max(__builtin_fabsf(val));
-            m2 = fix_zero_max(m2);
-            fuse.r2[rb * 64 + tid] = (int8_t)quant1(val, 127.0f / m2, noise2);
-            if (tid == 0) fuse.sr2[rb] = m2;
-        }
+        mvm8_requantize_wave<FUSE>(t.dsh[tid], noise, noise2, tid, r ? r + rb * 64 : nullptr, r ? sr + rb : nullptr, fuse_q, fuse_s, fuse.a,
+                                   FUSE ? fuse.r2 + rb * 64 : nullptr, FUSE ? fuse.sr2 + rb : nullptr);
     }
 }
 
@@ -518,7 +474,7 @@ __global__ __launch_bounds__(256, MVM8_MIN_WAVES) void k_m4_mvm8(const uint8_t *
 #pragma unroll
             for (int k = 0; k < NC; k++) {
                 const uint32_t i = tid + 256 * k;
-                if (i < nc) cs[i] = (sa[k] * (1.0f / 7.0f)) * (sv[k] * (1.0f / 127.0f));           // CloverMatrix4.h:1147-1149
+                if (i < nc) cs[i] = mvm8_factor(sa[k], sv[k]);
             }
         }
         __syncthreads();
@@ -550,10 +506,7 @@ __global__ __launch_bounds__(256, MVM8_MIN_WAVES) void k_m4_mvm8(const uint8_t *
         }
     }
 
-    // chain 2m / 2m+1 in lane m.  CloverMatrix4.h:1229-1234: h[L] = a[L+4] + a[L]; (h0 + h2) + (h1 + h3)
-    const float he = a_even + __shfl_xor(a_even, 2), ho = a_odd + __shfl_xor(a_odd, 2);      // m = 0,2: h0, h1;  m = 1,3: h2, h3
-    const float ge = he + __shfl_xor(he, 1), go = ho + __shfl_xor(ho, 1);                    // h0 + h2,  h1 + h3
-    const float dot = ge + go;
+    const float dot = mvm8_tree(a_even, a_odd);
 
     if (m == 0) {
         dsh[rho] = dot;
@@ -828,7 +781,7 @@ static int launch_mvm8(const int8_t *A, const float *sA, uint64_t rows, uint64_t
     return CLV_OK;
 }
 
-static int check_mvm8_args(const char *fn, const void *A, const void *sA, uint64_t rows, uint64_t cols, const void *x, const void *sx)
+int check_mvm8_args(const char *fn, const void *A, const void *sA, uint64_t rows, uint64_t cols, const void *x, const void *sx)
 {
     CLV_REQUIRE(A && sA && x && sx, "%s: null pointer", fn);
     // rows % 64: a row shard of a matrix (see check_mvm_args in matrix4.hip)

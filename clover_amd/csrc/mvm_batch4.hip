@@ -4,7 +4,7 @@
 // of many signals with one Phi) pays them once per vector.  Here a workgroup loads each 16 matrix bytes once and runs the chain
 // arithmetic of every vector of the group on them.  The chains of different vectors are independent and each vector's instruction
 // sequence is the one of mvm_device.h, so the results equal the single calls bit for bit.
-#include "rng_device.h"
+#include "mvm_batch_device.h"
 #include "mvm_device.h"
 
 #include <algorithm>
@@ -36,62 +36,12 @@ struct MvmBatchFuse {        // see MvmFuse
     float a;
 };
 
-// ST: where the draws of the launch lie in the XORShift stream, counted in draws (one draw = one step of the 4-lane generator) from the
-// state the launch reads.  Slot v's window begins at draw_base + v * draw_stride: row group rb uses draws 2 rb, 2 rb + 1 of it for the mvm
-// and, with FUSE, 2 G + 2 rb, 2 G + 2 rb + 1 for the scaleAndAdd (G = row groups), as k_m4_mvm64 does from position 0.  commit_draws == 0:
-// the launch leaves the state as it is (no slot, no stamp written); otherwise workgroup 0 writes the state advanced by commit_draws.
-struct MvmBatchRng {
-    uint64_t *state;
-    uint64_t seq;
-    const uint64_t *pow_rows;
-    uint64_t draw_base, draw_stride, commit_draws;
-};
+// MvmBatchRng (where the draws of a launch lie in the XORShift stream), wave_pow_apply_many, mvmb_noise and the jump-ahead prologue:
+// mvm_batch_device.h, shared with the mixed batched kernel (mvm_batch8.hip)
 
 #define MVMB_X_BYTES(NV) ((NV) * (MVMB_CHUNK / 2 + (MVMB_CHUNK / 64) * sizeof(float) + 64 * sizeof(float)))
 // ST: behind the row dots, per vector and window the start of each of the 4 generator lanes (32 B): 512 B at NV = 8 fused, 39 424 B in all
 #define MVMB_LDS_BYTES(NV, ST, FUSE) (MVMB_X_BYTES(NV) + ((ST) ? (NV) * ((FUSE) ? 2 : 1) * 4 * sizeof(uint64_t) : 0))
-
-// T^(e[i])(v0) for NE wave-uniform exponents at once (wave_pow_apply for one).  The rows of a table level are the same for every exponent:
-// one memory round trip per 8 bits of the LARGEST exponent serves all of them, and the NE chains of ballots are independent of each other,
-// so they overlap instead of queueing behind NE x (round trip + chain).  Powers of one matrix commute: any order of the levels.
-template <int NE>
-__device__ __forceinline__ void wave_pow_apply_many(const uint64_t *__restrict__ pow_rows, uint64_t v0, uint64_t *e, uint64_t *v)
-{
-    const uint64_t *row = pow_rows + (threadIdx.x & 63);
-    uint64_t any = 0;
-    v0 = uniform64(v0);
-#pragma unroll
-    for (int i = 0; i < NE; i++) {
-        e[i] = uniform64(e[i]);
-        v[i] = v0;
-        any |= e[i];
-    }
-    while (any) {
-        uint64_t R[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) R[k] = ((any >> k) & 1ull) ? row[64 * k] : 0ull;
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-#pragma unroll
-            for (int i = 0; i < NE; i++)
-                if ((e[i] >> k) & 1ull) v[i] = wave_matvec(R[k], v[i]);
-#pragma unroll
-        for (int i = 0; i < NE; i++) e[i] >>= 8;
-        any >>= 8;
-        row += 8 * 64;
-    }
-}
-
-// the noise of epilogue lane `lane` from the window whose four lane starts are base[0..3]: the window's two draws are generated in the
-// lane itself (gen_blocks on generator lane j >> 1; every lane of an AVX lane pair repeats them, which costs a wave nothing), then the
-// word and byte k_m4_mvm64 reads from its raw[]: group grp of AVX lane j is draw grp >> 2, dword j of the draw's eight, byte grp & 3
-__device__ __forceinline__ float mvmb_noise(const uint64_t *base, int grp, int j)
-{
-    uint64_t raw[8];
-    gen_blocks(base[j >> 1], 1, raw, 0);                       // raw[0], raw[4]: this generator lane's output of draw 0, draw 1
-    const uint64_t o = (grp >> 2) ? raw[4] : raw[0];
-    return noise_of((j & 1) ? (uint32_t)(o >> 32) : (uint32_t)o, grp & 3);
-}
 
 // Registers: the single-vector kernel runs four waves per SIMD (123 VGPRs, 36 KiB of LDS: four workgroups per CU), which is what hides
 // the HBM latency.  amdgpu_waves_per_eu(4, 4) holds every instantiation to the same 128 registers; U (matrix loads in flight per lane)
@@ -120,35 +70,7 @@ __global__ __launch_bounds__(MVMB_THREADS) __attribute__((amdgpu_waves_per_eu(4,
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t st_seq = 0;
     uint64_t *st_next = nullptr;
-    if constexpr (ST) {
-        st_seq = rng_effective_seq(rs.state, rs.seq);
-        const int slot = rng_read_slot(rs.state, st_seq);
-        const uint64_t a0 = rs.state[slot * RNG_SLOT_WORDS + 4 + wave];
-        // exponent NV * NW: the committed state, workgroup 0 only (what rng_commit writes; the stamp follows the last barrier)
-        const bool commits = rs.commit_draws && rb == 0;
-        uint64_t e[NV * NW + 1], b[NV * NW + 1];
-#pragma unroll
-        for (int v = 0; v < NV; v++)
-#pragma unroll
-            for (int w = 0; w < NW; w++)
-                e[v * NW + w] = v < nv ? rs.draw_base + (uint64_t)v * rs.draw_stride + 2 * (rb + (uint64_t)w * gridDim.x) : 0;
-        e[NV * NW] = commits ? rs.commit_draws - 1 : 0;
-        // at most 9 exponents per walk: the values and exponents live in SGPR pairs, and 17 of each spill
-        constexpr int NE = NV * NW + 1, H = NE <= 9 ? NE : NE / 2;
-        wave_pow_apply_many<H>(rs.pow_rows, a0, e, b);
-        if constexpr (H < NE) wave_pow_apply_many<NE - H>(rs.pow_rows, a0, e + H, b + H);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < NV * NW; i++) sbase[i * 4 + wave] = b[i];      // read in the epilogue, barriers in between
-        }
-        if (commits) {
-            st_next = rs.state + (slot ^ 1) * RNG_SLOT_WORDS;
-            if (lane == 0) {
-                st_next[wave] = b[NV * NW];
-                st_next[4 + wave] = xs_T(b[NV * NW]);
-            }
-        }
-    }
+    if constexpr (ST) st_next = mvmb_rng_prologue<NV, NW>(rs, nv, rb, sbase, st_seq);
 
     const int q = tid & 3, rho = tid >> 2;
     const uint64_t row = rb * 64 + rho;
@@ -222,12 +144,7 @@ __global__ __launch_bounds__(MVMB_THREADS) __attribute__((amdgpu_waves_per_eu(4,
             if (q == 0) dsh[v * 64 + rho] = dot;
         }
     __syncthreads();
-    if constexpr (ST) {
-        if (st_next && tid == 0) {                                           // every wave's part of the new state was written before the barrier
-            __threadfence();
-            st_next[RNG_STAMP_WORD] = st_seq;
-        }
-    }
+    if constexpr (ST) mvmb_rng_stamp(st_next, st_seq);        // every wave's part of the new state was written before the barrier
 #pragma unroll
     for (int v = 0; v < NV; v++)
         if (v < nv && wave == (v & 3)) {
@@ -291,6 +208,7 @@ static bool mvm_batch_selected(uint64_t rows, uint64_t cols, uint64_t g, bool st
 
 static std::atomic<uint64_t> g_mvm_batch_launches{0};
 extern "C" uint64_t clv_mvm_batch_launches(void) { return g_mvm_batch_launches.load(std::memory_order_relaxed); }
+void clv_internal_mvm_batch_count(void) { g_mvm_batch_launches.fetch_add(1, std::memory_order_relaxed); }
 
 // the draws of a batched launch on the host side: rng == NULL = rounding disabled
 struct MvmBatchDraws {
@@ -337,7 +255,7 @@ static int launch_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uin
 #undef MVMB_LAUNCH_R
 #undef MVMB_LAUNCH
     CLV_LAUNCH_CHECK();
-    g_mvm_batch_launches.fetch_add(1, std::memory_order_relaxed);
+    clv_internal_mvm_batch_count();
     return CLV_OK;
 }
 

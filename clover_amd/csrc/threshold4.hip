@@ -478,8 +478,9 @@ __global__ __launch_bounds__(TS_THREADS) void k_thresh_small_batch(ThreshBatchAr
 // thread), radix select in four 8-bit levels straight over the elements (a block has up to 128 distinct magnitudes, so the
 // candidate trick of the 4-bit kernel does not pay), same DPP scans, same lowest-index tie rule.
 #define TS8_MAXW 8
+// the body of k_thresh8_small and of k_thresh8_small_batch (one workgroup = one vector in both)
 template <int TS8_W>          // words per thread, compile-time so that the unrolled loops carry no dead slots
-__global__ __launch_bounds__(TS_THREADS) void k_thresh8_small(uint32_t *__restrict__ q, const float *__restrict__ s, uint32_t n, uint32_t k)
+__device__ __forceinline__ void thresh8_small_body(uint32_t *__restrict__ q, const float *__restrict__ s, uint32_t n, uint32_t k)
 {
     typedef ThreshElems<8> E;
     constexpr int COPIES = 8;                      // private histograms by lane & 7: the keys of a vector crowd into a few bins
@@ -581,6 +582,19 @@ __global__ __launch_bounds__(TS_THREADS) void k_thresh8_small(uint32_t *__restri
             q[i] = outw;
         }
     }
+}
+
+template <int W>
+__global__ __launch_bounds__(TS_THREADS) void k_thresh8_small(uint32_t *__restrict__ q, const float *__restrict__ s, uint32_t n, uint32_t k)
+{
+    thresh8_small_body<W>(q, s, n, k);
+}
+
+// clv8_threshold_batch: workgroup j runs the body above on vector j (ThreshBatchArgs: the pointers by value, groups of TS_BATCH_GROUP)
+template <int W>
+__global__ __launch_bounds__(TS_THREADS) void k_thresh8_small_batch(ThreshBatchArgs args, uint32_t n, uint32_t k)
+{
+    thresh8_small_body<W>(args.q[blockIdx.x], args.s[blockIdx.x], n, k);
 }
 
 // ---- single-workgroup path for CloverVector16 (n_pad <= TS_THREADS * TS_MAXW * 2 = 32768): the structure of k_thresh_small -- the
@@ -2053,6 +2067,57 @@ extern "C" int clv8_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64
     CLV_REQUIRE_WORKSPACE("clv8_threshold_mode", workspace);
     if (k >= n || n == 0) return CLV_OK;
     return threshold_reference<8>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream));
+}
+
+// CloverVector8::threshold on nvec vectors of one size.  q / s: HOST arrays of nvec device pointers.  FAST up to the one-workgroup limit
+// (n_pad <= 32768): one launch per TS_BATCH_GROUP vectors, workgroup j = k_thresh8_small's body on vector j; otherwise the sequence of single
+// calls.  Bit-identical to that sequence.
+extern "C" int clv8_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode,
+                                    void *stream)
+{
+    const char *fn = "clv8_threshold_batch";
+    CLV_REQUIRE(mode == CLV_THRESHOLD_FAST || mode == CLV_THRESHOLD_REFERENCE, "%s: unknown mode %d", fn, mode);
+    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "%s: n=%llu n_pad=%llu", fn, (unsigned long long)n, (unsigned long long)n_pad);
+    CLV_REQUIRE(n < (1ull << 32), "%s: vectors of 2^32 or more elements are not supported", fn);
+    if (!nvec) return CLV_OK;
+    CLV_REQUIRE(q && s, "%s: null pointer array", fn);
+    for (uint64_t j = 0; j < nvec; j++) CLV_REQUIRE(q[j] && s[j], "%s: null pointer in vector %llu", fn, (unsigned long long)j);
+    {
+        std::vector<ClvRange> rg;
+        rg.reserve(2 * nvec);
+        for (uint64_t j = 0; j < nvec; j++) {
+            rg.push_back(clv_range(q[j], n_pad, true, j, "q"));
+            rg.push_back(clv_range(s[j], n_pad / 64 * sizeof(float), false, j, "s"));
+        }
+        int rc = clv_internal_check_ranges(fn, rg);
+        if (rc) return rc;
+    }
+    if (k >= n || n == 0) return CLV_OK;                       // everything survives
+    if (nvec == 1 || mode != CLV_THRESHOLD_FAST || n_pad > (uint64_t)TS_THREADS * TS8_MAXW * 4) {
+        for (uint64_t j = 0; j < nvec; j++) {
+            int rc = clv8_threshold_mode(q[j], s[j], n, n_pad, k, mode, nullptr, stream);
+            if (rc) return rc;
+        }
+        return CLV_OK;
+    }
+    hipStream_t st = as_stream(stream);
+    const uint64_t wpt = ((n + 3) / 4 + TS_THREADS - 1) / TS_THREADS;         // words per thread, as clv8_threshold
+    for (uint64_t j0 = 0; j0 < nvec; j0 += TS_BATCH_GROUP) {
+        const uint64_t g = nvec - j0 < TS_BATCH_GROUP ? nvec - j0 : TS_BATCH_GROUP;
+        ThreshBatchArgs args;
+        for (uint64_t j = 0; j < TS_BATCH_GROUP; j++) {
+            args.q[j] = j < g ? (uint32_t *)q[j0 + j] : nullptr;
+            args.s[j] = j < g ? s[j0 + j] : nullptr;
+        }
+#define T8B_LAUNCH(W) hipLaunchKernelGGL(k_thresh8_small_batch<W>, dim3((unsigned)g), dim3(TS_THREADS), 0, st, args, (uint32_t)n, (uint32_t)k)
+        if (wpt <= 1) T8B_LAUNCH(1);
+        else if (wpt <= 2) T8B_LAUNCH(2);
+        else if (wpt <= 4) T8B_LAUNCH(4);
+        else T8B_LAUNCH(8);
+#undef T8B_LAUNCH
+        CLV_LAUNCH_CHECK();
+    }
+    return CLV_OK;
 }
 
 // CloverVector16::threshold(K) / threshold_min_heap (CloverVector16.h:612-768): the same selection on |f32(h)|, two elements per word and no

@@ -124,6 +124,13 @@ SIGNATURES = {
     "clv4_threshold_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _u64, C.c_int, _vp]),
     "clm4_iht_batch": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
                                 C.c_float, C.c_int, _vp, _vp]),
+    # the same with CloverVector8 vectors (mvm_batch8.hip)
+    "clm4_mvm_v8_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm4_mvm_v8_batch_at": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp]),
+    "clm4_mvm_v8_scale_and_add_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clv8_threshold_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _u64, C.c_int, _vp]),
+    "clm4_iht_v8_batch": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
+                                   C.c_float, C.c_int, _vp, _vp]),
     "clm4_shard_partition": (C.c_int, [_u64, C.c_int, C.c_int, C.POINTER(_u64), C.POINTER(_u64)]),
     "clm4_sharded_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(C.c_int), _u64, _u64]),
     "clm4_sharded_destroy": (C.c_int, [_vp]),

@@ -89,8 +89,9 @@ inline void Q_GD(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 &x, Clov
  * iteration for all signals; the last iteration advances the generator by everything.  The scaleAndAdd steps draw from y[j]'s and x[j]'s
  * own generators and stay single calls. */
 namespace clover_hip {
-inline void q_iht_batch_stochastic(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 *const *x, CloverVector4 *const *y, CloverVector4 *const *t1,
-                                   CloverVector4 *const *t2, CloverVector4 *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
+template <class QVector>       /* CloverVector4 or CloverVector8: either mvm draws 2 (rows / 64) */
+inline void q_iht_batch_stochastic(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, QVector *const *x, QVector *const *y, QVector *const *t1,
+                                   QVector *const *t2, QVector *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
                                    const float mu, const bool with_threshold)
 {
     for (uint64_t j = 0; j < count; j++) x[j]->clear();
@@ -101,7 +102,7 @@ inline void q_iht_batch_stochastic(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, Clov
         for (uint64_t j = 0; j < count; j++) y[j]->scaleAndAdd_parallel(*t1[j], -1.0f, *t2[j]);
         PhiT.mvm_batch_at(t2, t3, count, it * dn, iterations * dn, last ? count * iterations * dn : 0);
         for (uint64_t j = 0; j < count; j++) x[j]->scaleAndAdd_parallel(*t3[j], mu);
-        if (with_threshold) CloverVector4::threshold_batch(x, count, K);
+        if (with_threshold) QVector::threshold_batch(x, count, K);
     }
 }
 }
@@ -157,6 +158,29 @@ inline void Q_GD(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector8 &x, Clov
         Phi.mvm_scaleAndAdd(x, y, -1.0f, t1, t2);
         PhiT.mvm_scaleAndAdd(t2, x, mu, t3);
     }
+}
+
+/* the same for `count` signals with ONE Phi (clm4_iht_v8_batch; stochastic: CloverMatrix4::mvm_batch_at per step): bit-identical to
+ * calling Q_IHT / Q_GD above signal after signal, the generators of Phi and PhiT included */
+inline void Q_IHT_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector8 *const *x, CloverVector8 *const *y, CloverVector8 *const *t1,
+                        CloverVector8 *const *t2, CloverVector8 *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
+                        const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, K, mu, true);
+#else
+    clover_hip::q_iht_batch_stochastic(Phi, PhiT, x, y, t1, t2, t3, count, iterations, K, mu, true);
+#endif
+}
+
+inline void Q_GD_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector8 *const *x, CloverVector8 *const *y, CloverVector8 *const *t1,
+                       CloverVector8 *const *t2, CloverVector8 *const *t3, const uint64_t count, const uint64_t iterations, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#else
+    clover_hip::q_iht_batch_stochastic(Phi, PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#endif
 }
 
 

@@ -190,27 +190,58 @@ public:
         if (x.size() != getCols() || t.size_pad() != getRows()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
         if (u.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
     }
-    /* Not in the reference: this * x[j] for `count` vectors in ONE pass over the matrix per group of CLM4_MVM_BATCH_MAX (clm4_mvm_batch);
-     * r[j] equals what mvm(*x[j], *r[j]) gives, bit for bit.  The x[j] may repeat; the r[j] are distinct vectors, none of them an x.
-     * With stochastic rounding enabled the vectors draw from the matrix's generator one after another, as the single calls in order do --
-     * still one pass: the kernel jumps to every vector's place in the stream -- and the generator ends where those calls leave it. */
+    /* Not in the reference: this * x[j] for `count` vectors in ONE pass over the matrix per group of CLM4_MVM_BATCH_MAX (clm4_mvm_batch;
+     * CloverVector8 vectors: clm4_mvm_v8_batch); r[j] equals what mvm(*x[j], *r[j]) gives, bit for bit.  The x[j] may repeat; the r[j] are
+     * distinct vectors, none of them an x.  With stochastic rounding enabled the vectors draw from the matrix's generator one after another,
+     * as the single calls in order do -- still one pass: the kernel jumps to every vector's place in the stream -- and the generator ends
+     * where those calls leave it. */
     void mvm_batch(const CloverVector4 *const *x, CloverVector4 *const *r, uint64_t count)
     {
-        mvm_batch_at(x, r, count, 0, 2 * (rows >> 6), count * 2 * (rows >> 6), false);
+        mvm_batch_at_t<CloverVector4>(x, r, count, 0, 2 * (rows >> 6), count * 2 * (rows >> 6), false);
     }
-    /* mvm_batch with the place of every vector's draws chosen by the caller (clm4_mvm_batch_at), counted in draws -- mvm consumes
-     * 2 (rows / 64) -- from where the matrix's generator stands: vector j draws from draw_base + j * draw_stride on, and the generator
-     * is advanced by commit_draws afterwards (0: left as it is).  For callers whose stream order is not vector after vector
+    void mvm_batch(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count)
+    {
+        mvm_batch_at_t<CloverVector8>(x, r, count, 0, 2 * (rows >> 6), count * 2 * (rows >> 6), false);
+    }
+    /* mvm_batch with the place of every vector's draws chosen by the caller (clm4_mvm_batch_at / clm4_mvm_v8_batch_at), counted in draws
+     * -- mvm consumes 2 (rows / 64) -- from where the matrix's generator stands: vector j draws from draw_base + j * draw_stride on, and
+     * the generator is advanced by commit_draws afterwards (0: left as it is).  For callers whose stream order is not vector after vector
      * (Q_IHT_batch, CloverIHT.h).  With rounding disabled the three numbers are ignored. */
     void mvm_batch_at(const CloverVector4 *const *x, CloverVector4 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
                       uint64_t commit_draws)
     {
-        mvm_batch_at(x, r, count, draw_base, draw_stride, commit_draws, true);
+        mvm_batch_at_t<CloverVector4>(x, r, count, draw_base, draw_stride, commit_draws, true);
+    }
+    void mvm_batch_at(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
+                      uint64_t commit_draws)
+    {
+        mvm_batch_at_t<CloverVector8>(x, r, count, draw_base, draw_stride, commit_draws, true);
     }
 
 private:
-    void mvm_batch_at(const CloverVector4 *const *x, CloverVector4 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
-                      uint64_t commit_draws, bool positioned)
+    /* the batch entry points per vector type: the CloverVector4 and the CloverVector8 calls have the same signatures */
+    template <class V, class Dummy = void> struct BatchAbi;
+    template <class Dummy> struct BatchAbi<CloverVector4, Dummy> {
+        static decltype(&clm4_mvm_batch) mvm() { return clm4_mvm_batch; }
+        static decltype(&clm4_mvm_batch_at) mvm_at() { return clm4_mvm_batch_at; }
+        static decltype(&clm4_mvm_scale_and_add_batch) fused() { return clm4_mvm_scale_and_add_batch; }
+        static decltype(&clm4_iht_batch) iht() { return clm4_iht_batch; }
+    };
+    template <class Dummy> struct BatchAbi<CloverVector8, Dummy> {
+        static decltype(&clm4_mvm_v8_batch) mvm() { return clm4_mvm_v8_batch; }
+        static decltype(&clm4_mvm_v8_batch_at) mvm_at() { return clm4_mvm_v8_batch_at; }
+        static decltype(&clm4_mvm_v8_scale_and_add_batch) fused() { return clm4_mvm_v8_scale_and_add_batch; }
+        static decltype(&clm4_iht_v8_batch) iht() { return clm4_iht_v8_batch; }
+    };
+    template <class V>
+    void check_fused_t(const V &x, const V &u, const V &t) const
+    {
+        if (x.size() != getCols() || t.size_pad() != getRows()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
+        if (u.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+    }
+    template <class V>
+    void mvm_batch_at_t(const V *const *x, V *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride, uint64_t commit_draws,
+                        bool positioned)
     {
         std::vector<const int8_t *> px(count);
         std::vector<const float *> psx(count);
@@ -227,20 +258,15 @@ private:
         for (uint64_t j = 0; j < count; j++) { pr[j] = r[j]->dev_values_wo(); psr[j] = r[j]->dev_scales_wo(); }
         uint64_t *rng = clover_hip::rng_or_null(random);
         if (positioned)
-            clover_hip::check(clm4_mvm_batch_at(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng,
-                                                draw_base, draw_stride, commit_draws, nullptr), "CloverMatrix4::mvm_batch_at");
+            clover_hip::check(BatchAbi<V>::mvm_at()(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng,
+                                                    draw_base, draw_stride, commit_draws, nullptr), "CloverMatrix4::mvm_batch_at");
         else      /* the launcher may forward groups to the single calls where those were measured faster */
-            clover_hip::check(clm4_mvm_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng, nullptr),
+            clover_hip::check(BatchAbi<V>::mvm()(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng, nullptr),
                               "CloverMatrix4::mvm_batch");
         for (uint64_t j = 0; j < count; j++) r[j]->commit();
     }
-
-public:
-    /* mvm_scaleAndAdd for `count` vectors: t[j] = this * x[j], r[j] = quantize(u[j] + a * t[j]).  Rounding disabled: one launch per group
-     * (clm4_mvm_scale_and_add_batch).  Stochastic: the mvm draws from the matrix's generator and every scaleAndAdd from its u[j]'s own, so
-     * it is one mvm_batch and the scaleAndAdd calls -- the bits of the loop of mvm_scaleAndAdd, the matrix read once per group. */
-    void mvm_scaleAndAdd_batch(const CloverVector4 *const *x, const CloverVector4 *const *u, float a, CloverVector4 *const *t, CloverVector4 *const *r,
-                               uint64_t count)
+    template <class V>
+    void mvm_scaleAndAdd_batch_t(const V *const *x, const V *const *u, float a, V *const *t, V *const *r, uint64_t count)
     {
 #ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
         std::vector<const int8_t *> px(count), pu(count);
@@ -248,7 +274,7 @@ public:
         std::vector<int8_t *> pt(count), pr(count);
         std::vector<float *> pst(count), psr(count);
         for (uint64_t j = 0; j < count; j++) {
-            check_fused(*x[j], *u[j], *t[j]);
+            check_fused_t(*x[j], *u[j], *t[j]);
             if (r[j]->size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
             px[j] = x[j]->dev_values_ro();
             psx[j] = x[j]->dev_scales_ro();
@@ -261,18 +287,18 @@ public:
             pr[j] = r[j]->dev_values_wo();
             psr[j] = r[j]->dev_scales_wo();
         }
-        clover_hip::check(clm4_mvm_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(), psu.data(), a,
-                                                       pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
+        clover_hip::check(BatchAbi<V>::fused()(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(), psu.data(), a,
+                                               pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
                           "CloverMatrix4::mvm_scaleAndAdd_batch");
         for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
 #else
-        for (uint64_t j = 0; j < count; j++) check_fused(*x[j], *u[j], *t[j]);
+        for (uint64_t j = 0; j < count; j++) check_fused_t(*x[j], *u[j], *t[j]);
         mvm_batch(x, t, count);
-        for (uint64_t j = 0; j < count; j++) const_cast<CloverVector4 *>(u[j])->scaleAndAdd(*t[j], a, *r[j]);
+        for (uint64_t j = 0; j < count; j++) const_cast<V *>(u[j])->scaleAndAdd(*t[j], a, *r[j]);
 #endif
     }
-    /* in place: u[j] = quantize(u[j] + a * (this * x[j])) */
-    void mvm_scaleAndAdd_batch(const CloverVector4 *const *x, CloverVector4 *const *u, float a, CloverVector4 *const *t, uint64_t count)
+    template <class V>
+    void mvm_scaleAndAdd_batch_in_place_t(const V *const *x, V *const *u, float a, V *const *t, uint64_t count)
     {
 #ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
         std::vector<const int8_t *> px(count), pu(count);
@@ -280,7 +306,7 @@ public:
         std::vector<int8_t *> pt(count), pr(count);
         std::vector<float *> pst(count), psr(count);
         for (uint64_t j = 0; j < count; j++) {
-            check_fused(*x[j], *u[j], *t[j]);
+            check_fused_t(*x[j], *u[j], *t[j]);
             px[j] = x[j]->dev_values_ro();
             psx[j] = x[j]->dev_scales_ro();
         }
@@ -290,20 +316,19 @@ public:
             pt[j] = t[j]->dev_values_wo();
             pst[j] = t[j]->dev_scales_wo();
         }
-        clover_hip::check(clm4_mvm_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(), psu.data(), a,
-                                                       pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
+        clover_hip::check(BatchAbi<V>::fused()(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(), psu.data(), a,
+                                               pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
                           "CloverMatrix4::mvm_scaleAndAdd_batch");
         for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
 #else
-        for (uint64_t j = 0; j < count; j++) check_fused(*x[j], *u[j], *t[j]);
+        for (uint64_t j = 0; j < count; j++) check_fused_t(*x[j], *u[j], *t[j]);
         mvm_batch(x, t, count);
         for (uint64_t j = 0; j < count; j++) u[j]->scaleAndAdd(*t[j], a);
 #endif
     }
-    /* iht_loop for `count` signals with this matrix as Phi (clm4_iht_batch): per iteration every step runs once for a group of signals;
-     * x[j], t1[j], t2[j], t3[j] end as iht_loop(PhiT, *x[j], *y[j], ...) leaves them.  Deterministic rounding only, as iht_loop. */
-    void iht_loop_batch(CloverMatrix4 &PhiT, CloverVector4 *const *x, const CloverVector4 *const *y, CloverVector4 *const *t1, CloverVector4 *const *t2,
-                        CloverVector4 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    template <class V>
+    void iht_loop_batch_t(CloverMatrix4 &PhiT, V *const *x, const V *const *y, V *const *t1, V *const *t2, V *const *t3, uint64_t count,
+                          uint64_t iterations, uint64_t K, float mu, bool with_threshold)
     {
         std::vector<const int8_t *> py(count);
         std::vector<const float *> psy(count);
@@ -329,14 +354,52 @@ public:
             ps3[j] = t3[j]->dev_scales_wo();
         }
         const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
-        clover_hip::check(clm4_iht_batch(dev_values(), dev_scales(), PhiT.dev_values(), PhiT.dev_scales(), rows, cols, count, px.data(), psx.data(),
-                                         count ? x[0]->size() : 0, py.data(), psy.data(), p1.data(), ps1.data(), p2.data(), ps2.data(), p3.data(),
-                                         ps3.data(), iterations, K, mu, thr, nullptr, nullptr),
+        clover_hip::check(BatchAbi<V>::iht()(dev_values(), dev_scales(), PhiT.dev_values(), PhiT.dev_scales(), rows, cols, count, px.data(), psx.data(),
+                                             count ? x[0]->size() : 0, py.data(), psy.data(), p1.data(), ps1.data(), p2.data(), ps2.data(), p3.data(),
+                                             ps3.data(), iterations, K, mu, thr, nullptr, nullptr),
                           "CloverMatrix4::iht_loop_batch");
         for (uint64_t j = 0; j < count; j++) {
             x[j]->commit();
             if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }
         }
+    }
+
+public:
+    /* mvm_scaleAndAdd for `count` vectors: t[j] = this * x[j], r[j] = quantize(u[j] + a * t[j]).  Rounding disabled: one launch per group
+     * (clm4_mvm_scale_and_add_batch / clm4_mvm_v8_scale_and_add_batch).  Stochastic: the mvm draws from the matrix's generator and every
+     * scaleAndAdd from its u[j]'s own, so it is one mvm_batch and the scaleAndAdd calls -- the bits of the loop of mvm_scaleAndAdd, the
+     * matrix read once per group. */
+    void mvm_scaleAndAdd_batch(const CloverVector4 *const *x, const CloverVector4 *const *u, float a, CloverVector4 *const *t, CloverVector4 *const *r,
+                               uint64_t count)
+    {
+        mvm_scaleAndAdd_batch_t<CloverVector4>(x, u, a, t, r, count);
+    }
+    void mvm_scaleAndAdd_batch(const CloverVector8 *const *x, const CloverVector8 *const *u, float a, CloverVector8 *const *t, CloverVector8 *const *r,
+                               uint64_t count)
+    {
+        mvm_scaleAndAdd_batch_t<CloverVector8>(x, u, a, t, r, count);
+    }
+    /* in place: u[j] = quantize(u[j] + a * (this * x[j])) */
+    void mvm_scaleAndAdd_batch(const CloverVector4 *const *x, CloverVector4 *const *u, float a, CloverVector4 *const *t, uint64_t count)
+    {
+        mvm_scaleAndAdd_batch_in_place_t<CloverVector4>(x, u, a, t, count);
+    }
+    void mvm_scaleAndAdd_batch(const CloverVector8 *const *x, CloverVector8 *const *u, float a, CloverVector8 *const *t, uint64_t count)
+    {
+        mvm_scaleAndAdd_batch_in_place_t<CloverVector8>(x, u, a, t, count);
+    }
+    /* iht_loop for `count` signals with this matrix as Phi (clm4_iht_batch / clm4_iht_v8_batch): per iteration every step runs once for a
+     * group of signals; x[j], t1[j], t2[j], t3[j] end as iht_loop(PhiT, *x[j], *y[j], ...) leaves them.  Deterministic rounding only, as
+     * iht_loop. */
+    void iht_loop_batch(CloverMatrix4 &PhiT, CloverVector4 *const *x, const CloverVector4 *const *y, CloverVector4 *const *t1, CloverVector4 *const *t2,
+                        CloverVector4 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    {
+        iht_loop_batch_t<CloverVector4>(PhiT, x, y, t1, t2, t3, count, iterations, K, mu, with_threshold);
+    }
+    void iht_loop_batch(CloverMatrix4 &PhiT, CloverVector8 *const *x, const CloverVector8 *const *y, CloverVector8 *const *t1, CloverVector8 *const *t2,
+                        CloverVector8 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    {
+        iht_loop_batch_t<CloverVector8>(PhiT, x, y, t1, t2, t3, count, iterations, K, mu, with_threshold);
     }
     /* The reference's mvm_scalar (:311-392): every row wrapped in a non-owning CloverVector4 view over the matrix's own memory and
      * multiplied with dot() (the SIMD order, here the exact-order kernel), then 64 results at a time quantised by scalar code.  An

@@ -20,6 +20,8 @@
 #ifndef CLOVER_VECTOR8_H
 #define CLOVER_VECTOR8_H
 
+#include <vector>
+
 #include "CloverVector32.h"
 #include "clover_scalar.h"
 
@@ -226,6 +228,22 @@ public:
         commit();
     }
     void threshold_parallel(uint64_t k) { threshold(k); }
+    /* threshold(k) on `count` vectors of one size (clv8_threshold_batch): with the fast tie rule and vectors of up to 32768 elements
+     * ONE launch per 64 vectors, else the single calls in order; every v[j] ends as v[j]->threshold(k) leaves it.  Honours the exactness
+     * switch. */
+    static void threshold_batch(CloverVector8 *const *v, uint64_t count, uint64_t k)
+    {
+        std::vector<int8_t *> pq(count);
+        std::vector<const float *> ps(count);
+        for (uint64_t j = 0; j < count; j++) {
+            if (v[j]->length != v[0]->length) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+            pq[j] = v[j]->dev_values_rw();
+            ps[j] = v[j]->dev_scales_ro();
+        }
+        clover_hip::check(clv8_threshold_batch(pq.data(), ps.data(), count, count ? v[0]->length : 0, count ? v[0]->length_pad : 0, k,
+                                               clover_hip::threshold_mode(), nullptr), "CloverVector8::threshold_batch");
+        for (uint64_t j = 0; j < count; j++) v[j]->commit();
+    }
     /* threshold with the caller's own heap memory (CloverVector8.h:1696-1737, 1742-1824): as CloverVector4::threshold_min_heap */
     typedef clover_hip::idx_t idx_t;
     void threshold_min_heap(idx_t *min_heap, uint64_t k)

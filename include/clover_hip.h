@@ -468,7 +468,8 @@ int  clm4_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t co
 int  clm4_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
                     const int8_t *const *x, const float *const *sx, int8_t *const *r, float *const *sr,
                     uint64_t *rng_state_dev, uint64_t draw_base, uint64_t draw_stride, uint64_t commit_draws, void *stream);
-/* diagnostic: the number of batched-kernel launches (one matrix pass for a group of vectors, either rounding) this process has enqueued --
+/* diagnostic: the number of batched-kernel launches (one matrix pass for a group of vectors, either rounding, CloverVector4 or CloverVector8
+ * vectors: the calls above and the clm4_*_v8_batch calls below count in the same number) this process has enqueued --
  * the counterpart of clv_iht_persistent_launches: what a test or a benchmark reads to know that the one-pass kernel ran, not the forwarding
  * to single calls. */
 uint64_t clv_mvm_batch_launches(void);
@@ -479,6 +480,57 @@ int  clm4_mvm_scale_and_add_batch(const int8_t *A, const float *sA, uint64_t row
 int  clv4_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k,
                     int mode, void *stream);
 int  clm4_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, uint64_t nvec,
+                    int8_t *const *x, float *const *sx, uint64_t x_len, const int8_t *const *y, const float *const *sy,
+                    int8_t *const *t1, float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
+                    uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream);
+
+/* ---- the same with CloverVector8 vectors: CloverMatrix4 x CloverVector8, the configuration the reference publishes as "4-bit" ----------
+ * The five calls mirror the five above; the pointer arrays are HOST arrays of `nvec` DEVICE pointers, read during the call, nothing kept.
+ * CONTRACT: each call is bit-identical to the corresponding single call made for vector 0, then 1, ... on the same stream -- clm4_mvm_v8,
+ * clm4_mvm_v8_scale_and_add, clv8_threshold_mode with a NULL workspace, clm4_iht_v8 -- including what is left in t1 .. t3 and, with an
+ * rng, the XORShift state left behind.
+ *  - nvec may be any number: groups of at most CLM4_MVM_BATCH_MAX vectors run one matrix pass each; nvec == 1 forwards to the single
+ *    call; nvec == 0 or rows == 0 returns CLV_OK and does nothing.  The launcher takes the batched kernel only where it was measured
+ *    faster than the single launches and forwards to them elsewhere: same bits either way.
+ *  - rng_state_dev != NULL: the same one pass per group, with the draws where the sequence of single calls has them.  Vector j's draws
+ *    follow vector j - 1's in the stream (clm4_mvm_v8 draws 2 (rows/64), clm4_mvm_v8_scale_and_add 4 (rows/64)); every workgroup of the
+ *    batched kernel jumps from the state the launch finds to each vector's position itself, and the launch leaves the state advanced by
+ *    all of them.  Groups that run batched and groups that forward to single calls mix within one call.  For clm4_iht_v8_batch the order
+ *    is all iterations of vector 0 first: one iteration draws P = 4 (m/64) + 4 (n/64), a batched group places vector j's iteration `it` at
+ *    (j * iterations + it) * P and only its last launch advances the state.  The rules for stochastic calls above apply (graph capture:
+ *    clv_rng_graph_mode).
+ *  - clm4_mvm_v8_batch_at: clm4_mvm_batch_at for CloverVector8 vectors -- vector j re-quantises with the 2 (rows/64) draws that begin at
+ *    draw_base + j * draw_stride, across the groups too, exactly as clm4_mvm_v8 would with the state advanced that far; afterwards the state
+ *    is advanced by commit_draws, or untouched when commit_draws == 0.  Any stride is legal, 0 included.  With an rng this call ALWAYS runs
+ *    the batched kernel, for nvec == 1 and under CLV_MVM_BATCH=0 too; rng_state_dev == NULL: the three position numbers are ignored, the
+ *    call is clm4_mvm_v8_batch.  Every position (the end of every vector's window) and commit_draws must stay below 2^55.
+ *  - clv8_threshold_batch: FAST with n_pad <= 32768 (the one-workgroup kernel) is ONE launch per 64 vectors, workgroup j thresholding
+ *    vector j; REFERENCE mode and larger vectors run as the sequence of single calls (and use the stream's scratch as those do).
+ *  - clm4_iht_v8_batch: every x[j] cleared, then per iteration and group two positioned fused batch launches and, if threshold != 0, one
+ *    clv8_threshold_batch (threshold, x_len, K, mu as clm4_iht_v8).  Where a single clm4_iht_v8 takes the persistent kernel a group runs
+ *    this way only at the group sizes at which it was measured faster than that kernel and as single calls otherwise; those
+ *    do not capture into a hipGraph (clm4_iht_v8).
+ *  - CLV_MVM_BATCH in the environment (read per call; for tests and measurements): 1 = every group of two or more vectors runs
+ *    batched, 0 = every call forwards to the single calls.  Batched launches count in clv_mvm_batch_launches().
+ *  - checked before any device work (CLV_ERR_INVALID, the message names the call and the vector index): the size rules of the
+ *    single calls; no NULL array and no NULL entry (t and st: both arrays given or both NULL = t is not stored); no output range may
+ *    overlap an input range of ANY vector of the call -- another workgroup may still be reading it -- nor the matrix; no two outputs
+ *    may overlap (a vector of n elements is n bytes, its scales n/64 floats).  One exception: r[j] / sr[j] may be exactly qu[j] / su[j],
+ *    the in-place form.  As in clm4_mvm_v8_scale_and_add the result must not alias the vector being multiplied.  Repeated INPUT pointers
+ *    are allowed. */
+int  clm4_mvm_v8_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
+                    const int8_t *const *x, const float *const *sx, int8_t *const *r, float *const *sr,
+                    uint64_t *rng_state_dev, void *stream);
+int  clm4_mvm_v8_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
+                    const int8_t *const *x, const float *const *sx, int8_t *const *r, float *const *sr,
+                    uint64_t *rng_state_dev, uint64_t draw_base, uint64_t draw_stride, uint64_t commit_draws, void *stream);
+int  clm4_mvm_v8_scale_and_add_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
+                    const int8_t *const *x, const float *const *sx, const int8_t *const *qu, const float *const *su, float a,
+                    int8_t *const *t, float *const *st,      /* both arrays NULL: t is not stored */
+                    int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, void *stream);
+int  clv8_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k,
+                    int mode, void *stream);
+int  clm4_iht_v8_batch(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, uint64_t nvec,
                     int8_t *const *x, float *const *sx, uint64_t x_len, const int8_t *const *y, const float *const *sy,
                     int8_t *const *t1, float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
                     uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream);

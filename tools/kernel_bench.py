@@ -273,6 +273,89 @@ if any(selected(r) for r in BATCH_ROWS):
         sys.exit(0)
 
 
+# ---- several CloverVector8 with one CloverMatrix4 (mvm_batch8.hip): the rows above for the configuration the reference publishes as "4-bit".
+# Every row pairs the batch call under CLV_MVM_BATCH=1 with the same vectors issued as single calls in the same session; the *_st_* twins
+# run with a generator.  A run that names only these rows (KB_ONLY=mvm_v8,iht_v8) ends after them.
+V8_BATCH_ROWS = tuple(f"mvm_v8_batch{g}_{t}{nb}^2" for nb in (32768, 65536) for g in (2, 4, 8) for t in ("", "st_")) + \
+    tuple(f"mvm_v8_saa_batch{g}_{t}8192x4096" for g in (2, 4, 8) for t in ("", "st_")) + ("iht_v8_batch8_N8192", "iht_v8_batch8_st_N8192")
+
+
+def vec8_set(count, n, seed):
+    """count x (n int8 in [-127, 127], n / 64 scales): fp32 integers quantised to CloverVector8 on the device"""
+    out, f = [], hip.alloc(4 * n)
+    for j in range(count):
+        q, s = hip.alloc(n), hip.alloc(n // 16)
+        hip.check(lib.clv_fill_random_ints_f32(f.ptr, n, 100, seed + j, 0, None))
+        hip.check(lib.clv8_quantize(f.ptr, n, q.ptr, s.ptr, None, None))
+        out.append((q, s))
+    hip.sync()
+    return out
+
+
+if any(selected(r) for r in V8_BATCH_ROWS):
+    for nb in (32768, 65536):
+        if not any(selected(f"mvm_v8_batch{g}_{t}{nb}^2") for g in (2, 4, 8) for t in ("", "st_")):
+            continue
+        bA, bsA = hip.alloc(nb * nb // 2), hip.alloc((nb // 64) ** 2 * 4)
+        hip.check(lib.clv_fill_random_nibbles(bA.ptr, bA.nbytes, 41, 0, None))
+        hip.check(lib.clv_fill_random_scales(bsA.ptr, bsA.nbytes // 4, 42, 0, None))
+        bx, br = vec8_set(8, nb, 300), vec8_set(8, nb, 400)
+        one_b = nb * nb // 2 + 4 * (nb // 64) ** 2 + 2 * (nb + nb // 16)
+        for g in (2, 4, 8):
+            ax, asx, ar, asr = ptrs([v[0] for v in bx[:g]]), ptrs([v[1] for v in bx[:g]]), ptrs([v[0] for v in br[:g]]), ptrs([v[1] for v in br[:g]])
+            for tag, st in (("", None), ("st_", hip.new_rng(1, 2))):
+                sp = st.ptr if st else None
+
+                def singles(g=g, sp=sp):
+                    for j in range(g):
+                        hip.check(lib.clm4_mvm_v8(bA.ptr, bsA.ptr, nb, nb, bx[j][0].ptr, bx[j][1].ptr, br[j][0].ptr, br[j][1].ptr, sp, None))
+                rec_pair(f"mvm_v8_batch{g}_{tag}{nb}^2", one_b, g, singles,
+                         lambda g=g, a=(ax, asx, ar, asr), sp=sp: hip.check(lib.clm4_mvm_v8_batch(bA.ptr, bsA.ptr, nb, nb, g, a[0], a[1], a[2], a[3], sp, None)),
+                         reps=10 if nb == 32768 else 4)
+        del bA, bsA, bx, br
+    # the IHT shape (N = 8192: Phi 4096 x 8192, cache-resident): the x += mu Phi' t2 step for 2, 4 and 8 signals, and the whole loop for 8
+    im, inn, ig, iters = 4096, 8192, 8, 20
+    if any(selected(r) for r in V8_BATCH_ROWS[12:]):
+        P, sP, PT, sPT = hip.alloc(im * inn // 2), hip.alloc(4 * (im // 64) * (inn // 64)), hip.alloc(im * inn // 2), hip.alloc(4 * (im // 64) * (inn // 64))
+        hip.check(lib.clv_fill_random_nibbles(P.ptr, P.nbytes, 51, 0, None))
+        hip.check(lib.clv_fill_random_scales(sP.ptr, sP.nbytes // 4, 52, 0, None))
+        hip.check(lib.clm4_transpose(P.ptr, sP.ptr, im, inn, PT.ptr, sPT.ptr, None))
+        vy, vx, vt1, vt2, vt3, vr = (vec8_set(ig, n, seed) for n, seed in ((im, 500), (inn, 600), (im, 700), (im, 800), (inn, 900), (inn, 1000)))
+        A = {k: (ptrs([p[0] for p in v]), ptrs([p[1] for p in v])) for k, v in dict(y=vy, x=vx, t1=vt1, t2=vt2, t3=vt3, r=vr).items()}
+        saa_b = im * inn // 2 + 4 * (im // 64) * (inn // 64) + (im + im // 16) + 3 * (inn + inn // 16)
+        for tag, st in (("", None), ("st_", hip.new_rng(1, 2))):
+            sp = st.ptr if st else None
+            for sg in (2, 4, 8):
+                def saa_singles(sg=sg, sp=sp):
+                    for j in range(sg):
+                        hip.check(lib.clm4_mvm_v8_scale_and_add(PT.ptr, sPT.ptr, inn, im, vt2[j][0].ptr, vt2[j][1].ptr, vx[j][0].ptr, vx[j][1].ptr, 0.002,
+                                                                vt3[j][0].ptr, vt3[j][1].ptr, vr[j][0].ptr, vr[j][1].ptr, sp, None))
+                rec_pair(f"mvm_v8_saa_batch{sg}_{tag}8192x4096", saa_b, sg, saa_singles,
+                         lambda sg=sg, sp=sp: hip.check(lib.clm4_mvm_v8_scale_and_add_batch(PT.ptr, sPT.ptr, inn, im, sg, A["t2"][0], A["t2"][1], A["x"][0],
+                                                                                            A["x"][1], 0.002, A["t3"][0], A["t3"][1], A["r"][0], A["r"][1],
+                                                                                            sp, None)), reps=20)
+
+            def iht_singles(sp=sp):
+                for j in range(ig):
+                    hip.check(lib.clm4_iht_v8(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, vx[j][0].ptr, vx[j][1].ptr, inn, vy[j][0].ptr, vy[j][1].ptr,
+                                              vt1[j][0].ptr, vt1[j][1].ptr, vt2[j][0].ptr, vt2[j][1].ptr, vt3[j][0].ptr, vt3[j][1].ptr, iters, im // 4, 0.002,
+                                              1, sp, None))
+            name = f"iht_v8_batch8_{tag}N8192"
+            before = lib.clv_iht_persistent_launches()
+            rec_pair(name, 2 * (im * inn // 2), ig, iht_singles,
+                     lambda sp=sp: hip.check(lib.clm4_iht_v8_batch(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, ig, A["x"][0], A["x"][1], inn, A["y"][0], A["y"][1],
+                                                                   A["t1"][0], A["t1"][1], A["t2"][0], A["t2"][1], A["t3"][0], A["t3"][1], iters, im // 4,
+                                                                   0.002, 1, sp, None)), reps=2, per=iters)
+            if name in res:
+                res[name]["single_calls_took_the_persistent_kernel"] = bool(lib.clv_iht_persistent_launches() > before)
+                res[name]["note"] = (f"ms per iteration for all 8 signals, calls of {iters} iterations, K = m / 4, FAST threshold" +
+                                     (", one generator" if st else "") + "; the single calls are 8 x clm4_iht_v8 as the library runs it")
+        del P, sP, PT, sPT, vy, vx, vt1, vt2, vt3, vr
+    if ONLY and all(any(o in r for r in V8_BATCH_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
+
+
 # ---- vector ops at n = 2^30 (4 GiB fp32 source, 512 MiB + 64 MiB quantized) and n = 2^24
 for logn in (24, 30):
     n = 1 << logn
