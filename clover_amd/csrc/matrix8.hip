@@ -416,7 +416,7 @@ extern "C" int clm8_restore(const int8_t *q, const float *s, uint64_t rows, uint
     return CLV_OK;
 }
 
-static int m8_check_mvm(const char *fn, const void *A, const void *sA, uint64_t rows, uint64_t cols, const void *x, const void *r)
+int clv_internal_m8_check_mvm(const char *fn, const void *A, const void *sA, uint64_t rows, uint64_t cols, const void *x, const void *r)
 {
     CLV_REQUIRE(A && sA && x && r, "%s: null pointer", fn);
     // a whole CloverMatrix8 has rows % 128 == 0; a multiple of 64 is a row shard of one (as for clm4_mvm)
@@ -429,7 +429,7 @@ static int m8_check_mvm(const char *fn, const void *A, const void *sA, uint64_t 
 extern "C" int clm8_mvm(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx, int8_t *r, float *sr,
                         uint64_t *rng_state_dev, void *stream)
 {
-    int rc = m8_check_mvm("clm8_mvm", A, sA, rows, cols, x, r);
+    int rc = clv_internal_m8_check_mvm("clm8_mvm", A, sA, rows, cols, x, r);
     if (rc) return rc;
     CLV_REQUIRE(sx && sr, "clm8_mvm: null pointer");
     CLV_REQUIRE((const void *)r != (const void *)x, "clm8_mvm: the result must not alias the vector being multiplied");
@@ -466,7 +466,7 @@ extern "C" int clm8_mvm_scale_and_add(const int8_t *A, const float *sA, uint64_t
                                       const int8_t *qu, const float *su, float a, int8_t *t, float *st_, int8_t *r, float *sr,
                                       uint64_t *rng_state_dev, void *stream)
 {
-    int rc = m8_check_mvm(M8_SAA, A, sA, rows, cols, x, r);
+    int rc = clv_internal_m8_check_mvm(M8_SAA, A, sA, rows, cols, x, r);
     if (rc) return rc;
     CLV_REQUIRE(sx && qu && su && sr, M8_SAA ": null pointer");
     CLV_REQUIRE((t == nullptr) == (st_ == nullptr), M8_SAA ": t and st must both be given or both be NULL");
@@ -521,7 +521,7 @@ extern "C" int clm8_iht(const int8_t *Phi, const float *sPhi, const int8_t *PhiT
 
 extern "C" int clm8_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *r, void *stream)
 {
-    int rc = m8_check_mvm("clm8_mvm_f32", A, sA, rows, cols, x, r);
+    int rc = clv_internal_m8_check_mvm("clm8_mvm_f32", A, sA, rows, cols, x, r);
     if (rc) return rc;
     if (!rows) return CLV_OK;
     const dim3 grid((unsigned)(rows / 32)), block(256);

@@ -131,6 +131,12 @@ SIGNATURES = {
     "clv8_threshold_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _u64, C.c_int, _vp]),
     "clm4_iht_v8_batch": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
                                    C.c_float, C.c_int, _vp, _vp]),
+    # the pure 8-bit path (matrix8_batch.hip)
+    "clm8_mvm_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm8_mvm_batch_at": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp]),
+    "clm8_mvm_scale_and_add_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm8_iht_batch": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
+                                C.c_float, C.c_int, _vp, _vp]),
     "clm4_shard_partition": (C.c_int, [_u64, C.c_int, C.c_int, C.POINTER(_u64), C.POINTER(_u64)]),
     "clm4_sharded_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(C.c_int), _u64, _u64]),
     "clm4_sharded_destroy": (C.c_int, [_vp]),

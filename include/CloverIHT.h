@@ -89,8 +89,8 @@ inline void Q_GD(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 &x, Clov
  * iteration for all signals; the last iteration advances the generator by everything.  The scaleAndAdd steps draw from y[j]'s and x[j]'s
  * own generators and stay single calls. */
 namespace clover_hip {
-template <class QVector>       /* CloverVector4 or CloverVector8: either mvm draws 2 (rows / 64) */
-inline void q_iht_batch_stochastic(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, QVector *const *x, QVector *const *y, QVector *const *t1,
+template <class QMatrix, class QVector>       /* CloverMatrix4 with CloverVector4 or CloverVector8, CloverMatrix8 with CloverVector8: every mvm draws 2 (rows / 64) */
+inline void q_iht_batch_stochastic(QMatrix &Phi, QMatrix &PhiT, QVector *const *x, QVector *const *y, QVector *const *t1,
                                    QVector *const *t2, QVector *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
                                    const float mu, const bool with_threshold)
 {
@@ -218,6 +218,29 @@ inline void Q_GD<CloverMatrix8, CloverVector8>(CloverMatrix8 &Phi, CloverMatrix8
         Phi.mvm_scaleAndAdd(x, y, -1.0f, t1, t2);
         PhiT.mvm_scaleAndAdd(t2, x, mu, t3);
     }
+}
+
+/* the same for `count` signals with ONE 8-bit Phi (clm8_iht_batch; stochastic: CloverMatrix8::mvm_batch_at per step): bit-identical to
+ * calling Q_IHT / Q_GD above signal after signal, the generators of Phi and PhiT included */
+inline void Q_IHT_batch(CloverMatrix8 &Phi, CloverMatrix8 &PhiT, CloverVector8 *const *x, CloverVector8 *const *y, CloverVector8 *const *t1,
+                        CloverVector8 *const *t2, CloverVector8 *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
+                        const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, K, mu, true);
+#else
+    clover_hip::q_iht_batch_stochastic(Phi, PhiT, x, y, t1, t2, t3, count, iterations, K, mu, true);
+#endif
+}
+
+inline void Q_GD_batch(CloverMatrix8 &Phi, CloverMatrix8 &PhiT, CloverVector8 *const *x, CloverVector8 *const *y, CloverVector8 *const *t1,
+                       CloverVector8 *const *t2, CloverVector8 *const *t3, const uint64_t count, const uint64_t iterations, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#else
+    clover_hip::q_iht_batch_stochastic(Phi, PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#endif
 }
 
 /* CloverMatrix16 with CloverVector16 vectors: the half-precision loop the reference measures in test/performance/02_bit16.cpp:112-117.

@@ -17,6 +17,9 @@
  *
  *   mvm_scaleAndAdd                    -> clm8_mvm_scale_and_add  (not in the reference: mvm + the scaleAndAdd behind it, one launch)
  *   iht_loop                           -> clm8_iht        (the whole Q_IHT / Q_GD loop of 01_measure.h:923-946, 999-1021 in one call)
+ *   mvm_batch / mvm_batch_at / mvm_scaleAndAdd_batch / iht_loop_batch
+ *                                      -> clm8_mvm_batch, clm8_mvm_batch_at, clm8_mvm_scale_and_add_batch, clm8_iht_batch (not in the
+ *                                         reference: several vectors, ONE pass over the matrix per group of CLM4_MVM_BATCH_MAX)
  *   gemm                               -> clm8_gemm       (not in the reference, which has no GEMM; semantics in DESIGN.md 6)
  *
  * Q_IHT<CloverMatrix8, CloverVector8> and Q_GD<...> are specialised in CloverIHT.h (which includes this header): iht_loop when rounding is
@@ -29,6 +32,7 @@
 #include <iomanip>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "CloverMatrix32.h"
 #include "CloverVector32.h"
@@ -124,6 +128,8 @@ public:
     void setRandomKeys(__m256i key1, __m256i key2) { clover_hip::set_keys_m256(random, key1, key2); }   /* CloverRandom.h:90-94 */
 #endif
     void seedRandomKeys(uint64_t key1, uint64_t key2) { random.seed(key1, key2); }
+    /* the generator's present keys, read back from the device (for tests: as CloverMatrix4::getRandomKeys) */
+    void getRandomKeys(uint64_t key1[4], uint64_t key2[4]) const { random.get(key1, key2); }
 
     void quantize(const CloverMatrix32 &m)
     {
@@ -240,6 +246,157 @@ public:
         x.commit();
         if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
     }
+    /* Not in the reference: this * x[j] for `count` vectors in ONE pass over the matrix per group of CLM4_MVM_BATCH_MAX (clm8_mvm_batch);
+     * r[j] equals what mvm(*x[j], *r[j]) gives, bit for bit.  The x[j] may repeat; the r[j] are distinct vectors, none of them an x.  With
+     * stochastic rounding enabled the vectors draw from the matrix's generator one after another, as the single calls in order do -- still
+     * one pass: the kernel jumps to every vector's place in the stream -- and the generator ends where those calls leave it. */
+    void mvm_batch(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count)
+    {
+        mvm_batch_at_impl(x, r, count, 0, 2 * (rows >> 6), count * 2 * (rows >> 6), false);
+    }
+    /* mvm_batch with the place of every vector's draws chosen by the caller (clm8_mvm_batch_at), counted in draws -- mvm consumes
+     * 2 (rows / 64) -- from where the matrix's generator stands: vector j draws from draw_base + j * draw_stride on, and the generator is
+     * advanced by commit_draws afterwards (0: left as it is).  For callers whose stream order is not vector after vector (Q_IHT_batch,
+     * CloverIHT.h).  With rounding disabled the three numbers are ignored. */
+    void mvm_batch_at(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
+                      uint64_t commit_draws)
+    {
+        mvm_batch_at_impl(x, r, count, draw_base, draw_stride, commit_draws, true);
+    }
+    /* mvm_scaleAndAdd for `count` vectors: t[j] = this * x[j], r[j] = quantize(u[j] + a * t[j]).  Rounding disabled: one launch per group
+     * (clm8_mvm_scale_and_add_batch).  Stochastic: the mvm draws from the matrix's generator and every scaleAndAdd from its u[j]'s own, so
+     * it is one mvm_batch and the scaleAndAdd calls -- the bits of the loop of mvm_scaleAndAdd, the matrix read once per group. */
+    void mvm_scaleAndAdd_batch(const CloverVector8 *const *x, const CloverVector8 *const *u, float a, CloverVector8 *const *t,
+                               CloverVector8 *const *r, uint64_t count)
+    {
+        for (uint64_t j = 0; j < count; j++) {
+            check_fused(*x[j], *u[j], *t[j]);
+            if (r[j]->size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        }
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        std::vector<const int8_t *> px(count), pu(count);
+        std::vector<const float *> psx(count), psu(count);
+        std::vector<int8_t *> pt(count), pr(count);
+        std::vector<float *> pst(count), psr(count);
+        for (uint64_t j = 0; j < count; j++) {
+            px[j] = x[j]->dev_values_ro();
+            psx[j] = x[j]->dev_scales_ro();
+            pu[j] = u[j]->dev_values_ro();
+            psu[j] = u[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) {
+            pt[j] = t[j]->dev_values_wo();
+            pst[j] = t[j]->dev_scales_wo();
+            pr[j] = r[j]->dev_values_wo();
+            psr[j] = r[j]->dev_scales_wo();
+        }
+        clover_hip::check(clm8_mvm_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(), psu.data(), a,
+                                                       pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
+                          "CloverMatrix8::mvm_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
+#else
+        mvm_batch(x, t, count);
+        for (uint64_t j = 0; j < count; j++) const_cast<CloverVector8 *>(u[j])->scaleAndAdd(*t[j], a, *r[j]);
+#endif
+    }
+    /* in place: u[j] = quantize(u[j] + a * (this * x[j])) */
+    void mvm_scaleAndAdd_batch(const CloverVector8 *const *x, CloverVector8 *const *u, float a, CloverVector8 *const *t, uint64_t count)
+    {
+        for (uint64_t j = 0; j < count; j++) check_fused(*x[j], *u[j], *t[j]);
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        std::vector<const int8_t *> px(count), pu(count);
+        std::vector<const float *> psx(count), psu(count);
+        std::vector<int8_t *> pt(count), pr(count);
+        std::vector<float *> pst(count), psr(count);
+        for (uint64_t j = 0; j < count; j++) {
+            px[j] = x[j]->dev_values_ro();
+            psx[j] = x[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) {
+            pu[j] = pr[j] = u[j]->dev_values_rw();
+            psu[j] = psr[j] = u[j]->dev_scales_rw();
+            pt[j] = t[j]->dev_values_wo();
+            pst[j] = t[j]->dev_scales_wo();
+        }
+        clover_hip::check(clm8_mvm_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(), psu.data(), a,
+                                                       pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
+                          "CloverMatrix8::mvm_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
+#else
+        mvm_batch(x, t, count);
+        for (uint64_t j = 0; j < count; j++) u[j]->scaleAndAdd(*t[j], a);
+#endif
+    }
+    /* iht_loop for `count` signals with this matrix as Phi (clm8_iht_batch): per iteration every step runs once for a group of signals;
+     * x[j], t1[j], t2[j], t3[j] end as iht_loop(PhiT, *x[j], *y[j], ...) leaves them.  Deterministic rounding only, as iht_loop. */
+    void iht_loop_batch(CloverMatrix8 &PhiT, CloverVector8 *const *x, const CloverVector8 *const *y, CloverVector8 *const *t1,
+                        CloverVector8 *const *t2, CloverVector8 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu,
+                        bool with_threshold)
+    {
+        std::vector<const int8_t *> py(count);
+        std::vector<const float *> psy(count);
+        std::vector<int8_t *> px(count), p1(count), p2(count), p3(count);
+        std::vector<float *> psx(count), ps1(count), ps2(count), ps3(count);
+        for (uint64_t j = 0; j < count; j++) {
+            if (PhiT.getRows() != getCols() || PhiT.getCols() != getRows() || x[j]->size_pad() != getCols() || y[j]->size_pad() != getRows() ||
+                t1[j]->size_pad() != getRows() || t2[j]->size_pad() != getRows() || t3[j]->size_pad() != getCols() || x[j]->size() != x[0]->size()) {
+                std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+                exit(1);
+            }
+            py[j] = y[j]->dev_values_ro();
+            psy[j] = y[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) {
+            px[j] = x[j]->dev_values_wo();
+            psx[j] = x[j]->dev_scales_wo();
+            p1[j] = t1[j]->dev_values_wo();
+            ps1[j] = t1[j]->dev_scales_wo();
+            p2[j] = t2[j]->dev_values_wo();
+            ps2[j] = t2[j]->dev_scales_wo();
+            p3[j] = t3[j]->dev_values_wo();
+            ps3[j] = t3[j]->dev_scales_wo();
+        }
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm8_iht_batch(dev_values(), dev_scales(), PhiT.dev_values(), PhiT.dev_scales(), rows, cols, count, px.data(), psx.data(),
+                                         count ? x[0]->size() : 0, py.data(), psy.data(), p1.data(), ps1.data(), p2.data(), ps2.data(), p3.data(),
+                                         ps3.data(), iterations, K, mu, thr, nullptr, nullptr),
+                          "CloverMatrix8::iht_loop_batch");
+        for (uint64_t j = 0; j < count; j++) {
+            x[j]->commit();
+            if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }
+        }
+    }
+
+private:
+    void check_fused(const CloverVector8 &x, const CloverVector8 &u, const CloverVector8 &t) const
+    {
+        if (x.size() != getCols() || t.size_pad() != getRows()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
+        if (u.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+    }
+    void mvm_batch_at_impl(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
+                           uint64_t commit_draws, bool positioned)
+    {
+        std::vector<const int8_t *> px(count);
+        std::vector<const float *> psx(count);
+        std::vector<int8_t *> pr(count);
+        std::vector<float *> psr(count);
+        for (uint64_t j = 0; j < count; j++) {
+            check_mvm(*x[j], *r[j]);
+            px[j] = x[j]->dev_values_ro();
+            psx[j] = x[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) { pr[j] = r[j]->dev_values_wo(); psr[j] = r[j]->dev_scales_wo(); }
+        uint64_t *rng = clover_hip::rng_or_null(random);
+        if (positioned)
+            clover_hip::check(clm8_mvm_batch_at(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng,
+                                                draw_base, draw_stride, commit_draws, nullptr), "CloverMatrix8::mvm_batch_at");
+        else      /* the launcher may forward groups to the single calls where those were measured faster */
+            clover_hip::check(clm8_mvm_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng, nullptr),
+                              "CloverMatrix8::mvm_batch");
+        for (uint64_t j = 0; j < count; j++) r[j]->commit();
+    }
+
+public:
     /* :480-548: every row wrapped in a non-owning CloverVector8 view over the matrix's own memory and multiplied with dot() (the
      * reference's order), then 64 results at a time quantised by scalar code -- an implementation independent of the mvm kernel */
     void mvm_scalar(const CloverVector8 &productVector, CloverVector8 &resultVector)

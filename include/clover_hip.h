@@ -535,6 +535,27 @@ int  clm4_iht_v8_batch(const int8_t *Phi, const float *sPhi, const int8_t *PhiT,
                     int8_t *const *t1, float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
                     uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream);
 
+/* ---- the same for the pure 8-bit path: CloverMatrix8 x CloverVector8 (02_bit08.cpp), matrix8_batch.hip -------------------------------
+ * The matrix is a CloverMatrix8 image (rows x cols bytes, then one scale per 64 x 64 tile).  Arguments, contract, checks, CLV_MVM_BATCH
+ * and the launch counter are those of the four clm4_*_v8_batch calls above with clm8_mvm, clm8_mvm_scale_and_add and clm8_iht as the
+ * single calls (a plain mvm draws 2 (rows/64) per vector, the fused form 4 (rows/64)); the thresholds of clm8_iht_batch are
+ * clv8_threshold_batch.  No single clm8_iht takes a persistent kernel, so a group of clm8_iht_batch runs batched wherever the fused
+ * mvm does.  Deterministic calls capture into a hipGraph; with an rng the rules of clm8_mvm apply. */
+int  clm8_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
+                    const int8_t *const *x, const float *const *sx, int8_t *const *r, float *const *sr,
+                    uint64_t *rng_state_dev, void *stream);
+int  clm8_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
+                    const int8_t *const *x, const float *const *sx, int8_t *const *r, float *const *sr,
+                    uint64_t *rng_state_dev, uint64_t draw_base, uint64_t draw_stride, uint64_t commit_draws, void *stream);
+int  clm8_mvm_scale_and_add_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
+                    const int8_t *const *x, const float *const *sx, const int8_t *const *qu, const float *const *su, float a,
+                    int8_t *const *t, float *const *st,      /* both arrays NULL: t is not stored */
+                    int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, void *stream);
+int  clm8_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, uint64_t nvec,
+                    int8_t *const *x, float *const *sx, uint64_t x_len, const int8_t *const *y, const float *const *sy,
+                    int8_t *const *t1, float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
+                    uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream);
+
 /* ---- multi-GPU: row-sharded mvm on the GPUs of one node (one process, RCCL over xGMI) --------------- */
 /* MI355X counterpart of mvm_parallel's contiguous split of 64-row blocks over threads
  * (CloverMatrix4.h:1700-1705): shard `part` owns a contiguous multiple of 64 rows, x is replicated, the

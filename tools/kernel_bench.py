@@ -151,9 +151,10 @@ def rounds_of(fn, reps=10, rounds=5, warm=2):
     return sorted(ts)
 
 
-def rec_pair(name, nbytes_single, g, single, batch, reps=10, per=1):
-    """single: the g single calls; batch: the one batch call.  per: divides both (iterations of a loop call)"""
-    if not selected(name):
+def rec_pair(name, nbytes_single, g, single, batch, reps=10, per=1, alias=None):
+    """single: the g single calls; batch: the one batch call.  per: divides both (iterations of a loop call); alias: a second name KB_ONLY
+    may select the row by"""
+    if not (selected(name) or (alias and selected(alias))):
         return
     os.environ.pop("CLV_MVM_BATCH", None)
     one = [t / per for t in rounds_of(single, reps=reps)]
@@ -352,6 +353,98 @@ if any(selected(r) for r in V8_BATCH_ROWS):
                                      (", one generator" if st else "") + "; the single calls are 8 x clm4_iht_v8 as the library runs it")
         del P, sP, PT, sPT, vy, vx, vt1, vt2, vt3, vr
     if ONLY and all(any(o in r for r in V8_BATCH_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
+
+
+# ---- several CloverVector8 with one CloverMatrix8 (matrix8_batch.hip): the pure 8-bit path.  Every row pairs the batch call under
+# CLV_MVM_BATCH=1 with the same vectors issued as single calls (clm8_mvm, clm8_mvm_scale_and_add, clm8_iht) in the same session; the *_st_*
+# twins run with a generator.  The fused rows run at 8192 x 4096 (32 MiB: cache-resident) and at 65536^2 (4 GiB: streamed).
+# KB_ONLY=m8_mvm_batch,m8_iht_batch selects all of them (the m8_mvm_saa_batch rows answer to m8_mvm_batch too) and the run ends after them.
+M8_BATCH_ROWS = tuple(f"m8_mvm_batch{g}_{t}{nb}^2" for nb in (32768, 65536) for g in (2, 4, 8) for t in ("", "st_")) + \
+    tuple(f"m8_mvm_saa_batch{g}_{t}{shape}" for shape in ("8192x4096", "65536^2") for g in (2, 4, 8) for t in ("", "st_")) + \
+    ("m8_iht_batch8_N8192", "m8_iht_batch8_st_N8192")
+
+
+def m8_selected(name):
+    return selected(name) or selected(name.replace("_saa", ""))
+
+
+def m8_matrix(rows, cols, seed):
+    q, s = hip.alloc(rows * cols), hip.alloc(4 * (rows // 64) * (cols // 64))
+    hip.check(lib.clv_fill_random_nibbles(q.ptr, q.nbytes, seed, 0, None))
+    hip.check(lib.clv_fill_random_scales(s.ptr, s.nbytes // 4, seed + 1, 0, None))
+    return q, s
+
+
+if any(m8_selected(r) for r in M8_BATCH_ROWS):
+    for nb in (32768, 65536):
+        if not any(m8_selected(r) for r in M8_BATCH_ROWS if r.endswith(f"_{nb}^2")):
+            continue
+        bA, bsA = m8_matrix(nb, nb, 41)
+        bx, br, bu, bt = vec8_set(8, nb, 300), vec8_set(8, nb, 400), vec8_set(8, nb, 500), vec8_set(8, nb, 600)
+        one_b = nb * nb + 4 * (nb // 64) ** 2 + 2 * (nb + nb // 16)
+        for g in (2, 4, 8):
+            ax, asx, ar, asr = ptrs([v[0] for v in bx[:g]]), ptrs([v[1] for v in bx[:g]]), ptrs([v[0] for v in br[:g]]), ptrs([v[1] for v in br[:g]])
+            au, asu, at, ast = ptrs([v[0] for v in bu[:g]]), ptrs([v[1] for v in bu[:g]]), ptrs([v[0] for v in bt[:g]]), ptrs([v[1] for v in bt[:g]])
+            for tag, st in (("", None), ("st_", hip.new_rng(1, 2))):
+                sp = st.ptr if st else None
+
+                def singles(g=g, sp=sp):
+                    for j in range(g):
+                        hip.check(lib.clm8_mvm(bA.ptr, bsA.ptr, nb, nb, bx[j][0].ptr, bx[j][1].ptr, br[j][0].ptr, br[j][1].ptr, sp, None))
+                rec_pair(f"m8_mvm_batch{g}_{tag}{nb}^2", one_b, g, singles,
+                         lambda g=g, a=(ax, asx, ar, asr), sp=sp: hip.check(lib.clm8_mvm_batch(bA.ptr, bsA.ptr, nb, nb, g, a[0], a[1], a[2], a[3], sp, None)),
+                         reps=10 if nb == 32768 else 4)
+                if nb != 65536:
+                    continue
+
+                def saa_singles(g=g, sp=sp):
+                    for j in range(g):
+                        hip.check(lib.clm8_mvm_scale_and_add(bA.ptr, bsA.ptr, nb, nb, bx[j][0].ptr, bx[j][1].ptr, bu[j][0].ptr, bu[j][1].ptr, 0.002,
+                                                             bt[j][0].ptr, bt[j][1].ptr, br[j][0].ptr, br[j][1].ptr, sp, None))
+                name = f"m8_mvm_saa_batch{g}_{tag}{nb}^2"
+                rec_pair(name, one_b + 3 * (nb + nb // 16), g, saa_singles,
+                         lambda g=g, a=(ax, asx, au, asu, at, ast, ar, asr), sp=sp: hip.check(lib.clm8_mvm_scale_and_add_batch(
+                             bA.ptr, bsA.ptr, nb, nb, g, a[0], a[1], a[2], a[3], 0.002, a[4], a[5], a[6], a[7], sp, None)),
+                         reps=4, alias=name.replace("_saa", ""))
+        del bA, bsA, bx, br, bu, bt
+    # the IHT shape (N = 8192: Phi 4096 x 8192, 32 MiB, cache-resident): the x += mu Phi' t2 step for 2, 4 and 8 signals, and the whole loop for 8
+    im, inn, ig, iters = 4096, 8192, 8, 20
+    if any(m8_selected(r) for r in M8_BATCH_ROWS if r.endswith("8192x4096") or r.endswith("N8192")):
+        (P, sP), PT, sPT = m8_matrix(im, inn, 51), hip.alloc(im * inn), hip.alloc(4 * (im // 64) * (inn // 64))
+        hip.check(lib.clm8_transpose(P.ptr, sP.ptr, im, inn, PT.ptr, sPT.ptr, None))
+        vy, vx, vt1, vt2, vt3, vr = (vec8_set(ig, n, seed) for n, seed in ((im, 500), (inn, 600), (im, 700), (im, 800), (inn, 900), (inn, 1000)))
+        A = {k: (ptrs([p[0] for p in v]), ptrs([p[1] for p in v])) for k, v in dict(y=vy, x=vx, t1=vt1, t2=vt2, t3=vt3, r=vr).items()}
+        saa_b = im * inn + 4 * (im // 64) * (inn // 64) + (im + im // 16) + 3 * (inn + inn // 16)
+        for tag, st in (("", None), ("st_", hip.new_rng(1, 2))):
+            sp = st.ptr if st else None
+            for sg in (2, 4, 8):
+                def saa_singles(sg=sg, sp=sp):
+                    for j in range(sg):
+                        hip.check(lib.clm8_mvm_scale_and_add(PT.ptr, sPT.ptr, inn, im, vt2[j][0].ptr, vt2[j][1].ptr, vx[j][0].ptr, vx[j][1].ptr, 0.002,
+                                                             vt3[j][0].ptr, vt3[j][1].ptr, vr[j][0].ptr, vr[j][1].ptr, sp, None))
+                name = f"m8_mvm_saa_batch{sg}_{tag}8192x4096"
+                rec_pair(name, saa_b, sg, saa_singles,
+                         lambda sg=sg, sp=sp: hip.check(lib.clm8_mvm_scale_and_add_batch(PT.ptr, sPT.ptr, inn, im, sg, A["t2"][0], A["t2"][1], A["x"][0],
+                                                                                         A["x"][1], 0.002, A["t3"][0], A["t3"][1], A["r"][0], A["r"][1],
+                                                                                         sp, None)), reps=20, alias=name.replace("_saa", ""))
+
+            def iht_singles(sp=sp):
+                for j in range(ig):
+                    hip.check(lib.clm8_iht(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, vx[j][0].ptr, vx[j][1].ptr, inn, vy[j][0].ptr, vy[j][1].ptr,
+                                           vt1[j][0].ptr, vt1[j][1].ptr, vt2[j][0].ptr, vt2[j][1].ptr, vt3[j][0].ptr, vt3[j][1].ptr, iters, im // 4, 0.002,
+                                           1, sp, None))
+            name = f"m8_iht_batch8_{tag}N8192"
+            rec_pair(name, 2 * im * inn, ig, iht_singles,
+                     lambda sp=sp: hip.check(lib.clm8_iht_batch(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, ig, A["x"][0], A["x"][1], inn, A["y"][0], A["y"][1],
+                                                                A["t1"][0], A["t1"][1], A["t2"][0], A["t2"][1], A["t3"][0], A["t3"][1], iters, im // 4,
+                                                                0.002, 1, sp, None)), reps=2, per=iters)
+            if name in res:
+                res[name]["note"] = (f"ms per iteration for all 8 signals, calls of {iters} iterations, K = m / 4, FAST threshold" +
+                                     (", one generator" if st else "") + "; the single calls are 8 x clm8_iht (three launches per iteration each)")
+        del P, sP, PT, sPT, vy, vx, vt1, vt2, vt3, vr
+    if ONLY and all(any(o in r or o in r.replace("_saa", "") for r in M8_BATCH_ROWS) for o in ONLY.split(",")):
         print(json.dumps(res, indent=1))
         sys.exit(0)
 
