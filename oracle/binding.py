@@ -318,3 +318,41 @@ class RefXorshift:
 
     def jump(self, s0, s1) -> None:
         self.L.ref_xs_jump(_p(s0, C.POINTER(_u64)), _p(s1, C.POINTER(_u64)))
+
+
+class RefContainers:
+    """The REFERENCE's containers themselves (oracle/_ref/libclover_ref.so and libclover_ref_norng.so = oracle/ref_containers.cpp compiled over
+    the reference's include/Clover*.h with the declarations of oracle/ref_shim/).  Built by `make -C oracle ref` where the reference tree
+    exists; the prebuilt .so travel to the GPU box.  available() is False where neither holds (then only the committed fixtures pin).
+
+    stochastic=False loads the build with -DCLOVER_STOCHASTIC_ROUNDING_DISABLED.  `st` arguments are 32 uint64 (four generators of 8 lanes:
+    random_key1 then random_key2), updated in place; single operations use the first generator only."""
+
+    DIR = _HERE / "_ref"
+
+    @classmethod
+    def path(cls, stochastic: bool) -> Path:
+        return cls.DIR / ("libclover_ref.so" if stochastic else "libclover_ref_norng.so")
+
+    @classmethod
+    def available(cls) -> bool:
+        if not (cls.path(True).exists() and cls.path(False).exists()):
+            subprocess.run(["make", "-C", str(_HERE), "ref"], check=False, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        return cls.path(True).exists() and cls.path(False).exists()
+
+    def __init__(self, stochastic: bool):
+        if not self.available():
+            raise FileNotFoundError(str(self.path(stochastic)))
+        self.L = L = C.CDLL(str(self.path(stochastic)))
+        for name in ("cref_v4_dot", "cref_v8_dot", "cref_v16_dot", "cref_v32_dot"):
+            getattr(L, name).restype = C.c_float
+        assert bool(L.cref_stochastic()) == stochastic
+
+    @staticmethod
+    def _v(a):
+        return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+    def call(self, name: str, *args):
+        """cref_<name> with numpy arrays passed as pointers, Python ints as uint64 and floats as float"""
+        conv = [self._v(a) if isinstance(a, np.ndarray) or a is None else C.c_float(a) if isinstance(a, float) else _u64(a) for a in args]
+        return getattr(self.L, "cref_" + name)(*conv)

@@ -1,8 +1,8 @@
-"""Pins the CPU oracle on the reference's known-answer vectors.
+"""Checks the CPU oracle against the reference's known-answer vectors transcribed in SURVEY.md Appendix D: bytes, scale bits, dot
+bits (SIMD order AND dot_scalar), restore bits, matrix quantize + mvm bytes/scales.
 
-These are the only outputs of the reference's SIMD path available in this image (the reference needs
-IPP/MKL headers to build), so they are the parity anchor: bytes, scale bits, dot bits (SIMD order AND
-dot_scalar), restore bits, matrix quantize + mvm bytes/scales.
+Superseded as the parity anchor by tests/test_reference_fixtures.py, whose fixtures the reference's own container code writes;
+kept as a consistency check (and for dot_scalar, which the fixtures do not hold).
 """
 import json
 from pathlib import Path
