@@ -63,6 +63,28 @@ extern "C" int clm4_iht(const int8_t *Phi, const float *sPhi, const int8_t *PhiT
     return CLV_OK;
 }
 
+// The same loop with ONE matrix: Phi' t2 comes straight from Phi (clm4_mvm_transposed_scale_and_add, mvm_t4.hip), so no PhiT exists.
+// Always the launch-per-step loop -- the persistent kernel keeps both matrices in LDS -- and bit-identical to clm4_iht called with
+// PhiT = transpose(Phi): x, t1 .. t3 and the generator state.
+extern "C" int clm4_iht_one_matrix(const int8_t *Phi, const float *sPhi, uint64_t m, uint64_t n, int8_t *x, float *sx, uint64_t x_len,
+                                   const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3, float *st3,
+                                   uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream)
+{
+    CLV_REQUIRE(Phi && sPhi && x && sx && y && sy && t1 && st1 && t2 && st2 && t3 && st3, "clm4_iht_one_matrix: null pointer");
+    CLV_REQUIRE(m % 128 == 0 && n % 128 == 0 && x_len <= n, "clm4_iht_one_matrix: m=%llu n=%llu x_len=%llu", (unsigned long long)m,
+                (unsigned long long)n, (unsigned long long)x_len);
+    hipLaunchKernelGGL(k_v4_clear, dim3(64), dim3(256), 0, as_stream(stream), (uint32_t *)x, sx, n / 8, n / 64);   // x.clear()
+    CLV_LAUNCH_CHECK();
+    for (uint64_t it = 0; it < iterations; it++) {
+        int rc = clm4_mvm_scale_and_add(Phi, sPhi, m, n, x, sx, y, sy, -1.0f, t1, st1, t2, st2, rng_state_dev, stream);     // t1 = Phi * x; t2 = y - t1
+        if (!rc) rc = clm4_mvm_transposed_scale_and_add(Phi, sPhi, m, n, t2, st2, x, sx, mu, t3, st3, x, sx, rng_state_dev, stream);   // t3 = Phi' * t2; x += mu * t3
+        if (!rc && threshold)
+            rc = clv4_threshold_mode(x, sx, x_len, n, K, threshold == 2 ? CLV_THRESHOLD_REFERENCE : CLV_THRESHOLD_FAST, nullptr, stream);
+        if (rc) return rc;
+    }
+    return CLV_OK;
+}
+
 // Q_IHT / Q_GD for nvec signals with one Phi: the loop above with every step batched.  Arrays are HOST arrays of nvec device pointers.
 // Bit-identical to clm4_iht per vector (which may take the persistent kernel: that one equals the launch-per-step loop bit for bit).
 extern "C" int clm4_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, uint64_t nvec,

@@ -15,6 +15,13 @@ __device__ __forceinline__ void mvm_load(const u32x4 *__restrict__ Ap, int q, ui
     for (int u = 0; u < U; u++) a[u] = NT ? __builtin_nontemporal_load(&Ap[4 * (t0 + u) + q]) : Ap[4 * (t0 + u) + q];
 }
 
+// one link of a chain: the exact integer of a matrix word against its x word (v_dot8_i32_i4), its conversion and one fma with the block
+// factor c.  mvm_consume below applies it to the four words of a lane; k_m4_mvm_t (mvm_t4.hip) to the eight column words of a piece.
+__device__ __forceinline__ float mvm_chain_word(float c, uint32_t a, uint32_t x, float acc)
+{
+    return __builtin_fmaf(c, (float)sdot8(a, x, 0), acc);
+}
+
 // the chain arithmetic of one step on loaded matrix words: per word the exact integer (v_dot8_i32_i4), its conversion and one fma with
 // the block factor c -- the order every mvm kernel of the 4-bit path has to keep
 template <int U>
@@ -25,10 +32,10 @@ __device__ __forceinline__ void mvm_consume(const u32x4 (&a)[U], const u32x4 *xs
     for (int u = 0; u < U; u++) {
         const u32x4 xv = xs[4 * (t0 + u) + q];
         const float c = cs[2 * (t0 + u) + (q >> 1)];
-        a0 = __builtin_fmaf(c, (float)sdot8(a[u].x, xv.x, 0), a0);
-        a1 = __builtin_fmaf(c, (float)sdot8(a[u].y, xv.y, 0), a1);
-        a2 = __builtin_fmaf(c, (float)sdot8(a[u].z, xv.z, 0), a2);
-        a3 = __builtin_fmaf(c, (float)sdot8(a[u].w, xv.w, 0), a3);
+        a0 = mvm_chain_word(c, a[u].x, xv.x, a0);
+        a1 = mvm_chain_word(c, a[u].y, xv.y, a1);
+        a2 = mvm_chain_word(c, a[u].z, xv.z, a2);
+        a3 = mvm_chain_word(c, a[u].w, xv.w, a3);
     }
 }
 

@@ -2,6 +2,7 @@
 // One of the callers either side of the hot path.  With mvm these are the five steps of the reference's quantized IHT / GD
 // iterations (test/performance/01_measure.h:923-946, 999-1021), so x, t1..t3 can stay in HBM across iterations.
 #include "common.h"
+#include "nibble_transpose.h"
 
 // =================================================================================================
 // f2  CloverMatrix4::transpose (CloverMatrix4.h:1549-1663): out(j,i) = in(i,j) nibble-wise, tile scales
@@ -21,37 +22,6 @@
 #define TR_BH 8                      // tiles per XCD block: BH x BW (4x8: 0.214 ms, 8x8: 0.20-0.21, 16x8: 0.21, 8x16: 0.22, 2x16: 0.23 at 32768^2, r4)
 #define TR_BW 8
 #endif
-
-// 8 x 8 nibble transpose: W[r] = the word of input row r (element e at nib_shift(e): EVEN elements in the high nibble of their byte),
-// O[e] = the word of output row e.  In "position" space (position p = bits 4p .. 4p + 3, element e sits at position e ^ 1) this is the
-// plain matrix transpose of the rows taken in the order r ^ 1, read out in the order e ^ 1: the two permutations are register renaming.
-__device__ __forceinline__ void transpose8x8_nibbles(const uint32_t W[8], uint32_t O[8])
-{
-    uint32_t R[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) R[r] = W[r ^ 1];
-#pragma unroll
-    for (int i = 0; i < 8; i += 2) {                                       // nibbles: (row 2i, position 2j + 1) <-> (row 2i + 1, position 2j)
-        const uint32_t a = R[i], b = R[i + 1];
-        R[i] = (a & 0x0F0F0F0Fu) | ((b << 4) & 0xF0F0F0F0u);               // v_lshlrev + v_bfi
-        R[i + 1] = (b & 0xF0F0F0F0u) | ((a >> 4) & 0x0F0F0F0Fu);
-    }
-#pragma unroll
-    for (int r = 0; r < 8; r++)
-        if ((r & 2) == 0) {                                                // bytes: rows r, r + 2
-            const uint32_t a = R[r], b = R[r + 2];
-            R[r] = __builtin_amdgcn_perm(b, a, 0x06020400u);               // [a.b0, b.b0, a.b2, b.b2]
-            R[r + 2] = __builtin_amdgcn_perm(b, a, 0x07030501u);           // [a.b1, b.b1, a.b3, b.b3]
-        }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {                                          // halfwords: rows r, r + 4
-        const uint32_t a = R[r], b = R[r + 4];
-        R[r] = __builtin_amdgcn_perm(b, a, 0x05040100u);                   // [a.lo, b.lo]
-        R[r + 4] = __builtin_amdgcn_perm(b, a, 0x07060302u);               // [a.hi, b.hi]
-    }
-#pragma unroll
-    for (int e = 0; e < 8; e++) O[e] = R[e ^ 1];
-}
 
 template <bool EDGE, bool NT>
 __device__ __forceinline__ void transpose_tile(const uint32_t *__restrict__ q, uint32_t *__restrict__ qt, uint64_t rows, uint64_t cols, uint64_t wcols,

@@ -80,6 +80,41 @@ inline void Q_GD(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 &x, Clov
 }
 
 
+/* Not in the reference: the two loops above with ONE matrix -- the gradient step takes Phi' t2 straight from Phi
+ * (CloverMatrix4::mvm_transposed_scaleAndAdd -> clm4_mvm_transposed_scale_and_add), so no PhiT is built, held or kept in step with Phi.
+ * Rounding disabled: CloverMatrix4::iht_loop_one_matrix -> clm4_iht_one_matrix, the bits of Q_IHT / Q_GD with PhiT = transpose(Phi).
+ * Stochastic: the same calls as above; the gradient step draws from Phi's generator, where the two-matrix loop draws from PhiT's.  The
+ * two-matrix overloads stay the default: what one matrix costs per iteration is measured in DESIGN.md 3. */
+inline void Q_IHT_one_matrix(CloverMatrix4 &Phi, CloverVector4 &x, CloverVector4 &y, CloverVector4 &t1, CloverVector4 &t2, CloverVector4 &t3,
+                             const uint64_t iterations, const uint64_t K, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, K, mu, true);
+    return;
+#endif
+    x.clear();
+    for (uint64_t i = 0; i < iterations; i += 1) {
+        Phi.mvm_scaleAndAdd(x, y, -1.0f, t1, t2);
+        Phi.mvm_transposed_scaleAndAdd(t2, x, mu, t3);
+        x.threshold_parallel(K);
+    }
+}
+
+inline void Q_GD_one_matrix(CloverMatrix4 &Phi, CloverVector4 &x, CloverVector4 &y, CloverVector4 &t1, CloverVector4 &t2, CloverVector4 &t3,
+                            const uint64_t iterations, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, 0, mu, false);
+    return;
+#endif
+    x.clear();
+    for (uint64_t i = 0; i < iterations; i += 1) {
+        Phi.mvm_scaleAndAdd(x, y, -1.0f, t1, t2);
+        Phi.mvm_transposed_scaleAndAdd(t2, x, mu, t3);
+    }
+}
+
+
 /* Not in the reference: Q_IHT / Q_GD for `count` signals with ONE Phi: per iteration two passes over Phi / PhiT for every group of
  * CLM4_MVM_BATCH_MAX signals instead of two per signal.  x[j], t1[j], t2[j], t3[j] end as
  * Q_IHT(Phi, PhiT, *x[j], *y[j], *t1[j], *t2[j], *t3[j], ...) called for signal 0, then 1, ... leaves them, bit for bit, and so do the

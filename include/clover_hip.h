@@ -30,7 +30,8 @@
  *    (rng == NULL); with an rng state the same XORShift stream as the reference's sequential methods is
  *    consumed (bit-identical nibbles for identical keys).  Exceptions are spelled out per function.
  *  - STOCHASTIC CALLS (any function given a non-NULL rng_state_dev: clv4_quantize, clm4_quantize, clm4_mvm, clv4_scale_and_add,
- *    clm4_mvm_scale_and_add, clv8_quantize, clv8_scale_and_add, clm4_mvm_v8, clm4_mvm_v8_scale_and_add, clm4_iht, clm4_iht_v8,
+ *    clm4_mvm_scale_and_add, clm4_mvm_transposed, clm4_mvm_transposed_scale_and_add, clm4_iht_one_matrix, clv8_quantize, clv8_scale_and_add,
+ *    clm4_mvm_v8, clm4_mvm_v8_scale_and_add, clm4_iht, clm4_iht_v8,
  *    clm8_quantize, clm8_mvm, clm8_mvm_scale_and_add, clm8_iht):
  *      (1) calls that share a state buffer must be STREAM-ORDERED -- the same stream, or an event / sync between them: they consume one
  *          sequential XORShift stream, as the reference's methods do on one object, and each launch reads the state its predecessor left;
@@ -284,6 +285,27 @@ int  clv8_threshold_heap(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, 
 /* CloverMatrix4::transpose (CloverMatrix4.h:1549-1663; _parallel :2508-2640): qt(j,i) = q(i,j), tile scales
  * transposed.  q is rows x cols, qt is cols x rows.  Exact. */
 int  clm4_transpose(const int8_t *q, const float *s, uint64_t rows, uint64_t cols, int8_t *qt, float *st, void *stream);
+
+/* The transposed product r = quantize(A' x) straight from A (rows x cols, the stored layout): x has rows elements (rows/2 bytes +
+ * rows/64 scales), r has cols elements (cols/2 bytes + cols/64 scales).  CONTRACT: bit-identical to clm4_transpose(A -> At) followed by
+ * clm4_mvm(At, cols, rows, x -> r) on the same stream; with an rng output block cb takes draws 2 cb, 2 cb + 1 and the state is left
+ * advanced by 2 (cols/64), exactly as clm4_mvm on A' (stream-ordered per state; graph capture as clm4_mvm).  rows and cols are multiples
+ * of 128 (rows == 0 or cols == 0: CLV_OK, nothing done), no pointer is NULL, and r / sr overlap none of A, sA, x, sx: CLV_ERR_INVALID before
+ * any device work otherwise.  No allocation, no workspace: the deterministic call captures into a hipGraph. */
+int  clm4_mvm_transposed(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
+                         int8_t *r, float *sr, uint64_t *rng_state_dev, void *stream);
+/* the fused form, arguments as clm4_mvm_scale_and_add: t = quantize(A' x) (stored if t/st != NULL; both or neither), r = quantize(u + a * t);
+ * u, t, r: cols elements.  r/sr may alias qu/su; no output may overlap anything else.  Bit-identical to clm4_mvm_scale_and_add on a stored
+ * A', including the second draw window 2 G + 2 cb (G = cols/64) and the state advanced by 4 G. */
+int  clm4_mvm_transposed_scale_and_add(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
+                                       const int8_t *qu, const float *su, float a, int8_t *t, float *st, int8_t *r, float *sr,
+                                       uint64_t *rng_state_dev, void *stream);
+/* clm4_iht (below) without the PhiT / sPhiT pair: the launch-per-step loop with Phi' t2 taken from Phi by
+ * clm4_mvm_transposed_scale_and_add, never the persistent kernel.  Bit-identical to clm4_iht called with PhiT = transpose(Phi): x,
+ * t1 .. t3 and the generator state.  Half the resident matrix bytes; what that costs per iteration is measured in DESIGN.md 3. */
+int  clm4_iht_one_matrix(const int8_t *Phi, const float *sPhi, uint64_t m, uint64_t n, int8_t *x, float *sx, uint64_t x_len,
+                         const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3, float *st3,
+                         uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream);
 
 /* mixed precision CloverMatrix4::mvm(const CloverVector32&, CloverVector32&) (CloverMatrix4.h:1451-1547):
  * x: cols floats, r: rows floats (fp32 row dots, no re-quantisation).  Bit-identical (32 fma chains per row). */
