@@ -60,6 +60,13 @@ __device__ __forceinline__ float mvm8_tree(float a_even, float a_odd)
     return ge + go;
 }
 
+// the same tree on the eight chain ends of a row held by ONE lane (k_m4_mvm8_t, mvm_t8.hip), same association
+__device__ __forceinline__ float mvm8_tree8(const float (&a)[8])
+{
+    const float h0 = a[0] + a[4], h1 = a[1] + a[5], h2 = a[2] + a[6], h3 = a[3] + a[7];
+    return (h0 + h2) + (h1 + h3);
+}
+
 // FUSE: the CloverVector8::scaleAndAdd that follows this mvm in the IHT / GD loops, done on the row group while it is still in
 // the wave: r2 = quantize8(u + a * quantize8(A x)); its draws follow ALL the mvm draws in the stream, as in two separate calls.
 struct Mvm8Fuse {

@@ -638,6 +638,76 @@ public:
         u.scaleAndAdd(t, a);
 #endif
     }
+    /* Not in the reference: mvm_transposed and its fused forms for 8-bit vectors (clm4_mvm_v8_transposed, clm4_mvm_v8_transposed_scale_and_add):
+     * resultVector = this' * productVector from this matrix's own bytes, bit for bit what transpose(T); T.mvm(productVector, resultVector)
+     * gives, with stochastic rounding the draws from THIS matrix's generator included. */
+    void mvm_transposed(const CloverVector8 &productVector, CloverVector8 &resultVector)
+    {
+        if (productVector.size() != getRows() || resultVector.size_pad() != getCols()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        clover_hip::check(clm4_mvm_v8_transposed(dev_values(), dev_scales(), rows, cols, productVector.dev_values_ro(), productVector.dev_scales_ro(),
+                                                 resultVector.dev_values_wo(), resultVector.dev_scales_wo(), clover_hip::rng_or_null(random), nullptr),
+                          "CloverMatrix4::mvm_transposed");
+        resultVector.commit();
+    }
+    void check_fused_transposed(const CloverVector8 &x, const CloverVector8 &u, const CloverVector8 &t) const
+    {
+        if (x.size() != getRows() || t.size_pad() != getCols()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
+        if (u.size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+    }
+    void mvm_transposed_scaleAndAdd(const CloverVector8 &x, const CloverVector8 &u, float a, CloverVector8 &t, CloverVector8 &r)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        check_fused_transposed(x, u, t);
+        if (r.size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        clover_hip::check(clm4_mvm_v8_transposed_scale_and_add(dev_values(), dev_scales(), rows, cols, x.dev_values_ro(), x.dev_scales_ro(),
+                                                               u.dev_values_ro(), u.dev_scales_ro(), a, t.dev_values_wo(), t.dev_scales_wo(),
+                                                               r.dev_values_wo(), r.dev_scales_wo(), nullptr, nullptr),
+                          "CloverMatrix4::mvm_transposed_scaleAndAdd");
+        t.commit();
+        r.commit();
+#else
+        mvm_transposed(x, t);
+        const_cast<CloverVector8 &>(u).scaleAndAdd(t, a, r);
+#endif
+    }
+    /* in place: u = quantize(u + a * (this' * x)) */
+    void mvm_transposed_scaleAndAdd(const CloverVector8 &x, CloverVector8 &u, float a, CloverVector8 &t)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        check_fused_transposed(x, u, t);
+        int8_t *qu = u.dev_values_rw();
+        float *su = u.dev_scales_rw();
+        clover_hip::check(clm4_mvm_v8_transposed_scale_and_add(dev_values(), dev_scales(), rows, cols, x.dev_values_ro(), x.dev_scales_ro(), qu, su, a,
+                                                               t.dev_values_wo(), t.dev_scales_wo(), qu, su, nullptr, nullptr),
+                          "CloverMatrix4::mvm_transposed_scaleAndAdd");
+        t.commit();
+        u.commit();
+#else
+        mvm_transposed(x, t);
+        u.scaleAndAdd(t, a);
+#endif
+    }
+    /* iht_loop with CloverVector8 vectors and no PhiT (clm4_iht_v8_one_matrix): always the launch-per-step loop; the bits of iht_loop with
+     * PhiT = transpose of this.  Half the resident matrix bytes; DESIGN.md 3 has what that costs per iteration. */
+    void iht_loop_one_matrix(CloverVector8 &x, const CloverVector8 &y, CloverVector8 &t1, CloverVector8 &t2, CloverVector8 &t3,
+                             uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    {
+        if (x.size_pad() != getCols() || y.size_pad() != getRows() || t1.size_pad() != getRows() || t2.size_pad() != getRows() ||
+            t3.size_pad() != getCols()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm4_iht_v8_one_matrix(dev_values(), dev_scales(), rows, cols, x.dev_values_wo(), x.dev_scales_wo(), x.size(),
+                                                 y.dev_values_ro(), y.dev_scales_ro(), t1.dev_values_wo(), t1.dev_scales_wo(), t2.dev_values_wo(),
+                                                 t2.dev_scales_wo(), t3.dev_values_wo(), t3.dev_scales_wo(), iterations, K, mu, thr, nullptr, nullptr),
+                          "CloverMatrix4::iht_loop_one_matrix");
+        x.commit();
+        if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
+    }
 
     /* mixed precision: fp32 vector in, fp32 vector out (CloverMatrix4.h:1451-1547; _parallel :2397-2505) */
     void mvm(const CloverVector32 &productVector, CloverVector32 &resultVector)

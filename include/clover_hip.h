@@ -13,7 +13,7 @@
  *  - sizes are the PADDED sizes the reference containers hold: vector length_pad (multiple of 128,
  *    CloverVector.h:86-92), matrix rows/cols (multiples of 128, CloverMatrix.h:48-53).  The mvm family (clm4_mvm,
  *    clm4_rowdots, clm4_mvm_scale_and_add, clm4_mvm_v8*, clm4_rowdots_v8, clm4_mvm_f32) also accepts rows % 64 == 0:
- *    a row shard of a matrix, the unit mvm_parallel gives a thread (CloverMatrix4.h:1700-1705).
+ *    a row shard of a matrix, the unit mvm_parallel gives a thread (CloverMatrix4.h:1700-1705); not the *_transposed calls (128 both ways).
  *  - `workspace` arguments: NULL (the library's own scratch of the stream) or device memory of at least the bytes the function's
  *    *_workspace_bytes query returns, 16-BYTE ALIGNED (the kernels access it as float4 / uint64), uninitialised; a misaligned non-NULL
  *    workspace is rejected with CLV_ERR_INVALID before anything touches the device.  A call writes nothing outside its outputs and
@@ -31,7 +31,8 @@
  *    consumed (bit-identical nibbles for identical keys).  Exceptions are spelled out per function.
  *  - STOCHASTIC CALLS (any function given a non-NULL rng_state_dev: clv4_quantize, clm4_quantize, clm4_mvm, clv4_scale_and_add,
  *    clm4_mvm_scale_and_add, clm4_mvm_transposed, clm4_mvm_transposed_scale_and_add, clm4_iht_one_matrix, clv8_quantize, clv8_scale_and_add,
- *    clm4_mvm_v8, clm4_mvm_v8_scale_and_add, clm4_iht, clm4_iht_v8,
+ *    clm4_mvm_v8, clm4_mvm_v8_scale_and_add, clm4_mvm_v8_transposed, clm4_mvm_v8_transposed_scale_and_add, clm4_iht, clm4_iht_v8,
+ *    clm4_iht_v8_one_matrix,
  *    clm8_quantize, clm8_mvm, clm8_mvm_scale_and_add, clm8_iht):
  *      (1) calls that share a state buffer must be STREAM-ORDERED -- the same stream, or an event / sync between them: they consume one
  *          sequential XORShift stream, as the reference's methods do on one object, and each launch reads the state its predecessor left;
@@ -244,6 +245,27 @@ int  clm4_iht_v8(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const
                  int8_t *x, float *sx, uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1,
                  int8_t *t2, float *st2, int8_t *t3, float *st3, uint64_t iterations, uint64_t K, float mu, int threshold,
                  uint64_t *rng_state_dev, void *stream);
+/* The transposed mixed product r = quantize8(A' x) straight from A (rows x cols, the stored 4-bit layout): x is a CloverVector8 of rows
+ * elements (rows bytes + rows/64 scales), r of cols elements (cols bytes + cols/64 scales).  CONTRACT: bit-identical to
+ * clm4_transpose(A -> At) followed by clm4_mvm_v8(At, cols, rows, x -> r) on the same stream; with an rng output block cb takes the draws
+ * clm4_mvm_v8 gives row group cb of At and the state is left advanced by 2 (cols/64) (stream-ordered per state; graph capture as
+ * clm4_mvm_v8).  rows and cols are multiples of 128 (rows == 0 or cols == 0: CLV_OK, nothing done), no pointer is NULL, and r / sr overlap
+ * none of A, sA, x, sx: CLV_ERR_INVALID before any device work otherwise.  No allocation, no workspace: the deterministic call captures
+ * into a hipGraph. */
+int  clm4_mvm_v8_transposed(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
+                            int8_t *r, float *sr, uint64_t *rng_state_dev, void *stream);
+/* the fused form, arguments as clm4_mvm_v8_scale_and_add: t = quantize8(A' x) (stored if t/st != NULL; both or neither),
+ * r = quantize8(u + a * t); u, t, r: cols elements.  r/sr may alias qu/su; no output may overlap anything else.  Bit-identical to
+ * clm4_mvm_v8_scale_and_add on a stored A', including the second draw window behind all G = cols/64 first ones and the state advanced by 4 G. */
+int  clm4_mvm_v8_transposed_scale_and_add(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
+                                          const int8_t *qu, const float *su, float a, int8_t *t, float *st, int8_t *r, float *sr,
+                                          uint64_t *rng_state_dev, void *stream);
+/* clm4_iht_v8 without the PhiT / sPhiT pair: the launch-per-step loop with Phi' t2 taken from Phi by
+ * clm4_mvm_v8_transposed_scale_and_add, never the persistent kernel.  Bit-identical to clm4_iht_v8 called with PhiT = transpose(Phi): x,
+ * t1 .. t3 and the generator state.  Half the resident matrix bytes; what that costs per iteration is measured in DESIGN.md 3. */
+int  clm4_iht_v8_one_matrix(const int8_t *Phi, const float *sPhi, uint64_t m, uint64_t n, int8_t *x, float *sx, uint64_t x_len,
+                            const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3, float *st3,
+                            uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream);
 /* diagnostic: the number of clm4_iht / clm4_iht_v8 calls of this process that ran as ONE persistent launch (iht_persist.hip) rather than
  * as the launch-per-step loop -- what a test or a benchmark reads to know which of the two it measured. */
 uint64_t clv_iht_persistent_launches(void);

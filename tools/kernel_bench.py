@@ -547,6 +547,78 @@ if any(selected(r) for r in MVT_ROWS):
         sys.exit(0)
 
 
+# ---- A' x for CloverVector8 straight from A (mvm_t8.hip): the three rows per size of the block above with clm4_mvm_v8_transposed, clm4_transpose +
+# clm4_mvm_v8 and clm4_mvm_v8 on a held A', rounds alternated in one session; iht_v8_one_matrix_*: clm4_iht_v8_one_matrix against clm4_iht_v8.
+# KB_ONLY=mvm_v8_transposed,transpose_then_mvm_v8,mvm_v8_held_transpose,iht_v8_one_matrix selects them and the run ends after them.
+MVT8_ROWS = tuple(f"{k}_{nb}" for nb in MVT_SIZES for k in ("m4_mvm_v8_transposed", "m4_transpose_then_mvm_v8", "m4_mvm_v8_held_transpose")) + \
+    ("iht_v8_one_matrix_N8192", "iht_v8_one_matrix_gd_32768^2")
+
+if any(selected(r) for r in MVT8_ROWS):
+    for nb in MVT_SIZES:
+        if not any(selected(r) for r in MVT8_ROWS if r.endswith(f"_{nb}")):
+            continue
+        tA, tsA, tAt, tsAt = hip.alloc(nb * nb // 2), hip.alloc(4 * (nb // 64) ** 2), hip.alloc(nb * nb // 2), hip.alloc(4 * (nb // 64) ** 2)
+        hip.check(lib.clv_fill_random_nibbles(tA.ptr, tA.nbytes, 61, 0, None))
+        hip.check(lib.clv_fill_random_scales(tsA.ptr, tsA.nbytes // 4, 62, 0, None))
+        (tx, tsx), (tr, tsr) = vec8_set(1, nb, 310)[0], vec8_set(1, nb, 320)[0]
+        hip.check(lib.clm4_transpose(tA.ptr, tsA.ptr, nb, nb, tAt.ptr, tsAt.ptr, None))
+
+        def direct8():
+            hip.check(lib.clm4_mvm_v8_transposed(tA.ptr, tsA.ptr, nb, nb, tx.ptr, tsx.ptr, tr.ptr, tsr.ptr, None, None))
+
+        def pair8():
+            hip.check(lib.clm4_transpose(tA.ptr, tsA.ptr, nb, nb, tAt.ptr, tsAt.ptr, None))
+            hip.check(lib.clm4_mvm_v8(tAt.ptr, tsAt.ptr, nb, nb, tx.ptr, tsx.ptr, tr.ptr, tsr.ptr, None, None))
+
+        def held8():
+            hip.check(lib.clm4_mvm_v8(tAt.ptr, tsAt.ptr, nb, nb, tx.ptr, tsx.ptr, tr.ptr, tsr.ptr, None, None))
+        d, p, h = alternated((direct8, pair8, held8), reps=20 if nb == 8192 else 10 if nb == 32768 else 4)
+        mat_b = nb * nb // 2 + 4 * (nb // 64) ** 2
+        one_b = mat_b + 2 * (nb + nb // 16)
+        md, mp, mh = d[len(d) // 2], p[len(p) // 2], h[len(h) // 2]
+        for name, t, m, nbytes in ((f"m4_mvm_v8_transposed_{nb}", d, md, one_b), (f"m4_transpose_then_mvm_v8_{nb}", p, mp, 2 * mat_b + one_b),
+                                   (f"m4_mvm_v8_held_transpose_{nb}", h, mh, one_b)):
+            res[name] = {"ms": round(m, 5), "rounds_ms": [round(v, 5) for v in t], "spread_ms": round(t[-1] - t[0], 5),
+                         "GB/s": round(nbytes / m / 1e6, 1), "frac_of_8TBs": round(nbytes / m / 1e6 / 8000.0, 4)}
+        res[f"m4_mvm_v8_transposed_{nb}"].update({
+            "speedup_over_transpose_then_mvm_v8": round(mp / md, 3), "faster_than_the_pair_by_more_than_its_spread": bool(mp - md > p[-1] - p[0]),
+            "ratio_to_mvm_v8_on_a_held_transpose": round(md / mh, 3), "within_the_spread_of_the_held_transpose_call": bool(abs(md - mh) <= h[-1] - h[0])})
+        del tA, tsA, tAt, tsAt
+    for name, im, inn, thr, iters in (("iht_v8_one_matrix_N8192", 4096, 8192, 1, 20), ("iht_v8_one_matrix_gd_32768^2", 32768, 32768, 0, 4)):
+        if not selected(name):
+            continue
+        P, sP, PT, sPT = hip.alloc(im * inn // 2), hip.alloc(4 * (im // 64) * (inn // 64)), hip.alloc(im * inn // 2), hip.alloc(4 * (im // 64) * (inn // 64))
+        hip.check(lib.clv_fill_random_nibbles(P.ptr, P.nbytes, 63, 0, None))
+        hip.check(lib.clv_fill_random_scales(sP.ptr, sP.nbytes // 4, 64, 0, None))
+        hip.check(lib.clm4_transpose(P.ptr, sP.ptr, im, inn, PT.ptr, sPT.ptr, None))
+        (vy, vx, vt1, vt2, vt3) = (vec8_set(1, n, seed)[0] for n, seed in ((im, 500), (inn, 600), (im, 700), (im, 800), (inn, 900)))
+        tail = (vx[0].ptr, vx[1].ptr, inn, vy[0].ptr, vy[1].ptr, vt1[0].ptr, vt1[1].ptr, vt2[0].ptr, vt2[1].ptr, vt3[0].ptr, vt3[1].ptr, iters, im // 4,
+                0.002, thr, None, None)
+
+        def two8():
+            hip.check(lib.clm4_iht_v8(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, *tail))
+
+        def two8_loop():
+            os.environ["CLV_IHT_PERSISTENT"] = "0"
+            try:
+                hip.check(lib.clm4_iht_v8(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, *tail))
+            finally:
+                os.environ.pop("CLV_IHT_PERSISTENT", None)
+
+        def one8():
+            hip.check(lib.clm4_iht_v8_one_matrix(P.ptr, sP.ptr, im, inn, *tail))
+        t2, tl, t1 = ([v / iters for v in t] for t in alternated((two8, two8_loop, one8), reps=2))
+        res[name] = {"one_matrix_ms_per_iteration": round(t1[len(t1) // 2], 5), "clm4_iht_v8_ms_per_iteration": round(t2[len(t2) // 2], 5),
+                     "clm4_iht_v8_launch_per_step_ms_per_iteration": round(tl[len(tl) // 2], 5),
+                     "one_matrix_rounds_ms": [round(v, 5) for v in t1], "clm4_iht_v8_rounds_ms": [round(v, 5) for v in t2],
+                     "clm4_iht_v8_launch_per_step_rounds_ms": [round(v, 5) for v in tl],
+                     "note": f"calls of {iters} iterations, K = m / 4, threshold = {thr}; clm4_iht_v8 as it dispatches by itself, and with CLV_IHT_PERSISTENT=0"}
+        del P, sP, PT, sPT
+    if ONLY and all(any(o in r for r in MVT8_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
+
+
 # ---- vector ops at n = 2^30 (4 GiB fp32 source, 512 MiB + 64 MiB quantized) and n = 2^24
 for logn in (24, 30):
     n = 1 << logn
