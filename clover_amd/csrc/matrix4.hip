@@ -25,6 +25,31 @@
 
 #define MVM_CHUNK 65536u   // columns staged in LDS per pass
 
+#ifdef CLV_EXPERIMENTS
+// launch timeline (probe build only, tools/mvm_timeline.py): lane 0 of every wave writes the device wall clock (s_memrealtime, 100 MHz)
+// into slot p of its 8 words of the caller's buffer; the entry stamp also leaves the wave's HW_ID and XCC_ID registers in slots 5 and 6,
+// from which the driver tells the CUs apart.  Instantiations with STAMP are measured only with the stamps.
+#define MVM_STAMP_ENTRY 0
+#define MVM_STAMP_STAGED 1
+#define MVM_STAMP_FIRST 2
+#define MVM_STAMP_LAST 3
+#define MVM_STAMP_EXIT 4
+__device__ __forceinline__ void mvm_stamp(uint64_t *buf, int p)
+{
+    if ((threadIdx.x & 63) == 0) {
+        uint64_t *w = buf + ((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 8;
+        w[p] = __builtin_amdgcn_s_memrealtime();
+        if (p == MVM_STAMP_ENTRY) {
+            w[5] = __builtin_amdgcn_s_getreg(4 | (31 << 11));       // HW_REG_HW_ID
+            w[6] = __builtin_amdgcn_s_getreg(20 | (31 << 11));      // HW_REG_XCC_ID
+        }
+    }
+}
+#define MVM_STAMP(buf, p) do { if constexpr (STAMP) mvm_stamp(buf, p); } while (0)
+#else
+#define MVM_STAMP(buf, p) do { } while (0)
+#endif
+
 // 8 lanes per row (lane e owns chains 2e, 2e+1 and loads 8 bytes per step): twice the waves per workgroup, for
 // matrices with too few 64-row groups to fill the chip with 4-wave workgroups
 template <int U, bool NT>
@@ -48,7 +73,8 @@ __device__ __forceinline__ void mvm_steps8(const u32x2 *__restrict__ Ap, const u
 // group g of AVX lane j lands on row 8j+g: row l uses group g = l&7 (draw g>>2, byte g&3) of word W[l>>3].
 // With FUSE the scaleAndAdd draws follow ALL the mvm draws in the stream, as in the two separate calls: row group rb
 // then uses draws 2G + 2rb, 2G + 2rb + 1 (G = number of row groups), with the scaleAndAdd lane map 8j + (g ^ 1).
-template <int U, bool NT, bool ST, bool FUSE, int L = 4>
+// STAMP (probe build, ST == false): rng_state, unused without a generator, carries the buffer of the launch timeline.
+template <int U, bool NT, bool ST, bool FUSE, int L = 4, bool STAMP = false>
 __global__ __launch_bounds__(64 * L) void k_m4_mvm64(const uint8_t *__restrict__ A, const float *__restrict__ sA,
                                                   uint64_t cols, const uint8_t *__restrict__ x, const float *__restrict__ sx,
                                                   float *__restrict__ d_out, uint32_t *r, float *sr,
@@ -61,6 +87,8 @@ __global__ __launch_bounds__(64 * L) void k_m4_mvm64(const uint8_t *__restrict__
     uint64_t *rbase = reinterpret_cast<uint64_t *>(dsh + 64);           // ST: 4 lane bases, 8 raw draws (twice with FUSE)
     uint64_t *raw = rbase + 4;
     uint64_t *rbase2 = raw + 8, *raw2 = rbase2 + 4;
+    static_assert(!(STAMP && ST), "the timeline buffer travels in rng_state");
+    MVM_STAMP(rng_state, MVM_STAMP_ENTRY);
     if (ST) {
         const uint64_t a0 = rng_workgroup_begin(rng_state, seq, pow_rows, blockIdx.x, 1, (FUSE ? 4ull : 2ull) * gridDim.x, rbase);
         if (FUSE) {
@@ -114,6 +142,7 @@ __global__ __launch_bounds__(64 * L) void k_m4_mvm64(const uint8_t *__restrict__
             for (int k = 0; k < NC; k++) { const uint32_t i = tid + THREADS * k; if (i < nc) cs[i] = (sa[k] * CLV_RCP49) * sv[k]; }
         }
         __syncthreads();
+        if (c0 == 0) MVM_STAMP(rng_state, MVM_STAMP_STAGED);
 
         // (a register double-buffered variant -- next U loads requested before the current U are consumed -- was
         //  measured slower at every size: it costs the fourth wave per SIMD; r01 microbench variants 5-7)
@@ -121,6 +150,13 @@ __global__ __launch_bounds__(64 * L) void k_m4_mvm64(const uint8_t *__restrict__
         const uint32_t npairs = cw / 128;
         uint32_t t = 0;
         if constexpr (L == 4) {
+            if constexpr (STAMP) {      // the first step on its own, so that the loop below is the unstamped kernel's
+                if (c0 == 0 && U <= npairs) {
+                    mvm_steps<U, NT>(Ap, xs, cs, q, t, a0, a1, a2, a3);
+                    t = U;
+                    MVM_STAMP(rng_state, MVM_STAMP_FIRST);
+                }
+            }
             for (; t + U <= npairs; t += U) mvm_steps<U, NT>(Ap, xs, cs, q, t, a0, a1, a2, a3);
             for (; t < npairs; t++) mvm_steps<1, NT>(Ap, xs, cs, q, t, a0, a1, a2, a3);
         } else {
@@ -132,6 +168,7 @@ __global__ __launch_bounds__(64 * L) void k_m4_mvm64(const uint8_t *__restrict__
     }
 
     float dot = mvm_tree(a0, a1, a2, a3);
+    MVM_STAMP(rng_state, MVM_STAMP_LAST);
     if constexpr (L == 8) {
         // chain 2q+i: accumulator a = q>>2, AVX lane w = 2(q&3)+i.  Same tree: acc[0][w]+acc[1][w] (lanes q, q^4), then
         // v[w]+v[w+4] (q, q^2) gives x[2(q&1)+i], then (x0+x2)+(x1+x3) (q, q^1)
@@ -170,6 +207,115 @@ __global__ __launch_bounds__(64 * L) void k_m4_mvm64(const uint8_t *__restrict__
             requantize_wave(val, noise2, fuse.r2 + rb * 8, fuse.sr2 + rb, &m2);
         }
     }
+    MVM_STAMP(rng_state, MVM_STAMP_EXIT);
+}
+
+// ================================================================================================
+// mvm, one workgroup per CU: the single-round streaming shapes (2 CUs < rows / 64 <= 4 CUs, no generator)
+// ================================================================================================
+// k_m4_mvm64 serves those shapes with up to four workgroups per CU, all resident at once: each stages its own copy of the x chunk
+// (4 x 36 KiB of LDS writes per CU at the start of the launch, three quarters of them redundant), and nothing holds the CU's 16 waves
+// together.  Here ONE workgroup of 256 G threads (G = 3, 4) takes G consecutive 64-row groups: thread tid belongs to group g = tid >> 8
+// and maps inside it as in k_m4_mvm64 (t = tid & 255: row t >> 2, quarter t & 3, chains 4q..4q+3, nontemporal 16-byte loads, eight steps
+// in flight).  LDS holds one image of the x chunk, staged by all threads, G arrays of c[b] (one per group, the same expression) and
+// G x 64 dots.  The chain arithmetic, the tree and the epilogue are the helpers of mvm_device.h, so the bits are k_m4_mvm64's.
+// K > 0: a workgroup barrier every K outer iterations keeps the CU's waves within K iterations of each other (the trip count depends on
+// the chunk width alone, so every wave meets every barrier).  A group beyond `groups` (the ragged last workgroup) touches neither the
+// matrix, its scales nor a result -- a wave-uniform predicate -- but stages its share of x and takes part in every barrier.
+#define MVM_CU_LDS_BYTES(G) (MVM_CHUNK / 2 + (G) * (MVM_CHUNK / 64) * sizeof(float) + (G) * 64 * sizeof(float))
+
+template <int G, bool FUSE, int K, bool STAMP = false>
+__global__ __launch_bounds__(256 * G) void k_m4_mvm_cu(const uint8_t *__restrict__ A, const float *__restrict__ sA, uint32_t groups,
+                                                       uint64_t cols, const uint8_t *__restrict__ x, const float *__restrict__ sx,
+                                                       float *__restrict__ d_out, uint32_t *r, float *sr, MvmFuse fuse, uint64_t *stamps)
+{
+    static_assert(G == 3 || G == 4, "three or four row groups per workgroup");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    MVM_STAMP(stamps, MVM_STAMP_ENTRY);
+    constexpr int THREADS = 256 * G;
+    const int tid = threadIdx.x;
+    const int g = tid >> 8, t = tid & 255;
+    u32x4 *xs = reinterpret_cast<u32x4 *>(smem);                                            // MVM_CHUNK/2 bytes, shared by the G groups
+    float *cs = reinterpret_cast<float *>(smem + MVM_CHUNK / 2) + g * (MVM_CHUNK / 64);    // this group's MVM_CHUNK/64 factors
+    float *dsh = reinterpret_cast<float *>(smem + MVM_CHUNK / 2) + G * (MVM_CHUNK / 64) + g * 64;
+
+    const uint32_t rb = blockIdx.x * G + g;
+    const bool live = rb < groups;                      // uniform per wave (a group is four whole waves)
+    const uint64_t rbl = live ? rb : 0;                 // addresses of an idle group are formed, never used
+    const int q = t & 3, rho = t >> 2;
+    const uint64_t row = rbl * 64 + rho;
+    const u32x4 *Arow = reinterpret_cast<const u32x4 *>(A + row * (cols / 2));
+    const float *sArow = sA + rbl * (cols / 64);
+
+    // FUSE: this row group's block of u, fetched now so that the epilogue does not wait for it
+    uint32_t fuse_w = 0;
+    float fuse_s = 0.0f;
+    if (FUSE && live && t < 64) {
+        fuse_w = fuse.qu[rbl * 8 + (t >> 3)];
+        fuse_s = fuse.su[rbl];
+    }
+
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+
+    for (uint64_t c0 = 0; c0 < cols; c0 += MVM_CHUNK) {
+        const uint32_t cw = (uint32_t)((cols - c0) < MVM_CHUNK ? (cols - c0) : MVM_CHUNK);
+        if (c0) __syncthreads();
+        // stage x (once per workgroup) and c[b] (once per group): all loads first, then the LDS writes, as in k_m4_mvm64
+        const u32x4 *xg = reinterpret_cast<const u32x4 *>(x + c0 / 2);
+        {
+            constexpr int NX = (MVM_CHUNK / 32 + THREADS - 1) / THREADS;      // 16 B per thread: 2 (G = 4), 3 (G = 3)
+            constexpr int NC = MVM_CHUNK / 64 / 256;                          // 4 factors per thread of the group
+            u32x4 xr[NX];
+            float sa[NC], sv[NC];
+            const uint32_t nx = cw / 32, nc = cw / 64;
+#pragma unroll
+            for (int k = 0; k < NX; k++) { const uint32_t i = tid + THREADS * k; xr[k] = xg[i < nx ? i : 0]; }
+#pragma unroll
+            for (int k = 0; k < NC; k++) {
+                const uint32_t i = t + 256 * k, ii = i < nc ? i : 0;
+                sa[k] = live ? sArow[c0 / 64 + ii] : 0.0f;
+                sv[k] = sx[c0 / 64 + ii];
+            }
+#pragma unroll
+            for (int k = 0; k < NX; k++) { const uint32_t i = tid + THREADS * k; if (i < nx) xs[i] = xr[k]; }
+#pragma unroll
+            for (int k = 0; k < NC; k++) { const uint32_t i = t + 256 * k; if (i < nc) cs[i] = (sa[k] * CLV_RCP49) * sv[k]; }
+        }
+        __syncthreads();
+        if (c0 == 0) MVM_STAMP(stamps, MVM_STAMP_STAGED);
+
+        const u32x4 *Ap = Arow + c0 / 32;
+        const uint32_t npairs = cw / 128;
+        uint32_t tp = 0, it = 0;
+        for (; tp + 8 <= npairs; tp += 8) {
+            if (live) mvm_steps<8, true>(Ap, xs, cs, q, tp, a0, a1, a2, a3);
+            if (c0 == 0 && tp == 0) MVM_STAMP(stamps, MVM_STAMP_FIRST);
+            if constexpr (K > 0) {
+                if (++it == K) { it = 0; __builtin_amdgcn_s_barrier(); }     // lockstep only: no LDS is written inside the loop
+            }
+        }
+        if (live)
+            for (; tp < npairs; tp++) mvm_steps<1, true>(Ap, xs, cs, q, tp, a0, a1, a2, a3);
+    }
+
+    const float dot = mvm_tree(a0, a1, a2, a3);
+    MVM_STAMP(stamps, MVM_STAMP_LAST);
+    if (live && q == 0) {
+        dsh[rho] = dot;
+        if (d_out) d_out[row] = dot;
+    }
+    __syncthreads();
+    if (live && (r || FUSE) && t < 64) {                 // wave 0 of the group's four
+        float m;
+        const int qv = requantize_wave(dsh[t], 0.0f, r ? r + rbl * 8 : nullptr, r ? sr + rbl : nullptr, &m);
+        if (FUSE) {
+            const float su7 = div7(fuse_s), sv7 = div7(m * fuse.a);
+            const float val = __builtin_fmaf((float)qv, sv7, (float)unpack1(fuse_w, t & 7) * su7);
+            float m2;
+            requantize_wave(val, 0.0f, fuse.r2 + rbl * 8, fuse.sr2 + rbl, &m2);
+        }
+    }
+    MVM_STAMP(stamps, MVM_STAMP_EXIT);
 }
 
 // ================================================================================================
@@ -288,6 +434,36 @@ int clm4_gemm_fp6(const int8_t *A, const float *sA, uint64_t M, uint64_t K, cons
 
 #define MVM_LDS_BYTES (MVM_CHUNK / 2 + (MVM_CHUNK / 64) * sizeof(float) + 64 * sizeof(float) + 256)
 
+// k_m4_mvm_cu's shapes: streaming (the 256 MiB rule below), no generator, 2 CUs < rows / 64 <= 4 CUs.  Returns the row groups per
+// workgroup, G = ceil((rows / 64) / CUs) = 3 or 4, or 0 for every other call
+static int mvm_cu_groups_per_workgroup(uint64_t rows, uint64_t cols, bool with_rng)
+{
+    const uint64_t groups = rows / 64, cus = (uint64_t)clv_cu_count();
+    if (with_rng || rows * (cols / 2) <= (256ull << 20) || groups <= 2 * cus || groups > 4 * cus) return 0;
+    return (int)((groups + cus - 1) / cus);
+}
+
+// lockstep barrier of k_m4_mvm_cu every MVM_CU_K outer iterations; 0 = none, the fastest of none / 4 / 16 at 65536^2 (320.6 / 328.7 /
+// 322.5 us; DESIGN 3 "The single-round launch")
+#define MVM_CU_K 0
+
+template <int K, bool STAMP>
+static void launch_mvm_cu(int G, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx, float *d,
+                          int8_t *r, float *sr, const MvmFuse *fuse, uint64_t *stamps, hipStream_t st)
+{
+    const uint32_t groups = (uint32_t)(rows / 64);
+    const MvmFuse no_fuse = {nullptr, nullptr, 0.0f, nullptr, nullptr};
+#define MVM_CU_LAUNCH(G_, FUSE)                                                                                                           \
+    hipLaunchKernelGGL((k_m4_mvm_cu<G_, FUSE, K, STAMP>), dim3((groups + G_ - 1) / G_), dim3(256 * G_), MVM_CU_LDS_BYTES(G_), st,         \
+                       (const uint8_t *)A, sA, groups, cols, (const uint8_t *)x, sx, d, (uint32_t *)r, sr, FUSE ? *fuse : no_fuse, stamps)
+    if (G == 4) {
+        if (fuse) MVM_CU_LAUNCH(4, true); else MVM_CU_LAUNCH(4, false);
+    } else {
+        if (fuse) MVM_CU_LAUNCH(3, true); else MVM_CU_LAUNCH(3, false);
+    }
+#undef MVM_CU_LAUNCH
+}
+
 static int launch_mvm(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
                       float *d, int8_t *r, float *sr, uint64_t *rng, hipStream_t st, const MvmFuse *fuse = nullptr)
 {
@@ -315,7 +491,13 @@ static int launch_mvm(const int8_t *A, const float *sA, uint64_t rows, uint64_t 
     // few row groups (<= 2 per CU) of a matrix that streams from HBM: 8 lanes per row double the waves in flight
     // (32768^2: 92 -> 89 us); measured no better anywhere else (r01 microbench variants 7-10)
     const bool wide = streaming && !rng && rows / 64 <= 2ull * (uint64_t)clv_cu_count();
-    if (wide) {
+    // more than 2 and at most 4 row groups per CU: the four-wave kernel would run them as ONE round of resident workgroups; one
+    // workgroup per CU with a shared x image does (k_m4_mvm_cu).  Beyond 4 per CU later rounds hide a workgroup's prologue and
+    // epilogue behind its neighbours, which one workgroup per CU would expose: those stay on k_m4_mvm64
+    const int cu_g = mvm_cu_groups_per_workgroup(rows, cols, rng != nullptr);
+    if (cu_g) {
+        launch_mvm_cu<MVM_CU_K, false>(cu_g, A, sA, rows, cols, x, sx, d, r, sr, fuse, nullptr, st);
+    } else if (wide) {
         if (fuse)
             hipLaunchKernelGGL((k_m4_mvm64<16, true, false, true, 8>), grid, dim3(512), lds, st, (const uint8_t *)A, sA, cols,
                                (const uint8_t *)x, sx, d, (uint32_t *)r, sr, rng, seq, T.pow_rows, *fuse);
@@ -390,6 +572,45 @@ extern "C" int clvx_mvm_variant(int variant, const int8_t *A, const float *sA, u
     default: clv_set_error("clvx_mvm_variant: unknown variant %d", variant); return CLV_ERR_INVALID;
     }
 #undef CLVX_LAUNCH
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+
+// k_m4_mvm_cu with the lockstep barrier every K = 0 (none), 4 or 16 outer iterations, on a shape with 2 CUs < rows / 64 <= 4 CUs;
+// clvx_mvm_variant(0, ...) is the parent kernel for the same shape, so the two are an A/B inside one process.  stamps != NULL: the
+// stamped instantiation (8 words per wave, 4 G waves per workgroup, the idle ones of a ragged last workgroup included)
+extern "C" int clvx_mvm_cu(int K, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
+                           int8_t *r, float *sr, uint64_t *stamps, void *stream)
+{
+    const uint64_t groups = rows / 64, cus = (uint64_t)clv_cu_count();
+    CLV_REQUIRE(rows % 64 == 0 && cols % 128 == 0 && groups > 2 * cus && groups <= 4 * cus, "clvx_mvm_cu: rows / 64 = %llu is not in (2, 4] CUs",
+                (unsigned long long)groups);
+    const int G = (int)((groups + cus - 1) / cus);
+    hipStream_t st = as_stream(stream);
+#define CLVX_CU(K_)                                                                                             \
+    do {                                                                                                        \
+        if (stamps) launch_mvm_cu<K_, true>(G, A, sA, rows, cols, x, sx, nullptr, r, sr, nullptr, stamps, st);  \
+        else launch_mvm_cu<K_, false>(G, A, sA, rows, cols, x, sx, nullptr, r, sr, nullptr, nullptr, st);       \
+    } while (0)
+    switch (K) {
+    case 0: CLVX_CU(0); break;
+    case 4: CLVX_CU(4); break;
+    case 16: CLVX_CU(16); break;
+    default: clv_set_error("clvx_mvm_cu: K = %d is not instantiated", K); return CLV_ERR_INVALID;
+    }
+#undef CLVX_CU
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+
+// the parent kernel of those shapes, k_m4_mvm64<8, true, false, false>, with the timeline stamps (8 words per wave, rows / 64 * 4 waves)
+extern "C" int clvx_mvm64_stamped(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx, int8_t *r,
+                                  float *sr, uint64_t *stamps, void *stream)
+{
+    CLV_REQUIRE(stamps && rows % 64 == 0 && cols % 128 == 0, "clvx_mvm64_stamped: bad arguments");
+    hipLaunchKernelGGL((k_m4_mvm64<8, true, false, false, 4, true>), dim3((unsigned)(rows / 64)), dim3(256), MVM_LDS_BYTES, as_stream(stream),
+                       (const uint8_t *)A, sA, cols, (const uint8_t *)x, sx, (float *)nullptr, (uint32_t *)r, sr, stamps, 0ull,
+                       (const uint64_t *)nullptr, MvmFuse{nullptr, nullptr, 0.0f, nullptr, nullptr});
     CLV_LAUNCH_CHECK();
     return CLV_OK;
 }

@@ -29,7 +29,7 @@ res = {"_how": "rocprofv3 --pmc <one counter> --output-format csv -- python tool
 rows = cols = 65536
 alg = rows * cols // 2 + 4 * (rows // 64) * (cols // 64) + (cols // 2 + cols // 16) + (rows // 2 + rows // 16)
 for k, c in kernels.items():
-    if k.startswith("k_m4_mvm64") and "FETCH_SIZE" in c:
+    if k.startswith(("k_m4_mvm64", "k_m4_mvm_cu")) and "FETCH_SIZE" in c:      # whichever of the two clm4_mvm launched at C3
         rd = c["FETCH_SIZE"]["avg"] * 1024 * factor
         wr = c.get("WRITE_SIZE", {}).get("avg", 0.0) * 1024
         res["mvm_c3"] = {"rows": rows, "cols": cols, "kernel": k, "algorithmic_bytes": alg, "hbm_read_bytes": rd, "hbm_write_bytes": wr,

@@ -80,4 +80,36 @@ for (rows, cols) in SIZES:
             ref = got
         res[f"mvm_{rows}x{cols}_v{v}" + ("_cold" if nmat > 1 else "")] = {"us": round(ms * 1e3, 2), "GB/s": round(mvm_bytes(rows, cols) / ms / 1e6, 1),
                                                                          "same_as_v0": got == ref if nmat == 1 else None}
+    # MB_CU="0,4,16": k_m4_mvm_cu with the lockstep barrier every K outer iterations beside its parent (variant 0) on the shapes it takes
+    # (2 CUs < rows / 64 <= 4 CUs), the candidates ALTERNATING round by round so that drift hits all of them alike; per candidate the
+    # median, smallest and largest of MB_CU_ROUNDS (default 7) rounds of 20 calls
+    cus = hip.device_info()["compute_units"]
+    if os.environ.get("MB_CU") and 2 * cus < rows // 64 <= 4 * cus:
+        lib.clvx_mvm_cu.argtypes = [C.c_int, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp]
+        cands = [("parent", lambda: hip.check(lib.clvx_mvm_variant(0, big.ptr, sA.ptr, rows, cols, x.ptr, sx.ptr, r.ptr, sr.ptr, None)))]
+        for k in (int(v) for v in os.environ["MB_CU"].split(",")):
+            cands.append((f"cu_K{k}", lambda k=k: hip.check(lib.clvx_mvm_cu(k, big.ptr, sA.ptr, rows, cols, x.ptr, sx.ptr, r.ptr, sr.ptr, None, None))))
+        a, b = vp(), vp()
+        hip.check(lib.clv_event_create(C.byref(a)))
+        hip.check(lib.clv_event_create(C.byref(b)))
+        got, ts = {}, {name: [] for name, _ in cands}
+        for name, fn in cands:
+            hip.check(lib.clv_memset(r.ptr, 0x5A, r.nbytes, None))
+            for _ in range(3):
+                fn()
+            got[name] = (r.download(np.uint8).tobytes(), sr.download(np.float32).tobytes())
+        for _ in range(int(os.environ.get("MB_CU_ROUNDS", "7"))):
+            for name, fn in cands:
+                hip.check(lib.clv_event_record(a, None))
+                for _ in range(20):
+                    fn()
+                hip.check(lib.clv_event_record(b, None))
+                hip.check(lib.clv_event_sync(b))
+                ms = C.c_float()
+                hip.check(lib.clv_event_elapsed_ms(a, b, C.byref(ms)))
+                ts[name].append(ms.value / 20)
+        for name, _ in cands:
+            t = sorted(ts[name])
+            res[f"mvm_{rows}x{cols}_{name}"] = {"us": round(t[len(t) // 2] * 1e3, 2), "min_us": round(t[0] * 1e3, 2), "max_us": round(t[-1] * 1e3, 2),
+                                                "GB/s": round(mvm_bytes(rows, cols) / t[len(t) // 2] / 1e6, 1), "same_as_parent": got[name] == got["parent"]}
 print(json.dumps(res, indent=1))
