@@ -79,10 +79,12 @@ uint64_t clv_internal_dot_chain_bytes(uint64_t steps);
 int clv_internal_dot_chain(const void *X, uint64_t blocks_padded, float *out_dev, hipStream_t st);
 // CloverVector8::clear() as one launch (mixed8.hip): bytes 0, scales 1.0; first step of clm4_iht_v8 and clm8_iht
 int clv_internal_v8_clear(int8_t *x, float *sx, uint64_t n_pad, hipStream_t st);
+// CloverVector4::clear() as one launch (iht4.hip): nibbles 0, scales 1.0; first step of clm4_iht and clm4_iht_one_matrix
+int clv_internal_v4_clear(int8_t *x, float *sx, uint64_t n_pad, hipStream_t st);
 // zero-initialised hand-over slots per (device, stream), <= 64 KiB; every user leaves them zero again (runtime.hip)
 int clv_internal_sync_slots(void **ptr, uint64_t bytes, hipStream_t stream);
 
-// the batch calls (mvm_batch4.hip, threshold4.hip, iht4.hip) take host arrays of device pointers: no output range may overlap an input
+// the batch calls (mvm_batch_host.h, threshold4.hip) take host arrays of device pointers: no output range may overlap an input
 // range of ANY vector of the call (another workgroup may still be reading it) and no two outputs may overlap.  One exception the caller
 // expresses by leaving the input out: an in-place result, which IS its input.  Empty ranges never overlap anything.
 struct ClvRange {
@@ -95,23 +97,7 @@ static inline ClvRange clv_range(const void *p, uint64_t bytes, bool output, uin
 {
     return ClvRange{(uintptr_t)p, (uintptr_t)p + bytes, output, vec, name};
 }
-// mvm_batch4.hip: the launches of clm4_mvm_batch (qu == NULL) / clm4_mvm_scale_and_add_batch on CHECKED arguments; r / sr NULL: the mvm
-// result is not stored (fused form only).  rng != NULL: stochastic, the groups in stream order from the state the call finds.
-int clv_internal_mvm_batch_run(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
-                               const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
-                               float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, void *stream);
-// the same, ALWAYS on the batched kernel, with vector j's draws draw_base + j * draw_stride behind the state the call finds and the state
-// advanced by commit_draws at the end (0: left as it is); the positions have passed clv_internal_first_bad_window
-int clv_internal_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
-                              const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
-                              float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, uint64_t draw_base, uint64_t draw_stride,
-                              uint64_t commit_draws, void *stream);
-// mvm_batch8.hip: the same for CloverVector8 vectors (clm4_mvm_v8_batch_at / the fused form), always on the batched kernel
-int clv_internal_mvm_v8_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
-                                 const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
-                                 float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, uint64_t draw_base, uint64_t draw_stride,
-                                 uint64_t commit_draws, void *stream);
-void clv_internal_mvm_batch_count(void);      // mvm_batch4.hip: one more batched launch, of either vector type (clv_mvm_batch_launches)
+void clv_internal_mvm_batch_count(void);      // mvm_batch4.hip: one more batched launch, of any family (clv_mvm_batch_launches)
 // iht_persist.hip: whether a single clm4_iht_v8 with these arguments takes the persistent kernel k_iht8_persist
 bool clm4_iht_v8_persistent_eligible(uint64_t m, uint64_t n, uint64_t iterations, int threshold, bool stochastic);
 uint64_t clv_internal_first_bad_window(uint64_t nvec, uint64_t draw_base, uint64_t draw_stride, uint64_t window);

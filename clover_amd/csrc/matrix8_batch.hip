@@ -5,10 +5,8 @@
 // of a lane once and runs, per vector and block, one 16-byte LDS read of x, one of the factor, four v_dot4_i32_i8, two converts and two
 // fmas.  Each vector's instruction sequence is the one of m8_mvm_body (matrix8.hip), so the results equal the single calls bit for bit;
 // the re-quantisation and the scaleAndAdd behind it are mvm8_requantize_wave (mvm8_device.h), the same arithmetic as k_m8_mvm_saa's.
-#include "mvm_batch_device.h"
+#include "mvm_batch_host.h"
 #include "mvm8_device.h"
-
-#include <stdlib.h>
 
 // Columns of x staged in LDS per pass: 4 KiB of int8 + 256 B of block factors + 256 B of row dots per vector, 36 KiB at NV = 8 (36.5 KiB
 // with the generator starts of the fused stochastic form): four workgroups per CU, the budget of mvm_batch8.hip.
@@ -179,178 +177,40 @@ __global__ __launch_bounds__(M8B_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
 }
 
 // ---- dispatch ----------------------------------------------------------------------------------------------------------------
-// Whether a group of g vectors runs as one batched launch or as g single launches: CLV_MVM_BATCH as in mvm_batch4.hip (1 = always batched,
-// with an rng a remainder group of ONE vector too; 0 = never); unset = the rule measured on the MI355X (DESIGN.md 3,
-// profiles/m8_mvm_batch_kernel_bench.json; stochastic: profiles/m8_mvm_batch_st_kernel_bench.json): at 2, 4 and 8 vectors the batched
-// launch beat the single calls by more than their spread in every row -- 65536^2 and 32768^2 (streaming), fused at 8192 x 4096
-// (cache-resident) and at 65536^2, the IHT loop at N = 8192, either rounding -- so every group of two or more runs batched, whatever
-// the shape.  Not measured: groups of 3 and 5-7, matrices between 32 MiB and 1 GiB or below 32 MiB.
-static bool m8_batch_selected(uint64_t rows, uint64_t cols, uint64_t g, bool stochastic)
-{
-    if (g < 2 && !stochastic) return false;
-    const char *e = clv_env("CLV_MVM_BATCH");
-    if (e && *e) return atoi(e) != 0;
-    if (g < 2) return false;
-    (void)rows;
-    (void)cols;
-    return true;
-}
-
-// the draws of a batched launch on the host side: rng == NULL = rounding disabled
-struct M8BatchDraws {
-    uint64_t *rng;
-    uint64_t base, stride, commit;
+// what the host driver (mvm_batch_host.h) needs to know of this family
+struct M8Batch {
+    template <int NV> using Args = M8BatchArgs<NV>;
+    template <int NV> using Fuse = M8BatchFuse<NV>;
+    static uint64_t matrix_bytes(uint64_t rows, uint64_t cols) { return rows * cols; }
+    static uint64_t vector_bytes(uint64_t n) { return n; }
+    static int check_matrix(const char *fn, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols) { return clv_internal_m8_check_mvm(fn, A, sA, rows, cols, A, A); }
+    static bool result_may_not_alias_x(bool) { return true; }
+    static constexpr auto mvm = clm8_mvm;
+    static constexpr auto scale_and_add = clm8_mvm_scale_and_add;
+    static constexpr auto iht = clm8_iht;
+    static constexpr auto clear = clv_internal_v8_clear;
+    static constexpr auto threshold_batch = clv8_threshold_batch;
+    // no single clm8_iht takes a persistent kernel: it is the launch-per-step loop with the same three launches per iteration per SIGNAL,
+    // so the rule of the fused mvm holds (mvm_batch_selected)
+    static bool iht_prefers_single(uint64_t, uint64_t, uint64_t, int, bool, uint64_t) { return false; }
+    template <int NV, bool NT, bool FUSE, bool ST>
+    static void launch(dim3 grid, hipStream_t st, const uint8_t *A, const float *sA, uint64_t cols, int nv, const Args<NV> &arg, const Fuse<NV> &fuse,
+                       const MvmBatchRng &rs)
+    {
+        hipLaunchKernelGGL((k_m8_mvm_batch<NV, M8B_U, NT, FUSE, ST>), grid, dim3(M8B_THREADS), M8B_LDS_BYTES(NV, ST, FUSE), st, A, sA, cols, nv, arg, fuse,
+                           rs);
+    }
 };
 
-template <int NV>
-static int launch_m8_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t g, const int8_t *const *x,
-                           const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su, float a,
-                           int8_t *const *r2, float *const *sr2, const M8BatchDraws &dr, hipStream_t st)
-{
-    M8BatchArgs<NV> arg;
-    M8BatchFuse<NV> fuse;
-    for (uint64_t v = 0; v < NV; v++) {
-        const bool in = v < g;
-        arg.x[v] = in ? x[v] : nullptr;
-        arg.sx[v] = in ? sx[v] : nullptr;
-        arg.r[v] = in && r ? r[v] : nullptr;
-        arg.sr[v] = in && r ? sr[v] : nullptr;
-        fuse.qu[v] = in && qu ? qu[v] : nullptr;
-        fuse.su[v] = in && qu ? su[v] : nullptr;
-        fuse.r2[v] = in && qu ? r2[v] : nullptr;
-        fuse.sr2[v] = in && qu ? sr2[v] : nullptr;
-    }
-    fuse.a = a;
-    MvmBatchRng rs = {nullptr, 0, nullptr, 0, 0, 0};
-    if (dr.rng) {
-        RngTables T = {nullptr, nullptr, nullptr};
-        int rc = clv_rng_tables(&T);
-        if (rc) return rc;
-        // every launch takes a number of its own, committing or not: it is what picks the slot to read
-        rs = MvmBatchRng{dr.rng, clv_rng_seq_for(dr.rng, st), T.pow_rows, dr.base, dr.stride, dr.commit};
-    }
-    const dim3 grid((unsigned)(rows / 64)), block(M8B_THREADS);
-    // nontemporal loads by the rule of clm8_mvm: once the matrix cannot live in the 256 MiB Infinity Cache
-    const bool streaming = rows * cols > (256ull << 20);
-#define M8B_LAUNCH(NT, FUSE, ST)                                                                                                       \
-    hipLaunchKernelGGL((k_m8_mvm_batch<NV, M8B_U, NT, FUSE, ST>), grid, block, M8B_LDS_BYTES(NV, ST, FUSE), st, (const uint8_t *)A, sA, cols, \
-                       (int)g, arg, fuse, rs)
-#define M8B_LAUNCH_R(NT, FUSE) do { if (dr.rng) M8B_LAUNCH(NT, FUSE, true); else M8B_LAUNCH(NT, FUSE, false); } while (0)
-    if (streaming) { if (qu) M8B_LAUNCH_R(true, true); else M8B_LAUNCH_R(true, false); }
-    else { if (qu) M8B_LAUNCH_R(false, true); else M8B_LAUNCH_R(false, false); }
-#undef M8B_LAUNCH_R
-#undef M8B_LAUNCH
-    CLV_LAUNCH_CHECK();
-    clv_internal_mvm_batch_count();
-    return CLV_OK;
-}
-
-static int m8_launch_group(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t j0, uint64_t g, const int8_t *const *x,
-                           const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su, float a,
-                           int8_t *const *r2, float *const *sr2, const M8BatchDraws &dr, hipStream_t st)
-{
-#define M8B_GROUP(NV) \
-    launch_m8_batch<NV>(A, sA, rows, cols, g, x + j0, sx + j0, r ? r + j0 : nullptr, r ? sr + j0 : nullptr, qu ? qu + j0 : nullptr, \
-                        qu ? su + j0 : nullptr, a, qu ? r2 + j0 : nullptr, qu ? sr2 + j0 : nullptr, dr, st)
-    return g <= 2 ? M8B_GROUP(2) : g <= 4 ? M8B_GROUP(4) : M8B_GROUP(8);
-#undef M8B_GROUP
-}
-
-// the checked arguments of clm8_mvm_batch (qu == NULL) / clm8_mvm_scale_and_add_batch on the stream, group by group; r / sr NULL: the mvm
-// result is not stored (fused form only).  With an rng every group starts at the state the group before it left, so batched and
-// forwarded groups mix freely.
-static int m8_batch_run(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
-                        const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su, float a,
-                        int8_t *const *r2, float *const *sr2, uint64_t *rng, void *stream)
-{
-    hipStream_t st = as_stream(stream);
-    const uint64_t per_vector = (qu ? 4ull : 2ull) * (rows / 64);
-    for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
-        const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        int rc = CLV_OK;
-        if (!m8_batch_selected(rows, cols, g, rng != nullptr)) {
-            for (uint64_t j = j0; j < j0 + g && !rc; j++)
-                rc = qu ? clm8_mvm_scale_and_add(A, sA, rows, cols, x[j], sx[j], qu[j], su[j], a, r ? r[j] : nullptr, r ? sr[j] : nullptr, r2[j],
-                                                 sr2[j], rng, stream)
-                        : clm8_mvm(A, sA, rows, cols, x[j], sx[j], r[j], sr[j], rng, stream);
-        } else {
-            rc = m8_launch_group(A, sA, rows, cols, j0, g, x, sx, r, sr, qu, su, a, r2, sr2, M8BatchDraws{rng, 0, per_vector, g * per_vector}, st);
-        }
-        if (rc) return rc;
-    }
-    return CLV_OK;
-}
-
-// The positioned form: vector j's window begins draw_base + j * draw_stride draws behind the state the call finds, across groups too;
-// only the last group's launch commits.  Always the batched kernel.  rng == NULL: the deterministic kernel, the positions unused.
-static int m8_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
-                       const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su, float a,
-                       int8_t *const *r2, float *const *sr2, uint64_t *rng, uint64_t draw_base, uint64_t draw_stride, uint64_t commit_draws,
-                       void *stream)
-{
-    hipStream_t st = as_stream(stream);
-    for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
-        const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        const bool last = j0 + g == nvec;
-        int rc = m8_launch_group(A, sA, rows, cols, j0, g, x, sx, r, sr, qu, su, a, r2, sr2,
-                                 M8BatchDraws{rng, draw_base + j0 * draw_stride, draw_stride, last ? commit_draws : 0}, st);
-        if (rc) return rc;
-    }
-    return CLV_OK;
-}
-
 // ---- C ABI -------------------------------------------------------------------------------------------------------------------
-// every check of the three mvm calls, before any device work
-static int m8_check_batch_args(const char *fn, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
-                               const float *const *sx, const int8_t *const *qu, const float *const *su, int8_t *const *t, float *const *st_,
-                               int8_t *const *r, float *const *sr, bool fused)
-{
-    // a NULL vector array is reported as such, not as one of the single call's pointers
-    int rc = clv_internal_m8_check_mvm(fn, A, sA, rows, cols, A, A);
-    if (rc) return rc;
-    if (!nvec) return CLV_OK;
-    CLV_REQUIRE(x && sx && r && sr && (!fused || (qu && su)), "%s: null pointer array", fn);
-    CLV_REQUIRE((t == nullptr) == (st_ == nullptr), "%s: t and st must both be given or both be NULL", fn);
-    for (uint64_t j = 0; j < nvec; j++)
-        CLV_REQUIRE(x[j] && sx[j] && r[j] && sr[j] && (!fused || (qu[j] && su[j])) && (!t || (t[j] && st_[j])), "%s: null pointer in vector %llu", fn,
-                    (unsigned long long)j);
-    for (uint64_t j = 0; j < nvec; j++)
-        CLV_REQUIRE((const void *)r[j] != (const void *)x[j] && (const void *)sr[j] != (const void *)sx[j],
-                    "%s: the result of vector %llu must not alias the vector being multiplied", fn, (unsigned long long)j);
-    std::vector<ClvRange> rg;
-    rg.reserve(8 * nvec + 2);
-    const uint64_t sc = sizeof(float);
-    rg.push_back(clv_range(A, rows * cols, false, ~0ull, "A"));
-    rg.push_back(clv_range(sA, (rows / 64) * (cols / 64) * sc, false, ~0ull, "sA"));
-    for (uint64_t j = 0; j < nvec; j++) {
-        rg.push_back(clv_range(x[j], cols, false, j, "x"));
-        rg.push_back(clv_range(sx[j], cols / 64 * sc, false, j, "sx"));
-        rg.push_back(clv_range(r[j], rows, true, j, "r"));
-        rg.push_back(clv_range(sr[j], rows / 64 * sc, true, j, "sr"));
-        if (fused) {
-            // the in-place form r[j] == qu[j], sr[j] == su[j]: the result IS the input, only workgroup rb touches block rb of either
-            const bool in_place = (const void *)r[j] == (const void *)qu[j] && (const void *)sr[j] == (const void *)su[j];
-            if (!in_place) {
-                rg.push_back(clv_range(qu[j], rows, false, j, "qu"));
-                rg.push_back(clv_range(su[j], rows / 64 * sc, false, j, "su"));
-            }
-        }
-        if (t) {
-            rg.push_back(clv_range(t[j], rows, true, j, "t"));
-            rg.push_back(clv_range(st_[j], rows / 64 * sc, true, j, "st"));
-        }
-    }
-    return clv_internal_check_ranges(fn, rg);
-}
-
 extern "C" int clm8_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
                               const float *const *sx, int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, void *stream)
 {
-    int rc = m8_check_batch_args("clm8_mvm_batch", A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
+    int rc = mvm_batch_check_args<M8Batch>("clm8_mvm_batch", A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
     if (rc) return rc;
     if (!nvec || !rows) return CLV_OK;
     if (nvec == 1) return clm8_mvm(A, sA, rows, cols, x[0], sx[0], r[0], sr[0], rng_state_dev, stream);
-    return m8_batch_run(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr, rng_state_dev, stream);
+    return mvm_batch_run<M8Batch>(A, sA, rows, cols, nvec, {x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr}, rng_state_dev, stream);
 }
 
 extern "C" int clm8_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
@@ -358,107 +218,34 @@ extern "C" int clm8_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows
                                  uint64_t draw_stride, uint64_t commit_draws, void *stream)
 {
     const char *fn = "clm8_mvm_batch_at";
-    int rc = m8_check_batch_args(fn, A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
+    int rc = mvm_batch_check_args<M8Batch>(fn, A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
     if (rc) return rc;
     if (!rng_state_dev) return clm8_mvm_batch(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, stream);
-    CLV_REQUIRE(commit_draws < (1ull << (RNG_POW_LEVELS - 1)), "%s: commit_draws=%llu must stay below 2^55", fn, (unsigned long long)commit_draws);
-    const uint64_t bad = clv_internal_first_bad_window(nvec, draw_base, draw_stride, 2 * (rows / 64));
-    CLV_REQUIRE(bad == nvec, "%s: the draws of vector %llu (draw_base=%llu, draw_stride=%llu) do not stay below 2^55", fn, (unsigned long long)bad,
-                (unsigned long long)draw_base, (unsigned long long)draw_stride);
+    rc = mvm_batch_check_draws(fn, rows, nvec, draw_base, draw_stride, commit_draws);
+    if (rc) return rc;
     if (!nvec || !rows) return CLV_OK;
-    return m8_batch_at(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr, rng_state_dev, draw_base, draw_stride,
-                       commit_draws, stream);
+    return mvm_batch_at<M8Batch>(A, sA, rows, cols, nvec, {x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr}, rng_state_dev, draw_base, draw_stride,
+                                 commit_draws, stream);
 }
 
 extern "C" int clm8_mvm_scale_and_add_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
                                             const float *const *sx, const int8_t *const *qu, const float *const *su, float a, int8_t *const *t,
                                             float *const *st_, int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, void *stream)
 {
-    int rc = m8_check_batch_args("clm8_mvm_scale_and_add_batch", A, sA, rows, cols, nvec, x, sx, qu, su, t, st_, r, sr, true);
+    int rc = mvm_batch_check_args<M8Batch>("clm8_mvm_scale_and_add_batch", A, sA, rows, cols, nvec, x, sx, qu, su, t, st_, r, sr, true);
     if (rc) return rc;
     if (!nvec || !rows) return CLV_OK;
     if (nvec == 1)
         return clm8_mvm_scale_and_add(A, sA, rows, cols, x[0], sx[0], qu[0], su[0], a, t ? t[0] : nullptr, t ? st_[0] : nullptr, r[0], sr[0],
                                       rng_state_dev, stream);
-    return m8_batch_run(A, sA, rows, cols, nvec, x, sx, t, st_, qu, su, a, r, sr, rng_state_dev, stream);
+    return mvm_batch_run<M8Batch>(A, sA, rows, cols, nvec, {x, sx, t, st_, qu, su, a, r, sr}, rng_state_dev, stream);
 }
 
-// Q_IHT / Q_GD over a CloverMatrix8 for nvec signals with one Phi: the loop of clm8_iht with every step batched.  Arrays are HOST arrays of
-// nvec device pointers.  Bit-identical to clm8_iht per vector; no single clm8_iht takes a persistent kernel.
 extern "C" int clm8_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, uint64_t nvec,
                               int8_t *const *x, float *const *sx, uint64_t x_len, const int8_t *const *y, const float *const *sy,
                               int8_t *const *t1, float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
                               uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream)
 {
-    const char *fn = "clm8_iht_batch";
-    CLV_REQUIRE(Phi && sPhi && PhiT && sPhiT, "%s: null pointer", fn);
-    CLV_REQUIRE(m % 128 == 0 && n % 128 == 0 && x_len <= n, "%s: m=%llu n=%llu x_len=%llu", fn, (unsigned long long)m, (unsigned long long)n,
-                (unsigned long long)x_len);
-    CLV_REQUIRE(m / 64 <= 0x7FFFFFFFull && n / 64 <= 0x7FFFFFFFull, "%s: too many rows", fn);
-    if (!nvec) return CLV_OK;
-    CLV_REQUIRE(x && sx && y && sy && t1 && st1 && t2 && st2 && t3 && st3, "%s: null pointer array", fn);
-    for (uint64_t j = 0; j < nvec; j++)
-        CLV_REQUIRE(x[j] && sx[j] && y[j] && sy[j] && t1[j] && st1[j] && t2[j] && st2[j] && t3[j] && st3[j], "%s: null pointer in vector %llu", fn,
-                    (unsigned long long)j);
-    {
-        std::vector<ClvRange> rg;
-        rg.reserve(10 * nvec + 4);
-        const uint64_t sc = sizeof(float), tiles = (m / 64) * (n / 64);
-        rg.push_back(clv_range(Phi, m * n, false, ~0ull, "Phi"));
-        rg.push_back(clv_range(sPhi, tiles * sc, false, ~0ull, "sPhi"));
-        rg.push_back(clv_range(PhiT, m * n, false, ~0ull, "PhiT"));
-        rg.push_back(clv_range(sPhiT, tiles * sc, false, ~0ull, "sPhiT"));
-        for (uint64_t j = 0; j < nvec; j++) {
-            rg.push_back(clv_range(y[j], m, false, j, "y"));
-            rg.push_back(clv_range(sy[j], m / 64 * sc, false, j, "sy"));
-            rg.push_back(clv_range(x[j], n, true, j, "x"));
-            rg.push_back(clv_range(sx[j], n / 64 * sc, true, j, "sx"));
-            rg.push_back(clv_range(t1[j], m, true, j, "t1"));
-            rg.push_back(clv_range(st1[j], m / 64 * sc, true, j, "st1"));
-            rg.push_back(clv_range(t2[j], m, true, j, "t2"));
-            rg.push_back(clv_range(st2[j], m / 64 * sc, true, j, "st2"));
-            rg.push_back(clv_range(t3[j], n, true, j, "t3"));
-            rg.push_back(clv_range(st3[j], n / 64 * sc, true, j, "st3"));
-        }
-        int rc = clv_internal_check_ranges(fn, rg);
-        if (rc) return rc;
-    }
-    // Which groups run the batched loop: the rule of the fused mvm (m8_batch_selected; a single clm8_iht is the launch-per-step loop with
-    // the same three launches per iteration per SIGNAL).  CLV_MVM_BATCH = 1 / 0 forces one or the other.
-    // The draws keep the order of the single calls, all iterations of vector 0 first: one iteration draws P = 4 (m / 64) + 4 (n / 64), so
-    // vector j of a group has its Phi window of iteration `it` at (j * iterations + it) * P and its PhiT window 4 (m / 64) further on; only
-    // the group's last launch commits, all g * iterations * P.
-    const uint64_t P = 4 * (m / 64) + 4 * (n / 64);
-    hipStream_t st = as_stream(stream);
-    for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
-        const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        bool batched = g >= 2 && m && n && m8_batch_selected(m, n, g, rng_state_dev != nullptr);
-        if (rng_state_dev && P && iterations > ((1ull << 55) - 1) / (g * P)) batched = false;      // positions beyond the jump-ahead tables
-        if (!batched) {
-            for (uint64_t j = j0; j < j0 + g; j++) {
-                int rc = clm8_iht(Phi, sPhi, PhiT, sPhiT, m, n, x[j], sx[j], x_len, y[j], sy[j], t1[j], st1[j], t2[j], st2[j], t3[j], st3[j],
-                                  iterations, K, mu, threshold, rng_state_dev, stream);
-                if (rc) return rc;
-            }
-            continue;
-        }
-        for (uint64_t j = j0; j < j0 + g; j++) {
-            int rc = clv_internal_v8_clear(x[j], sx[j], n, st);      // x.clear()
-            if (rc) return rc;
-        }
-        const uint64_t stride = iterations * P;
-        for (uint64_t it = 0; it < iterations; it++) {
-            // t1 = Phi * x, t2 = y - t1;  t3 = Phi' * t2, x += mu * t3;  keep the K largest: three launches for the group
-            const uint64_t commit = it + 1 == iterations ? g * stride : 0;
-            int rc = m8_batch_at(Phi, sPhi, m, n, g, x + j0, sx + j0, t1 + j0, st1 + j0, y + j0, sy + j0, -1.0f, t2 + j0, st2 + j0, rng_state_dev,
-                                 it * P, stride, 0, stream);
-            if (!rc)
-                rc = m8_batch_at(PhiT, sPhiT, n, m, g, t2 + j0, st2 + j0, t3 + j0, st3 + j0, x + j0, sx + j0, mu, x + j0, sx + j0, rng_state_dev,
-                                 it * P + 4 * (m / 64), stride, commit, stream);
-            if (!rc && threshold)
-                rc = clv8_threshold_batch(x + j0, sx + j0, g, x_len, n, K, threshold == 2 ? CLV_THRESHOLD_REFERENCE : CLV_THRESHOLD_FAST, stream);
-            if (rc) return rc;
-        }
-    }
-    return CLV_OK;
+    return mvm_batch_iht<M8Batch>("clm8_iht_batch", Phi, sPhi, PhiT, sPhiT, m, n, nvec, x, sx, x_len, y, sy, t1, st1, t2, st2, t3, st3, iterations, K, mu,
+                                  threshold, rng_state_dev, stream);
 }

@@ -4,13 +4,11 @@
 // of many signals with one Phi) pays them once per vector.  Here a workgroup loads each 16 matrix bytes once and runs the chain
 // arithmetic of every vector of the group on them.  The chains of different vectors are independent and each vector's instruction
 // sequence is the one of mvm_device.h, so the results equal the single calls bit for bit.
-#include "mvm_batch_device.h"
+#include "mvm_batch_host.h"
 #include "mvm_device.h"
 
 #include <algorithm>
 #include <atomic>
-#include <stdlib.h>
-#include <string.h>
 
 // Columns of x staged in LDS per pass.  The single-vector kernel stages 65536 (36 KiB); NV vectors at that size would leave one workgroup
 // per CU.  8192 columns are 4 KiB of nibbles + 512 B of block factors per vector: 38 KiB at NV = 8, four workgroups per CU as there.
@@ -190,130 +188,9 @@ int clv_internal_check_ranges(const char *fn, std::vector<ClvRange> &ranges)
 }
 
 // ---- dispatch ----------------------------------------------------------------------------------------------------------------
-// Whether a group of g vectors runs as one batched launch or as g single launches.  CLV_MVM_BATCH (read on every call, as
-// CLV_IHT_PERSISTENT: the tests and tools/kernel_bench.py flip it inside one process): 1 = always batched, 0 = never; unset = the rule
-// measured on the MI355X (profiles/mvm_batch_kernel_bench.json; stochastic: profiles/mvm_batch_st_kernel_bench.json).
-// With an rng, CLV_MVM_BATCH=1 also puts a remainder group of ONE vector (nvec = 9, 17, ...) on the batched kernel: a forced call then hands
-// the state from batched launch to batched launch throughout, which is what the tests of that hand-over need.
-static bool mvm_batch_selected(uint64_t rows, uint64_t cols, uint64_t g, bool stochastic)
-{
-    if (g < 2 && !stochastic) return false;
-    const char *e = clv_env("CLV_MVM_BATCH");
-    if (e && *e) return atoi(e) != 0;
-    if (g < 2) return false;
-    (void)rows;
-    (void)cols;
-    return true;
-}
-
 static std::atomic<uint64_t> g_mvm_batch_launches{0};
 extern "C" uint64_t clv_mvm_batch_launches(void) { return g_mvm_batch_launches.load(std::memory_order_relaxed); }
 void clv_internal_mvm_batch_count(void) { g_mvm_batch_launches.fetch_add(1, std::memory_order_relaxed); }
-
-// the draws of a batched launch on the host side: rng == NULL = rounding disabled
-struct MvmBatchDraws {
-    uint64_t *rng;
-    uint64_t base, stride, commit;
-};
-
-template <int NV>
-static int launch_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t g, const int8_t *const *x,
-                            const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
-                            float a, int8_t *const *r2, float *const *sr2, const MvmBatchDraws &dr, hipStream_t st)
-{
-    MvmBatchArgs<NV> arg;
-    MvmBatchFuse<NV> fuse;
-    for (uint64_t v = 0; v < NV; v++) {
-        const bool in = v < g;
-        arg.x[v] = in ? (const uint8_t *)x[v] : nullptr;
-        arg.sx[v] = in ? sx[v] : nullptr;
-        arg.r[v] = in && r ? (uint32_t *)r[v] : nullptr;
-        arg.sr[v] = in && r ? sr[v] : nullptr;
-        fuse.qu[v] = in && qu ? (const uint32_t *)qu[v] : nullptr;
-        fuse.su[v] = in && qu ? su[v] : nullptr;
-        fuse.r2[v] = in && qu ? (uint32_t *)r2[v] : nullptr;
-        fuse.sr2[v] = in && qu ? sr2[v] : nullptr;
-    }
-    fuse.a = a;
-    MvmBatchRng rs = {nullptr, 0, nullptr, 0, 0, 0};
-    if (dr.rng) {
-        RngTables T = {nullptr, nullptr, nullptr};
-        int rc = clv_rng_tables(&T);
-        if (rc) return rc;
-        // every launch takes a number of its own, committing or not: it is what picks the slot to read
-        rs = MvmBatchRng{dr.rng, clv_rng_seq_for(dr.rng, st), T.pow_rows, dr.base, dr.stride, dr.commit};
-    }
-    const dim3 grid((unsigned)(rows / 64)), block(MVMB_THREADS);
-    // nontemporal loads by the rule of launch_mvm: once the matrix cannot live in the 256 MiB Infinity Cache
-    const bool streaming = rows * (cols / 2) > (256ull << 20);
-#define MVMB_LAUNCH(NT, FUSE, ST)                                                                                                       \
-    hipLaunchKernelGGL((k_m4_mvm_batch<NV, MVMB_U(NV), NT, FUSE, ST>), grid, block, MVMB_LDS_BYTES(NV, ST, FUSE), st, (const uint8_t *)A, sA, \
-                       cols, (int)g, arg, fuse, rs)
-#define MVMB_LAUNCH_R(NT, FUSE) do { if (dr.rng) MVMB_LAUNCH(NT, FUSE, true); else MVMB_LAUNCH(NT, FUSE, false); } while (0)
-    if (streaming) { if (qu) MVMB_LAUNCH_R(true, true); else MVMB_LAUNCH_R(true, false); }
-    else { if (qu) MVMB_LAUNCH_R(false, true); else MVMB_LAUNCH_R(false, false); }
-#undef MVMB_LAUNCH_R
-#undef MVMB_LAUNCH
-    CLV_LAUNCH_CHECK();
-    clv_internal_mvm_batch_count();
-    return CLV_OK;
-}
-
-static int launch_group(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t j0, uint64_t g, const int8_t *const *x,
-                        const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su, float a,
-                        int8_t *const *r2, float *const *sr2, const MvmBatchDraws &dr, hipStream_t st)
-{
-#define MVMB_GROUP(NV) \
-    launch_mvm_batch<NV>(A, sA, rows, cols, g, x + j0, sx + j0, r ? r + j0 : nullptr, r ? sr + j0 : nullptr, qu ? qu + j0 : nullptr, \
-                         qu ? su + j0 : nullptr, a, qu ? r2 + j0 : nullptr, qu ? sr2 + j0 : nullptr, dr, st)
-    return g <= 2 ? MVMB_GROUP(2) : g <= 4 ? MVMB_GROUP(4) : MVMB_GROUP(8);
-#undef MVMB_GROUP
-}
-
-// the checked arguments of clm4_mvm_batch (qu == NULL) / clm4_mvm_scale_and_add_batch on the stream, group by group; r / sr NULL: the mvm
-// result is not stored (fused form only).  With an rng every group starts at the state the group before it left: a batched group's windows
-// lie 2 G (fused: 4 G) draws apart from position 0 and its launch commits all of them, a forwarded group's single calls advance the state
-// themselves -- so the two kinds mix freely.
-int clv_internal_mvm_batch_run(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
-                               const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
-                               float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, void *stream)
-{
-    hipStream_t st = as_stream(stream);
-    const uint64_t per_vector = (qu ? 4ull : 2ull) * (rows / 64);
-    for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
-        const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        int rc = CLV_OK;
-        if (!mvm_batch_selected(rows, cols, g, rng != nullptr)) {
-            for (uint64_t j = j0; j < j0 + g && !rc; j++)
-                rc = qu ? clm4_mvm_scale_and_add(A, sA, rows, cols, x[j], sx[j], qu[j], su[j], a, r ? r[j] : nullptr, r ? sr[j] : nullptr, r2[j],
-                                                 sr2[j], rng, stream)
-                        : clm4_mvm(A, sA, rows, cols, x[j], sx[j], r[j], sr[j], rng, stream);
-        } else {
-            rc = launch_group(A, sA, rows, cols, j0, g, x, sx, r, sr, qu, su, a, r2, sr2, MvmBatchDraws{rng, 0, per_vector, g * per_vector}, st);
-        }
-        if (rc) return rc;
-    }
-    return CLV_OK;
-}
-
-// The positioned form: vector j's window begins draw_base + j * draw_stride draws behind the state the call finds, across groups too;
-// only the last group's launch commits.  Always the batched kernel (a window that is not where a single call would draw cannot be
-// forwarded).  rng == NULL: the deterministic kernel, the positions unused.  The caller has checked the positions (clv_internal_first_bad_window).
-int clv_internal_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
-                              const float *const *sx, int8_t *const *r, float *const *sr, const int8_t *const *qu, const float *const *su,
-                              float a, int8_t *const *r2, float *const *sr2, uint64_t *rng, uint64_t draw_base, uint64_t draw_stride,
-                              uint64_t commit_draws, void *stream)
-{
-    hipStream_t st = as_stream(stream);
-    for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
-        const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        const bool last = j0 + g == nvec;
-        int rc = launch_group(A, sA, rows, cols, j0, g, x, sx, r, sr, qu, su, a, r2, sr2,
-                              MvmBatchDraws{rng, draw_base + j0 * draw_stride, draw_stride, last ? commit_draws : 0}, st);
-        if (rc) return rc;
-    }
-    return CLV_OK;
-}
 
 // the first of nvec windows of `window` draws each that does not end at or below 2^55, the exponents wave_pow_apply has table levels
 // for; nvec if there is none
@@ -327,55 +204,47 @@ uint64_t clv_internal_first_bad_window(uint64_t nvec, uint64_t draw_base, uint64
     return nvec;
 }
 
-// ---- C ABI -------------------------------------------------------------------------------------------------------------------
-// every check of both calls, before any device work
-static int check_batch_args(const char *fn, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
-                            const float *const *sx, const int8_t *const *qu, const float *const *su, int8_t *const *t, float *const *st_,
-                            int8_t *const *r, float *const *sr, bool fused)
-{
-    // a NULL vector array is reported as such, not as one of check_mvm_args' pointers
-    int rc = check_mvm_args(fn, A, sA, rows, cols, A, sA);
-    if (rc) return rc;
-    if (!nvec) return CLV_OK;
-    CLV_REQUIRE(x && sx && r && sr && (!fused || (qu && su)), "%s: null pointer array", fn);
-    CLV_REQUIRE((t == nullptr) == (st_ == nullptr), "%s: t and st must both be given or both be NULL", fn);
-    for (uint64_t j = 0; j < nvec; j++)
-        CLV_REQUIRE(x[j] && sx[j] && r[j] && sr[j] && (!fused || (qu[j] && su[j])) && (!t || (t[j] && st_[j])), "%s: null pointer in vector %llu", fn,
-                    (unsigned long long)j);
-    std::vector<ClvRange> rg;
-    rg.reserve(8 * nvec + 2);
-    const uint64_t sc = sizeof(float);
-    rg.push_back(clv_range(A, rows * (cols / 2), false, ~0ull, "A"));
-    rg.push_back(clv_range(sA, (rows / 64) * (cols / 64) * sc, false, ~0ull, "sA"));
-    for (uint64_t j = 0; j < nvec; j++) {
-        rg.push_back(clv_range(x[j], cols / 2, false, j, "x"));
-        rg.push_back(clv_range(sx[j], cols / 64 * sc, false, j, "sx"));
-        rg.push_back(clv_range(r[j], rows / 2, true, j, "r"));
-        rg.push_back(clv_range(sr[j], rows / 64 * sc, true, j, "sr"));
-        if (fused) {
-            // the in-place form r[j] == qu[j], sr[j] == su[j]: the result IS the input, only workgroup rb touches block rb of either
-            const bool in_place = (const void *)r[j] == (const void *)qu[j] && (const void *)sr[j] == (const void *)su[j];
-            if (!in_place) {
-                rg.push_back(clv_range(qu[j], rows / 2, false, j, "qu"));
-                rg.push_back(clv_range(su[j], rows / 64 * sc, false, j, "su"));
-            }
-        }
-        if (t) {
-            rg.push_back(clv_range(t[j], rows / 2, true, j, "t"));
-            rg.push_back(clv_range(st_[j], rows / 64 * sc, true, j, "st"));
-        }
+// what the host driver (mvm_batch_host.h) needs to know of this family
+struct Mvm4Batch {
+    template <int NV> using Args = MvmBatchArgs<NV>;
+    template <int NV> using Fuse = MvmBatchFuse<NV>;
+    static uint64_t matrix_bytes(uint64_t rows, uint64_t cols) { return rows * (cols / 2); }
+    static uint64_t vector_bytes(uint64_t n) { return n / 2; }
+    static int check_matrix(const char *fn, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols) { return check_mvm_args(fn, A, sA, rows, cols, A, sA); }
+    static bool result_may_not_alias_x(bool) { return false; }
+    static constexpr auto mvm = clm4_mvm;
+    static constexpr auto scale_and_add = clm4_mvm_scale_and_add;
+    static constexpr auto iht = clm4_iht;
+    static constexpr auto clear = clv_internal_v4_clear;
+    static constexpr auto threshold_batch = clv4_threshold_batch;
+    // A single clm4_iht at m, n <= 8192 (threshold FAST or none) takes the persistent kernel, 9.4 us per iteration and signal at N = 8192:
+    // against it the batched loop was measured for a full group of 8 only (64.2 us per iteration for 8 signals against 75.5),
+    // so smaller groups of that class run as single calls (not measured: by the mvm rows a group of 2 would lose).  With an rng the same
+    // rule: the full group of 8 beat the stochastic persistent kernel too (80.2 us per iteration for 8 signals against 94.7,
+    // profiles/mvm_batch_st_kernel_bench.json).  Elsewhere the single call is the launch-per-step loop with the same three launches per
+    // iteration per SIGNAL, and the batched fused mvm was faster at 2, 4 and 8 vectors, either rounding.
+    static bool iht_prefers_single(uint64_t m, uint64_t n, uint64_t iterations, int threshold, bool, uint64_t g)
+    {
+        return g < CLM4_MVM_BATCH_MAX && threshold <= 1 && iterations && m <= 8192 && n <= 8192 && clv_env_int("CLV_IHT_PERSISTENT", 1) != 0;
     }
-    return clv_internal_check_ranges(fn, rg);
-}
+    template <int NV, bool NT, bool FUSE, bool ST>
+    static void launch(dim3 grid, hipStream_t st, const uint8_t *A, const float *sA, uint64_t cols, int nv, const Args<NV> &arg, const Fuse<NV> &fuse,
+                       const MvmBatchRng &rs)
+    {
+        hipLaunchKernelGGL((k_m4_mvm_batch<NV, MVMB_U(NV), NT, FUSE, ST>), grid, dim3(MVMB_THREADS), MVMB_LDS_BYTES(NV, ST, FUSE), st, A, sA, cols, nv,
+                           arg, fuse, rs);
+    }
+};
 
+// ---- C ABI -------------------------------------------------------------------------------------------------------------------
 extern "C" int clm4_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
                               const float *const *sx, int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, void *stream)
 {
-    int rc = check_batch_args("clm4_mvm_batch", A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
+    int rc = mvm_batch_check_args<Mvm4Batch>("clm4_mvm_batch", A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
     if (rc) return rc;
     if (!nvec || !rows) return CLV_OK;
     if (nvec == 1) return clm4_mvm(A, sA, rows, cols, x[0], sx[0], r[0], sr[0], rng_state_dev, stream);
-    return clv_internal_mvm_batch_run(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr, rng_state_dev, stream);
+    return mvm_batch_run<Mvm4Batch>(A, sA, rows, cols, nvec, {x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr}, rng_state_dev, stream);
 }
 
 extern "C" int clm4_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
@@ -383,16 +252,14 @@ extern "C" int clm4_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows
                                  uint64_t draw_stride, uint64_t commit_draws, void *stream)
 {
     const char *fn = "clm4_mvm_batch_at";
-    int rc = check_batch_args(fn, A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
+    int rc = mvm_batch_check_args<Mvm4Batch>(fn, A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
     if (rc) return rc;
     if (!rng_state_dev) return clm4_mvm_batch(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, stream);
-    CLV_REQUIRE(commit_draws < (1ull << (RNG_POW_LEVELS - 1)), "%s: commit_draws=%llu must stay below 2^55", fn, (unsigned long long)commit_draws);
-    const uint64_t bad = clv_internal_first_bad_window(nvec, draw_base, draw_stride, 2 * (rows / 64));
-    CLV_REQUIRE(bad == nvec, "%s: the draws of vector %llu (draw_base=%llu, draw_stride=%llu) do not stay below 2^55", fn, (unsigned long long)bad,
-                (unsigned long long)draw_base, (unsigned long long)draw_stride);
+    rc = mvm_batch_check_draws(fn, rows, nvec, draw_base, draw_stride, commit_draws);
+    if (rc) return rc;
     if (!nvec || !rows) return CLV_OK;
-    return clv_internal_mvm_batch_at(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr, rng_state_dev, draw_base,
-                                     draw_stride, commit_draws, stream);
+    return mvm_batch_at<Mvm4Batch>(A, sA, rows, cols, nvec, {x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr}, rng_state_dev, draw_base,
+                                   draw_stride, commit_draws, stream);
 }
 
 extern "C" int clm4_mvm_scale_and_add_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
@@ -400,11 +267,20 @@ extern "C" int clm4_mvm_scale_and_add_batch(const int8_t *A, const float *sA, ui
                                             float a, int8_t *const *t, float *const *st_, int8_t *const *r, float *const *sr,
                                             uint64_t *rng_state_dev, void *stream)
 {
-    int rc = check_batch_args("clm4_mvm_scale_and_add_batch", A, sA, rows, cols, nvec, x, sx, qu, su, t, st_, r, sr, true);
+    int rc = mvm_batch_check_args<Mvm4Batch>("clm4_mvm_scale_and_add_batch", A, sA, rows, cols, nvec, x, sx, qu, su, t, st_, r, sr, true);
     if (rc) return rc;
     if (!nvec || !rows) return CLV_OK;
     if (nvec == 1)
         return clm4_mvm_scale_and_add(A, sA, rows, cols, x[0], sx[0], qu[0], su[0], a, t ? t[0] : nullptr, t ? st_[0] : nullptr, r[0], sr[0],
                                       rng_state_dev, stream);
-    return clv_internal_mvm_batch_run(A, sA, rows, cols, nvec, x, sx, t, st_, qu, su, a, r, sr, rng_state_dev, stream);
+    return mvm_batch_run<Mvm4Batch>(A, sA, rows, cols, nvec, {x, sx, t, st_, qu, su, a, r, sr}, rng_state_dev, stream);
+}
+
+extern "C" int clm4_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, uint64_t nvec,
+                              int8_t *const *x, float *const *sx, uint64_t x_len, const int8_t *const *y, const float *const *sy,
+                              int8_t *const *t1, float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
+                              uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream)
+{
+    return mvm_batch_iht<Mvm4Batch>("clm4_iht_batch", Phi, sPhi, PhiT, sPhiT, m, n, nvec, x, sx, x_len, y, sy, t1, st1, t2, st2, t3, st3, iterations, K,
+                                    mu, threshold, rng_state_dev, stream);
 }
