@@ -2,6 +2,9 @@
 // forms) and the reference's min-heap walk (REFERENCE).
 // One of the callers either side of the hot path.  With mvm these are the five steps of the reference's quantized IHT / GD
 // iterations (test/performance/01_measure.h:923-946, 999-1021), so x, t1..t3 can stay in HBM across iterations.
+// The kernels of every path and element width come first (ThreshElems<BITS>: what differs between the widths on the device), each large
+// path with its workspace layout (Th4Layout, ThLargeLayout, ThRefLayout); the host side stands at the end, once for CloverVector4 / 8 / 16 /
+// 32: ThreshHost<BITS> (what differs on the host), thresh_ladder, the checks and the templates the extern "C" entries name their width to.
 #include "common.h"
 #include "clover_hip_fp32.h"
 #include "thresh_device.h"
@@ -41,7 +44,7 @@ __device__ __forceinline__ uint32_t f16_abs_key(uint16_t h)
 // The large-n kernels below serve every element width.  BITS = 16: CloverVector16, 2 raw binary16 values per word, no scales,
 // |value| = |f32(h)|.  BITS = 4: CloverVector4, 8 elements per word, |value| = |f32(s/7) * q|
 // (CloverVector4::get, :206-209).  BITS = 8: CloverVector8 (same algorithm, CloverVector8.h:1680-1740), 4 elements per word,
-// |value| = |f32((float)q * s) / 127| (CloverVector8::get, :137-140).
+// |value| = |f32((float)q * s) / 127| (CloverVector8::get, :137-140).  Host-side counterpart: ThreshHost<BITS>, behind the kernels it names.
 template <int BITS>
 struct ThreshElems {
     static constexpr int EPW = 32 / BITS;                                   // elements per 32-bit word
@@ -1531,17 +1534,30 @@ __global__ __launch_bounds__(256) void k_th4_apply3(u32x4 *__restrict__ q, const
 
 // (TH4_GROUPS / TH4_MAX_CPG are defined in front of k_th4_ties6)
 
-// workspace layout: [3 histograms of 4096 u32][ThreshState, 256 B][group_ties: 512 u32][chunk_ties: nblocks/256 + 1 u32, padded to
-// 256 B][cnt: nblocks u64]
+// workspace layout (byte offsets; clv4_threshold_workspace_bytes is `total`): [3 histograms of 4096 u32][ThreshState, 256 B]
+// [group_ties: 512 u32][chunk_ties: n_pad/64/256 + 1 u32, padded to 256 B][cnt: n_pad/64 u64][cand: the blocks' candidate words,
+// n_pad/64 u32] + 256 B of slack
+struct Th4Layout {
+    uint64_t ts, group_ties, chunk_ties, cnt, cand, total;
+    static Th4Layout of(uint64_t n_pad)
+    {
+        const uint64_t ts = 3 * 4096 * sizeof(uint32_t), group_ties = ts + 256, chunk_ties = group_ties + TH4_GROUPS * sizeof(uint32_t);
+        const uint64_t cnt = chunk_ties + (((n_pad / 64 / 256 + 1) * 4 + 255) & ~255ull), cand = cnt + (n_pad / 64) * sizeof(unsigned long long);
+        return {ts, group_ties, chunk_ties, cnt, cand, cand + (n_pad / 64) * sizeof(uint32_t) + 256};
+    }
+};
+
 static int threshold4_large(uint32_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *workspace, hipStream_t st)
 {
     const uint64_t nblocks = (n + 63) / 64;
     const uint32_t nchunks = (uint32_t)((nblocks + 255) / 256);
-    uint32_t *hists = (uint32_t *)workspace;
-    ThreshState *ts = (ThreshState *)(hists + 3 * 4096);
-    uint32_t *group_ties = (uint32_t *)((char *)ts + 256);
-    uint32_t *chunk_ties = group_ties + TH4_GROUPS;
-    unsigned long long *cnt = (unsigned long long *)((char *)chunk_ties + (((uint64_t)(n_pad / 64 / 256 + 1) * 4 + 255) & ~255ull));
+    const Th4Layout lay = Th4Layout::of(n_pad);
+    char *const ws = (char *)workspace;
+    uint32_t *hists = (uint32_t *)ws;
+    ThreshState *ts = (ThreshState *)(ws + lay.ts);
+    uint32_t *group_ties = (uint32_t *)(ws + lay.group_ties);
+    uint32_t *chunk_ties = (uint32_t *)(ws + lay.chunk_ties);
+    unsigned long long *cnt = (unsigned long long *)(ws + lay.cnt);
     // the three-launch form (round 6): k != 0, a zeroed control block on this stream, at most TH4_P_MAX_CPG chunks per CU
     const int three = (int)clv_env_int("CLV_THRESHOLD_THREE_LAUNCH", 1);      // read per call: A/B runs flip it
     if (three && k != 0) {
@@ -1550,7 +1566,7 @@ static int threshold4_large(uint32_t *q, const float *s, uint64_t n, uint64_t n_
         void *slots = nullptr;
         if (cpg2 <= TH4_P_MAX_CPG && groups2 <= TH4_GROUPS && clv_internal_sync_slots(&slots, CLV_SYNC_SLOT_BYTES_TOTAL, st) == CLV_OK) {
             uint32_t *ctl = (uint32_t *)((char *)slots + CLV_SYNC_SLOT_THRESHOLD_OFFSET);
-            uint32_t *cand = (uint32_t *)(cnt + n_pad / 64);
+            uint32_t *cand = (uint32_t *)(ws + lay.cand);
             const uint64_t want1 = (nblocks + 1024 * TH4_K1_U - 1) / (1024 * TH4_K1_U), cap1 = (uint64_t)cus * 2;
             hipLaunchKernelGGL(k_th4_count_hist0, dim3((unsigned)(want1 < cap1 ? want1 : cap1)), dim3(1024), 0, st, (const u32x4 *)q, s, n, cnt, nblocks, ctl);
             int rc = clv_internal_persist_enter(st);                      // resident workgroups that wait for each other: one such launch at a time
@@ -1610,12 +1626,24 @@ static int threshold4_large(uint32_t *q, const float *s, uint64_t n, uint64_t n_
 
 __global__ void k_thresh_state_none(ThreshState *ts) { *ts = ThreshState{0, 0, 0x7F800000u, 0}; }
 
+// workspace layout of threshold_large<BITS> (byte offsets; the clv8 / clv_f16 / clv_f32 _threshold_workspace_bytes are `total`):
+// [histogram: 4096 u32][ThreshState, 256 B][block_ties: one u32 per TH_WORDS_PER_BLOCK words of n_pad elements] + 256 B of slack
+struct ThLargeLayout {
+    uint64_t ts, block_ties, total;
+    static ThLargeLayout of(uint64_t n_pad, int epw)
+    {
+        const uint64_t ts = 4096 * sizeof(uint32_t), block_ties = ts + 256;
+        return {ts, block_ties, block_ties + (n_pad / epw + TH_WORDS_PER_BLOCK - 1) / TH_WORDS_PER_BLOCK * sizeof(uint32_t) + 256};
+    }
+};
+
 template <int BITS>
-static int threshold_large(uint32_t *q, const float *s, uint64_t n, uint64_t k, void *workspace, hipStream_t st)
+static int threshold_large(uint32_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *workspace, hipStream_t st)
 {
+    const ThLargeLayout lay = ThLargeLayout::of(n_pad, ThreshElems<BITS>::EPW);
     uint32_t *hist = (uint32_t *)workspace;
-    ThreshState *ts = (ThreshState *)(hist + 4096);
-    uint32_t *block_ties = (uint32_t *)((char *)ts + 256);
+    ThreshState *ts = (ThreshState *)((char *)workspace + lay.ts);
+    uint32_t *block_ties = (uint32_t *)((char *)workspace + lay.block_ties);
     const uint64_t nwords = (n + ThreshElems<BITS>::EPW - 1) / ThreshElems<BITS>::EPW;
     const uint32_t nblocks = (uint32_t)((nwords + TH_WORDS_PER_BLOCK - 1) / TH_WORDS_PER_BLOCK);
     CLV_HIP(hipMemsetAsync(hist, 0, 4096 * sizeof(uint32_t) + 256, st));
@@ -1638,48 +1666,6 @@ static int threshold_large(uint32_t *q, const float *s, uint64_t n, uint64_t k, 
     hipLaunchKernelGGL(k_thresh_apply<BITS>, dim3(nblocks), dim3(256), 0, st, q, s, n, ts, block_ties);
     CLV_LAUNCH_CHECK();
     return CLV_OK;
-}
-
-extern "C" uint64_t clv4_threshold_workspace_bytes(uint64_t n_pad)
-{
-    const uint64_t chunk_bytes = ((n_pad / 64 / 256 + 1) * 4 + 255) & ~255ull;
-    return 3 * 4096 * sizeof(uint32_t) + 256 + TH4_GROUPS * sizeof(uint32_t) + chunk_bytes + (n_pad / 64) * sizeof(unsigned long long) +
-           (n_pad / 64) * sizeof(uint32_t) /* the blocks' candidate words */ + 256;
-}
-
-extern "C" uint64_t clv8_threshold_workspace_bytes(uint64_t n_pad)
-{
-    const uint64_t blocks = (n_pad / 4 + TH_WORDS_PER_BLOCK - 1) / TH_WORDS_PER_BLOCK;
-    return 4096 * sizeof(uint32_t) + 256 + blocks * sizeof(uint32_t) + 256;
-}
-
-extern "C" int clv4_threshold(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *workspace, void *stream)
-{
-    CLV_REQUIRE(q && s, "clv4_threshold: null pointer");
-    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv4_threshold: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
-    CLV_REQUIRE(n < (1ull << 32), "clv4_threshold: vectors of 2^32 or more elements are not supported");
-    CLV_REQUIRE_WORKSPACE("clv4_threshold", workspace);
-    hipStream_t st = as_stream(stream);
-    if (k >= n || n == 0) return CLV_OK;                       // everything survives
-    if (n_pad <= (uint64_t)TS_THREADS * TS_MAXW * 8) {
-        const uint64_t wpt = ((n + 7) / 8 + TS_THREADS - 1) / TS_THREADS;         // words per thread
-#define T4_LAUNCH(W) hipLaunchKernelGGL(k_thresh_small<W>, dim3(1), dim3(TS_THREADS), 0, st, (uint32_t *)q, s, (uint32_t)n, (uint32_t)k)
-        // (fewer, fatter threads -- W = 8 so that every block is one thread's and the tables need no atomics -- were measured slower at
-        //  N = 8192 and 32768: 7.7 / 12.4 us against 5.4 / 10.9)
-        if (wpt <= 1) T4_LAUNCH(1);
-        else if (wpt <= 2) T4_LAUNCH(2);
-        else if (wpt <= 4) T4_LAUNCH(4);
-        else if (wpt <= 8) T4_LAUNCH(8);
-        else T4_LAUNCH(16);
-#undef T4_LAUNCH
-        CLV_LAUNCH_CHECK();
-        return CLV_OK;
-    }
-    if (!workspace) {
-        int rc = clv_internal_workspace(&workspace, clv4_threshold_workspace_bytes(n_pad), as_stream(stream));
-        if (rc) return rc;
-    }
-    return threshold4_large((uint32_t *)q, s, n, n_pad, k, workspace, st);
 }
 
 // =================================================================================================
@@ -1901,13 +1887,19 @@ __global__ __launch_bounds__(256) void k_thr_ref_apply(uint32_t *__restrict__ q,
     }
 }
 
-extern "C" uint64_t clv_threshold_reference_workspace_bytes_k(uint64_t n_pad, uint64_t k)
-{
-    // [|value| per element: 4 n][survivor bitmap: n / 8][the heap's entries, ONLY when it does not fit LDS (k > 20000): 8 (k + 1)] + slack
-    const uint64_t kk = k < n_pad ? k : n_pad;
-    return n_pad * 4 + ((n_pad / 8 + 255) & ~255ull) + (kk > THR_LDS_WHOLE_MAX ? (kk + 1) * 8 : 0) + 512;
-}
-extern "C" uint64_t clv_threshold_reference_workspace_bytes(uint64_t n_pad) { return clv_threshold_reference_workspace_bytes_k(n_pad, n_pad); }   // any k
+// workspace layout of the reference walk (byte offsets; clv_threshold_reference_workspace_bytes_k is `total`): [|value| per element:
+// 4 n_pad][survivor bitmap: n_pad / 8, padded to 256 B][the heap's entries, ONLY when it does not fit LDS (k > 20000): 8 (k + 1)] +
+// 512 B of slack
+struct ThRefLayout {
+    uint64_t keep, gheap, total;
+    static ThRefLayout of(uint64_t n_pad, uint64_t k)
+    {
+        const uint64_t kk = k < n_pad ? k : n_pad, keep = n_pad * 4, gheap = keep + ((n_pad / 8 + 255) & ~255ull);
+        return {keep, gheap, gheap + (kk > THR_LDS_WHOLE_MAX ? (kk + 1) * 8 : 0) + 512};
+    }
+};
+extern "C" uint64_t clv_threshold_reference_workspace_bytes_k(uint64_t n_pad, uint64_t k) { return ThRefLayout::of(n_pad, k).total; }
+extern "C" uint64_t clv_threshold_reference_workspace_bytes(uint64_t n_pad) { return ThRefLayout::of(n_pad, n_pad).total; }   // any k
 
 template <int BITS>
 static int threshold_reference(uint32_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *workspace, hipStream_t st,
@@ -1915,15 +1907,16 @@ static int threshold_reference(uint32_t *q, const float *s, uint64_t n, uint64_t
 {
     // the walk steps a 32-bit element index 64 at a time (k_thr_ref_walk): base + 64 must not wrap
     CLV_REQUIRE(n <= 0xFFFFFFFFull - 64, "threshold (reference order): n=%llu, at most 2^32 - 65 elements", (unsigned long long)n);
+    const ThRefLayout lay = ThRefLayout::of(n_pad, k);
     if (!workspace) {
         // the library's own scratch is sized for THIS k: the 8-bytes-per-element heap region exists only beyond the LDS heap (ADVICE r5:
         // a 2^30-element vector used to pin 13 GB of grow-only scratch for any k)
-        int rc = clv_internal_workspace(&workspace, clv_threshold_reference_workspace_bytes_k(n_pad, k), st);
+        int rc = clv_internal_workspace(&workspace, lay.total, st);
         if (rc) return rc;
     }
     float *vals = (float *)workspace;
-    uint32_t *keep = (uint32_t *)((char *)workspace + n_pad * 4);
-    uint2 *gheap = (uint2 *)((char *)keep + ((n_pad / 8 + 255) & ~255ull));
+    uint32_t *keep = (uint32_t *)((char *)workspace + lay.keep);
+    uint2 *gheap = (uint2 *)((char *)workspace + lay.gheap);
     const uint64_t keep_words = (n + 31) / 32;
     const uint64_t nwords = (n + ThreshElems<BITS>::EPW - 1) / ThreshElems<BITS>::EPW;
     const uint64_t want = (nwords + 255) / 256, cap = (uint64_t)clv_cu_count() * 8;
@@ -1946,162 +1939,184 @@ static int threshold_reference(uint32_t *q, const float *s, uint64_t n, uint64_t
     return CLV_OK;
 }
 
-extern "C" int clv4_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream)
+// =================================================================================================
+// The host side of the C ABI's threshold entries, written once for CloverVector4 / 8 / 16 / 32.  ThreshHost<BITS> holds what differs:
+//   EPW, MAXW                elements per word; the largest compiled words per thread (one workgroup serves n_pad <= TS_THREADS * MAXW * EPW)
+//   SCALES, ALIGNED_X        whether a scale array exists (a kernel argument, a pointer to check); whether x must be 16-byte aligned
+//   SMALL_SWITCH             the environment switch, read per call, whose 0 keeps the large-vector path at every n (NULL: none)
+//   small<W>, small_batch<W> the one-workgroup kernel and, where one exists (4 / 8), its batch form
+//   q_bytes(n_pad)           bytes of a vector's q, for the batch call's overlap check (4 / 8)
+//   large, workspace_bytes   the large-vector path and the size of the workspace it carves
+// =================================================================================================
+template <int BITS>
+struct ThreshHost;
+
+template <>
+struct ThreshHost<4> {
+    // (fewer, fatter threads -- W = 8 so that every block is one thread's and the tables need no atomics -- were measured slower at
+    //  N = 8192 and 32768: 7.7 / 12.4 us against 5.4 / 10.9)
+    static constexpr int EPW = 8, MAXW = TS_MAXW;
+    static constexpr bool SCALES = true, ALIGNED_X = false;
+    static constexpr const char *SMALL_SWITCH = nullptr;
+    template <int W> static constexpr auto small = k_thresh_small<W>;
+    template <int W> static constexpr auto small_batch = k_thresh_small_batch<W>;
+    static uint64_t q_bytes(uint64_t n_pad) { return n_pad / 2; }
+    static constexpr auto large = threshold4_large;
+    static uint64_t workspace_bytes(uint64_t n_pad) { return Th4Layout::of(n_pad).total; }
+};
+
+// the large-vector path of the 8-, 16- and 32-bit widths: threshold_large<BITS> on ThLargeLayout
+template <int BITS>
+struct ThreshHostLarge {
+    static constexpr int (*large)(uint32_t *, const float *, uint64_t, uint64_t, uint64_t, void *, hipStream_t) = threshold_large<BITS>;
+    static uint64_t workspace_bytes(uint64_t n_pad) { return ThLargeLayout::of(n_pad, ThreshElems<BITS>::EPW).total; }
+};
+
+template <>
+struct ThreshHost<8> : ThreshHostLarge<8> {
+    static constexpr int EPW = 4, MAXW = TS8_MAXW;
+    static constexpr bool SCALES = true, ALIGNED_X = false;
+    static constexpr const char *SMALL_SWITCH = nullptr;
+    template <int W> static constexpr auto small = k_thresh8_small<W>;
+    template <int W> static constexpr auto small_batch = k_thresh8_small_batch<W>;
+    static uint64_t q_bytes(uint64_t n_pad) { return n_pad; }
+};
+
+template <>
+struct ThreshHost<16> : ThreshHostLarge<16> {
+    static constexpr int EPW = 2, MAXW = TS_MAXW;
+    static constexpr bool SCALES = false, ALIGNED_X = false;
+    static constexpr const char *SMALL_SWITCH = "CLV_F16_THRESHOLD_SMALL";
+    template <int W> static constexpr auto small = k_f16_thresh_small<W>;
+};
+
+template <>
+struct ThreshHost<32> : ThreshHostLarge<32> {
+    static constexpr int EPW = 1, MAXW = TS_MAXW;
+    static constexpr bool SCALES = false, ALIGNED_X = true;
+    static constexpr const char *SMALL_SWITCH = "CLV_F32_THRESHOLD_SMALL";
+    template <int W> static constexpr auto small = k_f32_thresh_small<W>;
+};
+
+// words per thread -> the compiled W: f(std::integral_constant<int, W>) with the smallest W in 1, 2, 4, 8, 16 that holds wpt, MAXW at most
+// (so the 8-bit kernels are never instantiated at 16)
+template <int MAXW, class F>
+static inline void thresh_ladder(uint64_t wpt, F &&f)
 {
-    if (mode == CLV_THRESHOLD_FAST) return clv4_threshold(q, s, n, n_pad, k, workspace, stream);
-    CLV_REQUIRE(mode == CLV_THRESHOLD_REFERENCE, "clv4_threshold_mode: unknown mode %d", mode);
-    CLV_REQUIRE(q && s, "clv4_threshold_mode: null pointer");
-    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv4_threshold_mode: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
-    CLV_REQUIRE(n < (1ull << 32), "clv4_threshold_mode: vectors of 2^32 or more elements are not supported");
-    CLV_REQUIRE_WORKSPACE("clv4_threshold_mode", workspace);
-    if (k >= n || n == 0) return CLV_OK;
-    return threshold_reference<4>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream));
+    if (wpt <= 1) f(std::integral_constant<int, 1>());
+    else if (wpt <= 2) f(std::integral_constant<int, 2>());
+    else if (wpt <= 4) f(std::integral_constant<int, 4>());
+    else if (MAXW == 8 || wpt <= 8) f(std::integral_constant<int, 8>());
+    else f(std::integral_constant<int, MAXW>());
 }
 
-// CloverVector4::threshold on nvec vectors of one size.  q / s: HOST arrays of nvec device pointers.  FAST up to the one-workgroup limit:
-// one launch, workgroup j = k_thresh_small's body on vector j; otherwise the sequence of single calls.  Bit-identical to that sequence.
-extern "C" int clv4_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode,
-                                    void *stream)
+template <class H>
+static inline uint64_t thresh_words_per_thread(uint64_t n) { return ((n + H::EPW - 1) / H::EPW + TS_THREADS - 1) / TS_THREADS; }
+
+static int thresh_check_mode(const char *fn, int mode)
 {
-    const char *fn = "clv4_threshold_batch";
     CLV_REQUIRE(mode == CLV_THRESHOLD_FAST || mode == CLV_THRESHOLD_REFERENCE, "%s: unknown mode %d", fn, mode);
-    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "%s: n=%llu n_pad=%llu", fn, (unsigned long long)n, (unsigned long long)n_pad);
-    CLV_REQUIRE(n < (1ull << 32), "%s: vectors of 2^32 or more elements are not supported", fn);
-    if (!nvec) return CLV_OK;
-    CLV_REQUIRE(q && s, "%s: null pointer array", fn);
-    for (uint64_t j = 0; j < nvec; j++) CLV_REQUIRE(q[j] && s[j], "%s: null pointer in vector %llu", fn, (unsigned long long)j);
-    {
-        std::vector<ClvRange> rg;
-        rg.reserve(2 * nvec);
-        for (uint64_t j = 0; j < nvec; j++) {
-            rg.push_back(clv_range(q[j], n_pad / 2, true, j, "q"));
-            rg.push_back(clv_range(s[j], n_pad / 64 * sizeof(float), false, j, "s"));
-        }
-        int rc = clv_internal_check_ranges(fn, rg);
-        if (rc) return rc;
-    }
-    if (k >= n || n == 0) return CLV_OK;                       // everything survives
-    if (nvec == 1 || mode != CLV_THRESHOLD_FAST || n_pad > (uint64_t)TS_THREADS * TS_MAXW * 8) {
-        for (uint64_t j = 0; j < nvec; j++) {
-            int rc = clv4_threshold_mode(q[j], s[j], n, n_pad, k, mode, nullptr, stream);
-            if (rc) return rc;
-        }
-        return CLV_OK;
-    }
-    hipStream_t st = as_stream(stream);
-    const uint64_t wpt = ((n + 7) / 8 + TS_THREADS - 1) / TS_THREADS;         // words per thread, as clv4_threshold
-    for (uint64_t j0 = 0; j0 < nvec; j0 += TS_BATCH_GROUP) {
-        const uint64_t g = nvec - j0 < TS_BATCH_GROUP ? nvec - j0 : TS_BATCH_GROUP;
-        ThreshBatchArgs args;
-        for (uint64_t j = 0; j < TS_BATCH_GROUP; j++) {
-            args.q[j] = j < g ? (uint32_t *)q[j0 + j] : nullptr;
-            args.s[j] = j < g ? s[j0 + j] : nullptr;
-        }
-#define T4_LAUNCH(W) hipLaunchKernelGGL(k_thresh_small_batch<W>, dim3((unsigned)g), dim3(TS_THREADS), 0, st, args, (uint32_t)n, (uint32_t)k)
-        if (wpt <= 1) T4_LAUNCH(1);
-        else if (wpt <= 2) T4_LAUNCH(2);
-        else if (wpt <= 4) T4_LAUNCH(4);
-        else if (wpt <= 8) T4_LAUNCH(8);
-        else T4_LAUNCH(16);
-#undef T4_LAUNCH
-        CLV_LAUNCH_CHECK();
-    }
     return CLV_OK;
 }
 
-// threshold_min_heap (CloverVector4.h:1929-1970, CloverVector8.h:1696-1737): the REFERENCE walk, and the K-entry heap as the walk leaves it
-template <int BITS>
-static int threshold_heap(const char *fn, int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream)
+static int thresh_check_sizes(const char *fn, uint64_t n, uint64_t n_pad)
 {
-    CLV_REQUIRE(q && s && heap_dev, "%s: null pointer", fn);
     CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "%s: n=%llu n_pad=%llu", fn, (unsigned long long)n, (unsigned long long)n_pad);
     CLV_REQUIRE(n < (1ull << 32), "%s: vectors of 2^32 or more elements are not supported", fn);
+    return CLV_OK;
+}
+
+// one vector's pointers (`others`: the entry's further pointers are all there), then its sizes
+template <int BITS>
+static int thresh_check_vector(const char *fn, const void *q, const float *s, bool others, uint64_t n, uint64_t n_pad)
+{
+    typedef ThreshHost<BITS> H;
+    CLV_REQUIRE(q && (s || !H::SCALES) && others, "%s: null pointer", fn);
+    CLV_REQUIRE(!H::ALIGNED_X || ((uintptr_t)q & 15u) == 0, "%s: x must be 16-byte aligned", fn);
+    return thresh_check_sizes(fn, n, n_pad);
+}
+
+// FAST on checked arguments with k < n: the one-workgroup kernel up to its limit, the large-vector path beyond
+template <int BITS>
+static int threshold_fast(uint32_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *workspace, hipStream_t st)
+{
+    typedef ThreshHost<BITS> H;
+    if (n_pad <= (uint64_t)TS_THREADS * H::MAXW * H::EPW && (!H::SMALL_SWITCH || clv_env_int(H::SMALL_SWITCH, 1))) {
+        thresh_ladder<H::MAXW>(thresh_words_per_thread<H>(n), [&](auto w) {
+            constexpr int W = decltype(w)::value;
+            if constexpr (H::SCALES) hipLaunchKernelGGL(H::template small<W>, dim3(1), dim3(TS_THREADS), 0, st, q, s, (uint32_t)n, (uint32_t)k);
+            else hipLaunchKernelGGL(H::template small<W>, dim3(1), dim3(TS_THREADS), 0, st, q, (uint32_t)n, (uint32_t)k);
+        });
+        CLV_LAUNCH_CHECK();
+        return CLV_OK;
+    }
+    if (!workspace) {
+        int rc = clv_internal_workspace(&workspace, H::workspace_bytes(n_pad), st);
+        if (rc) return rc;
+    }
+    return H::large(q, s, n, n_pad, k, workspace, st);
+}
+
+// a single call: every check in the entries' order -- mode, pointers, (alignment of x,) sizes, workspace --, the early return, the mode.
+// MODE = false: the plain entries of CloverVector4 / 8, which have no mode argument and never name the reference walk.
+template <int BITS, bool MODE>
+static int threshold_single(const char *fn, void *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream)
+{
+    int rc = MODE ? thresh_check_mode(fn, mode) : CLV_OK;
+    if (!rc) rc = thresh_check_vector<BITS>(fn, q, s, true, n, n_pad);
+    if (rc) return rc;
+    CLV_REQUIRE_WORKSPACE(fn, workspace);
+    if (k >= n || n == 0) return CLV_OK;                       // everything survives
+    if constexpr (MODE)
+        if (mode == CLV_THRESHOLD_REFERENCE) return threshold_reference<BITS>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream));
+    return threshold_fast<BITS>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream));
+}
+
+// threshold_min_heap (CloverVector4.h:1929-1970, CloverVector8.h:1696-1737, CloverVector16.h:612-768): the REFERENCE walk, and the K-entry
+// heap as the walk leaves it
+template <int BITS>
+static int threshold_heap(const char *fn, void *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream)
+{
+    int rc = thresh_check_vector<BITS>(fn, q, s, heap_dev != nullptr, n, n_pad);
+    if (rc) return rc;
     // the reference's loop copies the first k elements into the heap unconditionally: k > n reads beyond the vector there -- rejected here
     CLV_REQUIRE(k >= 1 && k <= n, "%s: k=%llu must lie in 1 .. n=%llu", fn, (unsigned long long)k, (unsigned long long)n);
     CLV_REQUIRE_WORKSPACE(fn, workspace);
     return threshold_reference<BITS>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream), (uint2 *)heap_dev);
 }
-extern "C" int clv4_threshold_heap(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream)
-{
-    return threshold_heap<4>("clv4_threshold_heap", q, s, n, n_pad, k, heap_dev, workspace, stream);
-}
-extern "C" int clv8_threshold_heap(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream)
-{
-    return threshold_heap<8>("clv8_threshold_heap", q, s, n, n_pad, k, heap_dev, workspace, stream);
-}
 
-// CloverVector8::threshold(K) (CloverVector8.h:1680-1740): same algorithm and tie rule on |q * scale / 127|
-extern "C" int clv8_threshold(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *workspace, void *stream)
+// threshold on nvec vectors of one size.  q / s: HOST arrays of nvec device pointers.  FAST up to the one-workgroup limit: one launch per
+// TS_BATCH_GROUP vectors, workgroup j = the one-workgroup kernel's body on vector j; otherwise the sequence of single calls (`single`: the
+// width's _mode entry).  Bit-identical to that sequence.
+template <int BITS>
+static int threshold_batch(const char *fn, int (*single)(int8_t *, const float *, uint64_t, uint64_t, uint64_t, int, void *, void *),
+                           int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *stream)
 {
-    CLV_REQUIRE(q && s, "clv8_threshold: null pointer");
-    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv8_threshold: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
-    CLV_REQUIRE(n < (1ull << 32), "clv8_threshold: vectors of 2^32 or more elements are not supported");
-    CLV_REQUIRE_WORKSPACE("clv8_threshold", workspace);
-    hipStream_t st = as_stream(stream);
-    if (k >= n || n == 0) return CLV_OK;
-    if (n_pad <= (uint64_t)TS_THREADS * TS8_MAXW * 4) {
-        const uint64_t w = ((n + 3) / 4 + TS_THREADS - 1) / TS_THREADS;
-#define T8_LAUNCH(W) hipLaunchKernelGGL(k_thresh8_small<W>, dim3(1), dim3(TS_THREADS), 0, st, (uint32_t *)q, s, (uint32_t)n, (uint32_t)k)
-        if (w <= 1) T8_LAUNCH(1);
-        else if (w <= 2) T8_LAUNCH(2);
-        else if (w <= 4) T8_LAUNCH(4);
-        else T8_LAUNCH(8);
-#undef T8_LAUNCH
-        CLV_LAUNCH_CHECK();
-        return CLV_OK;
-    }
-    if (!workspace) {
-        int rc = clv_internal_workspace(&workspace, clv8_threshold_workspace_bytes(n_pad), as_stream(stream));
-        if (rc) return rc;
-    }
-    return threshold_large<8>((uint32_t *)q, s, n, k, workspace, st);
-}
-
-extern "C" int clv8_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream)
-{
-    if (mode == CLV_THRESHOLD_FAST) return clv8_threshold(q, s, n, n_pad, k, workspace, stream);
-    CLV_REQUIRE(mode == CLV_THRESHOLD_REFERENCE, "clv8_threshold_mode: unknown mode %d", mode);
-    CLV_REQUIRE(q && s, "clv8_threshold_mode: null pointer");
-    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv8_threshold_mode: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
-    CLV_REQUIRE(n < (1ull << 32), "clv8_threshold_mode: vectors of 2^32 or more elements are not supported");
-    CLV_REQUIRE_WORKSPACE("clv8_threshold_mode", workspace);
-    if (k >= n || n == 0) return CLV_OK;
-    return threshold_reference<8>((uint32_t *)q, s, n, n_pad, k, workspace, as_stream(stream));
-}
-
-// CloverVector8::threshold on nvec vectors of one size.  q / s: HOST arrays of nvec device pointers.  FAST up to the one-workgroup limit
-// (n_pad <= 32768): one launch per TS_BATCH_GROUP vectors, workgroup j = k_thresh8_small's body on vector j; otherwise the sequence of single
-// calls.  Bit-identical to that sequence.
-extern "C" int clv8_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode,
-                                    void *stream)
-{
-    const char *fn = "clv8_threshold_batch";
-    CLV_REQUIRE(mode == CLV_THRESHOLD_FAST || mode == CLV_THRESHOLD_REFERENCE, "%s: unknown mode %d", fn, mode);
-    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "%s: n=%llu n_pad=%llu", fn, (unsigned long long)n, (unsigned long long)n_pad);
-    CLV_REQUIRE(n < (1ull << 32), "%s: vectors of 2^32 or more elements are not supported", fn);
+    typedef ThreshHost<BITS> H;
+    int rc = thresh_check_mode(fn, mode);
+    if (!rc) rc = thresh_check_sizes(fn, n, n_pad);
+    if (rc) return rc;
     if (!nvec) return CLV_OK;
     CLV_REQUIRE(q && s, "%s: null pointer array", fn);
     for (uint64_t j = 0; j < nvec; j++) CLV_REQUIRE(q[j] && s[j], "%s: null pointer in vector %llu", fn, (unsigned long long)j);
-    {
-        std::vector<ClvRange> rg;
-        rg.reserve(2 * nvec);
-        for (uint64_t j = 0; j < nvec; j++) {
-            rg.push_back(clv_range(q[j], n_pad, true, j, "q"));
-            rg.push_back(clv_range(s[j], n_pad / 64 * sizeof(float), false, j, "s"));
-        }
-        int rc = clv_internal_check_ranges(fn, rg);
-        if (rc) return rc;
+    std::vector<ClvRange> rg;
+    rg.reserve(2 * nvec);
+    for (uint64_t j = 0; j < nvec; j++) {
+        rg.push_back(clv_range(q[j], H::q_bytes(n_pad), true, j, "q"));
+        rg.push_back(clv_range(s[j], n_pad / 64 * sizeof(float), false, j, "s"));
     }
+    rc = clv_internal_check_ranges(fn, rg);
+    if (rc) return rc;
     if (k >= n || n == 0) return CLV_OK;                       // everything survives
-    if (nvec == 1 || mode != CLV_THRESHOLD_FAST || n_pad > (uint64_t)TS_THREADS * TS8_MAXW * 4) {
+    if (nvec == 1 || mode != CLV_THRESHOLD_FAST || n_pad > (uint64_t)TS_THREADS * H::MAXW * H::EPW) {
         for (uint64_t j = 0; j < nvec; j++) {
-            int rc = clv8_threshold_mode(q[j], s[j], n, n_pad, k, mode, nullptr, stream);
+            rc = single(q[j], s[j], n, n_pad, k, mode, nullptr, stream);
             if (rc) return rc;
         }
         return CLV_OK;
     }
     hipStream_t st = as_stream(stream);
-    const uint64_t wpt = ((n + 3) / 4 + TS_THREADS - 1) / TS_THREADS;         // words per thread, as clv8_threshold
+    const uint64_t wpt = thresh_words_per_thread<H>(n);         // as the single call
     for (uint64_t j0 = 0; j0 < nvec; j0 += TS_BATCH_GROUP) {
         const uint64_t g = nvec - j0 < TS_BATCH_GROUP ? nvec - j0 : TS_BATCH_GROUP;
         ThreshBatchArgs args;
@@ -2109,99 +2124,77 @@ extern "C" int clv8_threshold_batch(int8_t *const *q, const float *const *s, uin
             args.q[j] = j < g ? (uint32_t *)q[j0 + j] : nullptr;
             args.s[j] = j < g ? s[j0 + j] : nullptr;
         }
-#define T8B_LAUNCH(W) hipLaunchKernelGGL(k_thresh8_small_batch<W>, dim3((unsigned)g), dim3(TS_THREADS), 0, st, args, (uint32_t)n, (uint32_t)k)
-        if (wpt <= 1) T8B_LAUNCH(1);
-        else if (wpt <= 2) T8B_LAUNCH(2);
-        else if (wpt <= 4) T8B_LAUNCH(4);
-        else T8B_LAUNCH(8);
-#undef T8B_LAUNCH
+        thresh_ladder<H::MAXW>(wpt, [&](auto w) {
+            hipLaunchKernelGGL(H::template small_batch<decltype(w)::value>, dim3((unsigned)g), dim3(TS_THREADS), 0, st, args, (uint32_t)n, (uint32_t)k);
+        });
         CLV_LAUNCH_CHECK();
     }
     return CLV_OK;
 }
 
+// ---- the entries: each names its width and the name its errors are reported under
+extern "C" uint64_t clv4_threshold_workspace_bytes(uint64_t n_pad) { return ThreshHost<4>::workspace_bytes(n_pad); }
+extern "C" uint64_t clv8_threshold_workspace_bytes(uint64_t n_pad) { return ThreshHost<8>::workspace_bytes(n_pad); }
+extern "C" uint64_t clv_f16_threshold_workspace_bytes(uint64_t n_pad) { return ThreshHost<16>::workspace_bytes(n_pad); }
+extern "C" uint64_t clv_f32_threshold_workspace_bytes(uint64_t n_pad) { return ThreshHost<32>::workspace_bytes(n_pad); }
+
+// CloverVector4::threshold(K), FAST.  The _mode entry's FAST IS this call, errors under this name included.
+extern "C" int clv4_threshold(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *workspace, void *stream)
+{
+    return threshold_single<4, false>("clv4_threshold", q, s, n, n_pad, k, CLV_THRESHOLD_FAST, workspace, stream);
+}
+extern "C" int clv4_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream)
+{
+    if (mode == CLV_THRESHOLD_FAST) return clv4_threshold(q, s, n, n_pad, k, workspace, stream);
+    return threshold_single<4, true>("clv4_threshold_mode", q, s, n, n_pad, k, mode, workspace, stream);
+}
+extern "C" int clv4_threshold_heap(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream)
+{
+    return threshold_heap<4>("clv4_threshold_heap", q, s, n, n_pad, k, heap_dev, workspace, stream);
+}
+extern "C" int clv4_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode,
+                                    void *stream)
+{
+    return threshold_batch<4>("clv4_threshold_batch", clv4_threshold_mode, q, s, nvec, n, n_pad, k, mode, stream);
+}
+
+// CloverVector8::threshold(K) (CloverVector8.h:1680-1740): same algorithm and tie rule on |q * scale / 127|
+extern "C" int clv8_threshold(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *workspace, void *stream)
+{
+    return threshold_single<8, false>("clv8_threshold", q, s, n, n_pad, k, CLV_THRESHOLD_FAST, workspace, stream);
+}
+extern "C" int clv8_threshold_mode(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream)
+{
+    if (mode == CLV_THRESHOLD_FAST) return clv8_threshold(q, s, n, n_pad, k, workspace, stream);
+    return threshold_single<8, true>("clv8_threshold_mode", q, s, n, n_pad, k, mode, workspace, stream);
+}
+extern "C" int clv8_threshold_heap(int8_t *q, const float *s, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream)
+{
+    return threshold_heap<8>("clv8_threshold_heap", q, s, n, n_pad, k, heap_dev, workspace, stream);
+}
+extern "C" int clv8_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode,
+                                    void *stream)
+{
+    return threshold_batch<8>("clv8_threshold_batch", clv8_threshold_mode, q, s, nvec, n, n_pad, k, mode, stream);
+}
+
 // CloverVector16::threshold(K) / threshold_min_heap (CloverVector16.h:612-768): the same selection on |f32(h)|, two elements per word and no
 // scales.  FAST: k_f16_thresh_small up to n_pad = 32768 (one launch, no workspace), the large-vector path beyond -- and at every n with
 // CLV_F16_THRESHOLD_SMALL=0 (read per call: A/B runs flip it); the two give the same bits.
-extern "C" uint64_t clv_f16_threshold_workspace_bytes(uint64_t n_pad)
-{
-    const uint64_t blocks = (n_pad / 2 + TH_WORDS_PER_BLOCK - 1) / TH_WORDS_PER_BLOCK;
-    return 4096 * sizeof(uint32_t) + 256 + blocks * sizeof(uint32_t) + 256;
-}
-
 extern "C" int clv_f16_threshold_mode(uint16_t *h, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream)
 {
-    CLV_REQUIRE(mode == CLV_THRESHOLD_FAST || mode == CLV_THRESHOLD_REFERENCE, "clv_f16_threshold_mode: unknown mode %d", mode);
-    CLV_REQUIRE(h, "clv_f16_threshold_mode: null pointer");
-    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv_f16_threshold_mode: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
-    CLV_REQUIRE(n < (1ull << 32), "clv_f16_threshold_mode: vectors of 2^32 or more elements are not supported");
-    CLV_REQUIRE_WORKSPACE("clv_f16_threshold_mode", workspace);
-    if (k >= n || n == 0) return CLV_OK;
-    if (mode == CLV_THRESHOLD_REFERENCE) return threshold_reference<16>((uint32_t *)h, nullptr, n, n_pad, k, workspace, as_stream(stream));
-    if (n_pad <= (uint64_t)TS_THREADS * TS_MAXW * 2 && clv_env_int("CLV_F16_THRESHOLD_SMALL", 1)) {
-        const uint64_t w = ((n + 1) / 2 + TS_THREADS - 1) / TS_THREADS;
-#define TF_LAUNCH(W) hipLaunchKernelGGL(k_f16_thresh_small<W>, dim3(1), dim3(TS_THREADS), 0, as_stream(stream), (uint32_t *)h, (uint32_t)n, (uint32_t)k)
-        if (w <= 1) TF_LAUNCH(1);
-        else if (w <= 2) TF_LAUNCH(2);
-        else if (w <= 4) TF_LAUNCH(4);
-        else if (w <= 8) TF_LAUNCH(8);
-        else TF_LAUNCH(16);
-#undef TF_LAUNCH
-        CLV_LAUNCH_CHECK();
-        return CLV_OK;
-    }
-    if (!workspace) {
-        int rc = clv_internal_workspace(&workspace, clv_f16_threshold_workspace_bytes(n_pad), as_stream(stream));
-        if (rc) return rc;
-    }
-    return threshold_large<16>((uint32_t *)h, nullptr, n, k, workspace, as_stream(stream));
+    return threshold_single<16, true>("clv_f16_threshold_mode", h, nullptr, n, n_pad, k, mode, workspace, stream);
 }
-
 extern "C" int clv_f16_threshold_heap(uint16_t *h, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream)
 {
-    CLV_REQUIRE(h && heap_dev, "clv_f16_threshold_heap: null pointer");
-    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv_f16_threshold_heap: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
-    CLV_REQUIRE(n < (1ull << 32), "clv_f16_threshold_heap: vectors of 2^32 or more elements are not supported");
-    CLV_REQUIRE(k >= 1 && k <= n, "clv_f16_threshold_heap: k=%llu must lie in 1 .. n=%llu", (unsigned long long)k, (unsigned long long)n);
-    CLV_REQUIRE_WORKSPACE("clv_f16_threshold_heap", workspace);
-    return threshold_reference<16>((uint32_t *)h, nullptr, n, n_pad, k, workspace, as_stream(stream), (uint2 *)heap_dev);
+    return threshold_heap<16>("clv_f16_threshold_heap", h, nullptr, n, n_pad, k, heap_dev, workspace, stream);
 }
 
 // CloverVector32::threshold(K) (CloverVector32.h:549-600): the same selection on |x|, one element per word and no scales.  FAST:
 // k_f32_thresh_small up to n_pad = TS_THREADS * TS_MAXW = 16384 (one launch, no workspace), the large-vector path beyond -- and at every n
 // with CLV_F32_THRESHOLD_SMALL=0 (read per call: A/B runs flip it); the two give the same bits.  NaN patterns have keys above infinity's:
 // FAST keeps them first (include/clover_hip_fp32.h).
-extern "C" uint64_t clv_f32_threshold_workspace_bytes(uint64_t n_pad)
-{
-    const uint64_t blocks = (n_pad + TH_WORDS_PER_BLOCK - 1) / TH_WORDS_PER_BLOCK;
-    return 4096 * sizeof(uint32_t) + 256 + blocks * sizeof(uint32_t) + 256;
-}
-
 extern "C" int clv_f32_threshold_mode(float *x, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *workspace, void *stream)
 {
-    CLV_REQUIRE(mode == CLV_THRESHOLD_FAST || mode == CLV_THRESHOLD_REFERENCE, "clv_f32_threshold_mode: unknown mode %d", mode);
-    CLV_REQUIRE(x, "clv_f32_threshold_mode: null pointer");
-    CLV_REQUIRE(((uintptr_t)x & 15u) == 0, "clv_f32_threshold_mode: x must be 16-byte aligned");
-    CLV_REQUIRE(n_pad % 128 == 0 && n <= n_pad, "clv_f32_threshold_mode: n=%llu n_pad=%llu", (unsigned long long)n, (unsigned long long)n_pad);
-    CLV_REQUIRE(n < (1ull << 32), "clv_f32_threshold_mode: vectors of 2^32 or more elements are not supported");
-    CLV_REQUIRE_WORKSPACE("clv_f32_threshold_mode", workspace);
-    if (k >= n || n == 0) return CLV_OK;
-    if (mode == CLV_THRESHOLD_REFERENCE) return threshold_reference<32>((uint32_t *)x, nullptr, n, n_pad, k, workspace, as_stream(stream));
-    if (n_pad <= (uint64_t)TS_THREADS * TS_MAXW && clv_env_int("CLV_F32_THRESHOLD_SMALL", 1)) {
-        const uint64_t w = (n + TS_THREADS - 1) / TS_THREADS;
-#define T32_LAUNCH(W) hipLaunchKernelGGL(k_f32_thresh_small<W>, dim3(1), dim3(TS_THREADS), 0, as_stream(stream), (uint32_t *)x, (uint32_t)n, (uint32_t)k)
-        if (w <= 1) T32_LAUNCH(1);
-        else if (w <= 2) T32_LAUNCH(2);
-        else if (w <= 4) T32_LAUNCH(4);
-        else if (w <= 8) T32_LAUNCH(8);
-        else T32_LAUNCH(16);
-#undef T32_LAUNCH
-        CLV_LAUNCH_CHECK();
-        return CLV_OK;
-    }
-    if (!workspace) {
-        int rc = clv_internal_workspace(&workspace, clv_f32_threshold_workspace_bytes(n_pad), as_stream(stream));
-        if (rc) return rc;
-    }
-    return threshold_large<32>((uint32_t *)x, nullptr, n, k, workspace, as_stream(stream));
+    return threshold_single<32, true>("clv_f32_threshold_mode", x, nullptr, n, n_pad, k, mode, workspace, stream);
 }
