@@ -4,6 +4,7 @@
 // 64x64 tile in a row-major (rows/64) x (cols/64) grid.  Value = q * (scale / 127).  Every kernel below reproduces the
 // reference's SIMD arithmetic order bit for bit; tests/matrix8_restate.c states the same orders on the CPU.
 #include "rng_device.h"
+#include "mvm8_device.h"
 
 #include <stdlib.h>
 
@@ -142,7 +143,7 @@ __device__ __forceinline__ void m8_mvm_steps(const u32x2 *__restrict__ Ar, const
 #pragma unroll
     for (int u = 0; u < M8_MVM_U; u++) {
         if (u < nb) {
-            const float c = (su[u] * (1.0f / 127.0f)) * (sv[u] * (1.0f / 127.0f));
+            const float c = m8_factor(su[u], sv[u]);
             a0 = __builtin_fmaf(c, (float)i8dot4(hi[u].x, xh[u].x, i8dot4(lo[u].x, xl[u].x, 0)), a0);
             a1 = __builtin_fmaf(c, (float)i8dot4(hi[u].y, xh[u].y, i8dot4(lo[u].y, xl[u].y, 0)), a1);
         }
@@ -216,7 +217,7 @@ __device__ __forceinline__ void m8_mvm_body(const uint8_t *__restrict__ A, const
     if (tid < 64) {
         const float d = dsh[tid];
         float noise = 0.0f;
-        if (ST) noise = noise_of(reinterpret_cast<const uint32_t *>(raw + (size_t)(tid >> 5) * 4)[tid & 7], (tid >> 3) & 3);
+        if (ST) noise = m8_mvm_noise(raw, tid);
         const float m = fix_zero_max(wave_max(__builtin_fabsf(d)));
         const float k = 127.0f / m;
         const int qv = quant1(d, k, noise);
@@ -227,7 +228,7 @@ __device__ __forceinline__ void m8_mvm_body(const uint8_t *__restrict__ A, const
         if (FUSE) {
             const float val = __builtin_fmaf((float)qv, div127(m * fuse.a), (float)fuse_q * div127(fuse_s));
             float noise2 = 0.0f;
-            if (ST) noise2 = noise_of(reinterpret_cast<const uint32_t *>(raw2 + (size_t)(tid >> 5) * 4)[(tid & 31) >> 2], tid & 3);
+            if (ST) noise2 = m8_saa_noise(raw2, tid);
             const float m2 = fix_zero_max(wave_max(__builtin_fabsf(val)));
             fuse.r2[rb * 64 + tid] = (int8_t)quant1(val, 127.0f / m2, noise2);
             if (tid == 0) fuse.sr2[rb] = m2;

@@ -1,12 +1,20 @@
-// mvm8_device.h -- device helpers shared by the mixed mvm kernels (4-bit matrix x CloverVector8): k_m4_mvm8 (mixed8.hip) and
-// k_m4_mvm8_batch (mvm_batch8.hip).  The bits of a result are fixed by this instruction sequence, so both kernels take it from here
-// (as mvm_device.h does for the 4-bit pair).
+// mvm8_device.h -- device helpers shared by the mvm kernels with CloverVector8 vectors: the mixed ones (4-bit matrix: k_m4_mvm8, mixed8.hip;
+// k_m4_mvm8_batch, mvm_batch8.hip; k_m4_mvm8_t, mvm_t8.hip) and, for the factor, the noise maps, the tree and the re-quantisation, the
+// CloverMatrix8 ones (k_m8_mvm, matrix8.hip; k_m8_mvm_t, matrix8_t.hip).  The bits of a result are fixed by this instruction sequence, so
+// the kernels take it from here (as mvm_device.h does for the 4-bit pair).
 #pragma once
 
-#include "common.h"
+#include "rng_device.h"
 
 // the size rules of the mixed mvm family (mixed8.hip): rows % 64 == 0, cols % 128 == 0, no NULL among the four pointers
 int check_mvm8_args(const char *fn, const void *A, const void *sA, uint64_t rows, uint64_t cols, const void *x, const void *sx);
+
+// the argument checks of the transposed calls that take CloverVector8 vectors (mvm_t8.hip; clm4_mvm_v8_transposed* and clm8_mvm_transposed*),
+// before any device work: a_bytes = the bytes of A's values (rows * cols / 2 for a CloverMatrix4, rows * cols for a CloverMatrix8).
+// qu == NULL: the plain call.  > 0: nothing to do (an empty matrix)
+int clv_internal_check_mvm8_t_args(const char *fn, const void *A, uint64_t a_bytes, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x,
+                                   const float *sx, bool fused, const int8_t *qu, const float *su, const int8_t *t, const float *st_, const int8_t *r,
+                                   const float *sr);
 
 // 8 nibbles of a dword (elements e0..e7) -> int8 dwords {e0..e3} and {e4..e7}, each value times 16
 __device__ __forceinline__ void widen8(uint32_t w, uint32_t &d03, uint32_t &d47)
@@ -50,6 +58,9 @@ __device__ __forceinline__ void mvm8_block(uint32_t w_first, uint32_t w_second, 
 
 // the block factor of the chains (CloverMatrix4.h:1147-1149)
 __device__ __forceinline__ float mvm8_factor(float sa, float sx) { return (sa * (1.0f / 7.0f)) * (sx * (1.0f / 127.0f)); }
+
+// the block factor of the CloverMatrix8 chains (CloverMatrix8.h:1002-1299): k_m8_mvm (matrix8.hip) and k_m8_mvm_t (matrix8_t.hip)
+__device__ __forceinline__ float m8_factor(float sa, float sx) { return (sa * (1.0f / 127.0f)) * (sx * (1.0f / 127.0f)); }
 
 // chain 2m / 2m+1 in lane m of the row's quad.  CloverMatrix4.h:1229-1234: h[L] = a[L+4] + a[L]; (h0 + h2) + (h1 + h3); the row's dot
 // product comes out in all four lanes
@@ -99,4 +110,16 @@ __device__ __forceinline__ void mvm8_requantize_wave(float d, float noise, float
         r2[lane] = (int8_t)quant1(val, 127.0f / m2, noise2);
         if (lane == 0) *sr2 = m2;
     }
+}
+
+// The element <-> noise maps of a 64-element block re-quantised by one wave (CloverMatrix8.h:1140-1299, CloverVector8.h:1089-1358): raw =
+// the block's two draws as gen_blocks leaves them (raw[4 draw + generator lane]), l = the element.  The mvm's re-quantisation takes draw
+// l >> 5, word l & 7, byte (l >> 3) & 3; the scaleAndAdd behind it draw l >> 5, word (l & 31) >> 2, byte l & 3.
+__device__ __forceinline__ float m8_mvm_noise(const uint64_t *raw, int l)
+{
+    return noise_of(reinterpret_cast<const uint32_t *>(raw + (size_t)(l >> 5) * 4)[l & 7], (l >> 3) & 3);
+}
+__device__ __forceinline__ float m8_saa_noise(const uint64_t *raw, int l)
+{
+    return noise_of(reinterpret_cast<const uint32_t *>(raw + (size_t)(l >> 5) * 4)[(l & 31) >> 2], l & 3);
 }

@@ -264,10 +264,11 @@ static int launch_mvm8_t(const int8_t *A, const float *sA, uint64_t rows, uint64
     return CLV_OK;
 }
 
-// the argument checks of both calls, before any device work (the rules of check_mvm_t_args, mvm_t4.hip, with CloverVector8 byte counts).
-// qu == NULL: the plain call.  > 0: nothing to do (an empty matrix)
-static int check_mvm8_t_args(const char *fn, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
-                             bool fused, const int8_t *qu, const float *su, const int8_t *t, const float *st_, const int8_t *r, const float *sr)
+// the argument checks of the transposed calls with CloverVector8 vectors, before any device work (the rules of check_mvm_t_args, mvm_t4.hip,
+// with CloverVector8 byte counts); declared in mvm8_device.h, shared with matrix8_t.hip
+int clv_internal_check_mvm8_t_args(const char *fn, const void *A, uint64_t a_bytes, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x,
+                                   const float *sx, bool fused, const int8_t *qu, const float *su, const int8_t *t, const float *st_, const int8_t *r,
+                                   const float *sr)
 {
     CLV_REQUIRE(A && sA && x && sx && r && sr && (!fused || (qu && su)), "%s: null pointer", fn);
     CLV_REQUIRE((t == nullptr) == (st_ == nullptr), "%s: t and st must both be given or both be NULL", fn);
@@ -278,7 +279,7 @@ static int check_mvm8_t_args(const char *fn, const int8_t *A, const float *sA, u
     std::vector<ClvRange> rg;
     rg.reserve(10);
     const uint64_t sc = sizeof(float);
-    rg.push_back(clv_range(A, rows * (cols / 2), false, ~0ull, "A"));
+    rg.push_back(clv_range(A, a_bytes, false, ~0ull, "A"));
     rg.push_back(clv_range(sA, (rows / 64) * (cols / 64) * sc, false, ~0ull, "sA"));
     rg.push_back(clv_range(x, rows, false, 0, "x"));
     rg.push_back(clv_range(sx, rows / 64 * sc, false, 0, "sx"));
@@ -299,7 +300,7 @@ static int check_mvm8_t_args(const char *fn, const int8_t *A, const float *sA, u
 extern "C" int clm4_mvm_v8_transposed(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx, int8_t *r,
                                       float *sr, uint64_t *rng_state_dev, void *stream)
 {
-    const int rc = check_mvm8_t_args("clm4_mvm_v8_transposed", A, sA, rows, cols, x, sx, false, nullptr, nullptr, nullptr, nullptr, r, sr);
+    const int rc = clv_internal_check_mvm8_t_args("clm4_mvm_v8_transposed", A, rows * (cols / 2), sA, rows, cols, x, sx, false, nullptr, nullptr, nullptr, nullptr, r, sr);
     if (rc) return rc > 0 ? CLV_OK : rc;
     return launch_mvm8_t(A, sA, rows, cols, x, sx, r, sr, rng_state_dev, as_stream(stream), nullptr);
 }
@@ -308,7 +309,7 @@ extern "C" int clm4_mvm_v8_transposed_scale_and_add(const int8_t *A, const float
                                                     const float *sx, const int8_t *qu, const float *su, float a, int8_t *t, float *st_, int8_t *r,
                                                     float *sr, uint64_t *rng_state_dev, void *stream)
 {
-    const int rc = check_mvm8_t_args("clm4_mvm_v8_transposed_scale_and_add", A, sA, rows, cols, x, sx, true, qu, su, t, st_, r, sr);
+    const int rc = clv_internal_check_mvm8_t_args("clm4_mvm_v8_transposed_scale_and_add", A, rows * (cols / 2), sA, rows, cols, x, sx, true, qu, su, t, st_, r, sr);
     if (rc) return rc > 0 ? CLV_OK : rc;
     const Mvm8Fuse fuse = {qu, su, a, r, sr};
     return launch_mvm8_t(A, sA, rows, cols, x, sx, t, st_, rng_state_dev, as_stream(stream), &fuse);

@@ -105,6 +105,10 @@ SIGNATURES = {
                            C.c_int, _vp, _vp]),
     "clm8_mvm_f32": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "clm8_transpose": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm8_mvm_transposed": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm8_mvm_transposed_scale_and_add": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm8_iht_one_matrix": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float,
+                                     C.c_int, _vp, _vp]),
     "clm8_gemm": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp]),
     "clm8_gemm_i32": (C.c_int, [_vp, _u64, _u64, _vp, _u64, _u64, _u64, _vp, _vp]),
     "clm4_gemm_m8": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp]),
@@ -609,18 +613,43 @@ class CloverHip:
 
     def m8_iht(self, qPhi, sPhi, qPhiT, sPhiT, m, n, qy, sy, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
                rng: DevBuf | None = None, prefill: int = 0x55):
-        """clm8_iht on buffers prefilled with `prefill` bytes: {"x": (q, s), "t1": ..., "t2": ..., "t3": ...}"""
-        b = [self.to_device(v) for v in (qPhi, sPhi, qPhiT, sPhiT, qy, sy)]
+        """clm8_iht on buffers prefilled with `prefill` bytes -- or, with qPhiT None, clm8_iht_one_matrix:
+        {"x": (q, s), "t1": ..., "t2": ..., "t3": ...}"""
+        b = [self.to_device(v) for v in ((qPhi, sPhi, qy, sy) if qPhiT is None else (qPhi, sPhi, qy, sy, qPhiT, sPhiT))]
         lens = {"x": n, "t1": m, "t2": m, "t3": n}
         v = {}
         for name, ln in lens.items():
             v[name] = (self.alloc(ln), self.alloc(ln // 16))
             for d in v[name]:
                 self.check(self.lib.clv_memset(d.ptr, prefill, d.nbytes, None))
-        self.check(self.lib.clm8_iht(b[0].ptr, b[1].ptr, b[2].ptr, b[3].ptr, m, n, v["x"][0].ptr, v["x"][1].ptr, n if x_len is None else x_len,
-                                     b[4].ptr, b[5].ptr, v["t1"][0].ptr, v["t1"][1].ptr, v["t2"][0].ptr, v["t2"][1].ptr, v["t3"][0].ptr,
-                                     v["t3"][1].ptr, iterations, K, mu, threshold, rng.ptr if rng else None, None))
+        tail = (v["x"][0].ptr, v["x"][1].ptr, n if x_len is None else x_len, b[2].ptr, b[3].ptr, v["t1"][0].ptr, v["t1"][1].ptr, v["t2"][0].ptr,
+                v["t2"][1].ptr, v["t3"][0].ptr, v["t3"][1].ptr, iterations, K, mu, threshold, rng.ptr if rng else None, None)
+        if qPhiT is None:
+            self.check(self.lib.clm8_iht_one_matrix(b[0].ptr, b[1].ptr, m, n, *tail))
+        else:
+            self.check(self.lib.clm8_iht(b[0].ptr, b[1].ptr, b[4].ptr, b[5].ptr, m, n, *tail))
         return {name: (v[name][0].download(np.int8, ln), v[name][1].download(np.float32, ln // 64)) for name, ln in lens.items()}
+
+    def m8_mvm_transposed(self, qA, sA, rows, cols, qx, sx, rng: DevBuf | None = None):
+        """(r, sr) of clm8_mvm_transposed: A is rows x cols, x has rows int8, r has cols.  qA may be a DevBuf (a matrix uploaded once)"""
+        dA, dsA = (qA, sA) if isinstance(qA, DevBuf) else (self.to_device(qA), self.to_device(sA))
+        dx, dsx = self.to_device(qx), self.to_device(sx)
+        dr, dsr = self.alloc(max(cols, 1)), self.alloc(max(cols // 16, 4))
+        self.check(self.lib.clm8_mvm_transposed(dA.ptr, dsA.ptr, rows, cols, dx.ptr, dsx.ptr, dr.ptr, dsr.ptr, rng.ptr if rng else None, None))
+        return dr.download(np.int8, cols), dsr.download(np.float32, cols // 64)
+
+    def m8_mvm_transposed_scale_and_add(self, qA, sA, rows, cols, qx, sx, qu, su, a: float, rng: DevBuf | None = None, in_place: bool = False,
+                                        want_t: bool = True):
+        """(t, st, r, sr) of clm8_mvm_transposed_scale_and_add (u, t, r: cols int8); t/st are None when want_t is False"""
+        dA, dsA = (qA, sA) if isinstance(qA, DevBuf) else (self.to_device(qA), self.to_device(sA))
+        b = [self.to_device(v) for v in (qx, sx, qu, su)]
+        dt, dst = (self.alloc(cols), self.alloc(cols // 16)) if want_t else (None, None)
+        dr, dsr = (b[2], b[3]) if in_place else (self.alloc(cols), self.alloc(cols // 16))
+        self.check(self.lib.clm8_mvm_transposed_scale_and_add(dA.ptr, dsA.ptr, rows, cols, b[0].ptr, b[1].ptr, b[2].ptr, b[3].ptr, a,
+                                                              dt.ptr if dt else None, dst.ptr if dst else None, dr.ptr, dsr.ptr,
+                                                              rng.ptr if rng else None, None))
+        t = (dt.download(np.int8, cols), dst.download(np.float32, cols // 64)) if want_t else (None, None)
+        return t[0], t[1], dr.download(np.int8, cols), dsr.download(np.float32, cols // 64)
 
     def m8_mvm_f32(self, qA, sA, rows, cols, x) -> np.ndarray:
         b = [self.to_device(a) for a in (qA, sA, np.ascontiguousarray(x, dtype=np.float32))]

@@ -288,6 +288,38 @@ inline void Q_GD<CloverMatrix8, CloverVector8>(CloverMatrix8 &Phi, CloverMatrix8
     }
 }
 
+/* Not in the reference: the two loops above with ONE matrix (CloverMatrix8::mvm_transposed_scaleAndAdd -> clm8_mvm_transposed_scale_and_add;
+ * rounding disabled: iht_loop_one_matrix -> clm8_iht_one_matrix), the bits of Q_IHT / Q_GD with PhiT = transpose(Phi).  Stochastic: the
+ * gradient step draws from Phi's generator, where the two-matrix loop draws from PhiT's.  The two-matrix forms stay the default. */
+inline void Q_IHT_one_matrix(CloverMatrix8 &Phi, CloverVector8 &x, CloverVector8 &y, CloverVector8 &t1, CloverVector8 &t2, CloverVector8 &t3,
+                             const uint64_t iterations, const uint64_t K, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, K, mu, true);
+    return;
+#endif
+    x.clear();
+    for (uint64_t i = 0; i < iterations; i += 1) {
+        Phi.mvm_scaleAndAdd(x, y, -1.0f, t1, t2);
+        Phi.mvm_transposed_scaleAndAdd(t2, x, mu, t3);
+        x.threshold_parallel(K);
+    }
+}
+
+inline void Q_GD_one_matrix(CloverMatrix8 &Phi, CloverVector8 &x, CloverVector8 &y, CloverVector8 &t1, CloverVector8 &t2, CloverVector8 &t3,
+                            const uint64_t iterations, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, 0, mu, false);
+    return;
+#endif
+    x.clear();
+    for (uint64_t i = 0; i < iterations; i += 1) {
+        Phi.mvm_scaleAndAdd(x, y, -1.0f, t1, t2);
+        Phi.mvm_transposed_scaleAndAdd(t2, x, mu, t3);
+    }
+}
+
 /* the same for `count` signals with ONE 8-bit Phi (clm8_iht_batch; stochastic: CloverMatrix8::mvm_batch_at per step): bit-identical to
  * calling Q_IHT / Q_GD above signal after signal, the generators of Phi and PhiT included */
 inline void Q_IHT_batch(CloverMatrix8 &Phi, CloverMatrix8 &PhiT, CloverVector8 *const *x, CloverVector8 *const *y, CloverVector8 *const *t1,

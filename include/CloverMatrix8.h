@@ -17,6 +17,9 @@
  *
  *   mvm_scaleAndAdd                    -> clm8_mvm_scale_and_add  (not in the reference: mvm + the scaleAndAdd behind it, one launch)
  *   iht_loop                           -> clm8_iht        (the whole Q_IHT / Q_GD loop of 01_measure.h:923-946, 999-1021 in one call)
+ *   mvm_transposed / mvm_transposed_scaleAndAdd / iht_loop_one_matrix
+ *                                      -> clm8_mvm_transposed, clm8_mvm_transposed_scale_and_add, clm8_iht_one_matrix (not in the reference:
+ *                                         this' * x from this matrix's own bytes, and the loop with no stored transpose)
  *   mvm_batch / mvm_batch_at / mvm_scaleAndAdd_batch / iht_loop_batch
  *                                      -> clm8_mvm_batch, clm8_mvm_batch_at, clm8_mvm_scale_and_add_batch, clm8_iht_batch (not in the
  *                                         reference: several vectors, ONE pass over the matrix per group of CLM4_MVM_BATCH_MAX)
@@ -243,6 +246,76 @@ public:
                                    x.size(), y.dev_values_ro(), y.dev_scales_ro(), t1.dev_values_wo(), t1.dev_scales_wo(), t2.dev_values_wo(),
                                    t2.dev_scales_wo(), t3.dev_values_wo(), t3.dev_scales_wo(), iterations, K, mu, thr, nullptr, nullptr),
                           "CloverMatrix8::iht_loop");
+        x.commit();
+        if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
+    }
+    /* Not in the reference: mvm_transposed and its fused forms (clm8_mvm_transposed, clm8_mvm_transposed_scale_and_add): resultVector =
+     * this' * productVector from this matrix's own bytes, bit for bit what transpose(T); T.mvm(productVector, resultVector) gives, with
+     * stochastic rounding the draws from THIS matrix's generator included. */
+    void mvm_transposed(const CloverVector8 &productVector, CloverVector8 &resultVector)
+    {
+        if (productVector.size() != getRows() || resultVector.size_pad() != getCols()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        clover_hip::check(clm8_mvm_transposed(dev_values(), dev_scales(), rows, cols, productVector.dev_values_ro(), productVector.dev_scales_ro(),
+                                              resultVector.dev_values_wo(), resultVector.dev_scales_wo(), clover_hip::rng_or_null(random), nullptr),
+                          "CloverMatrix8::mvm_transposed");
+        resultVector.commit();
+    }
+    void check_fused_transposed(const CloverVector8 &x, const CloverVector8 &u, const CloverVector8 &t) const
+    {
+        if (x.size() != getRows() || t.size_pad() != getCols()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
+        if (u.size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+    }
+    void mvm_transposed_scaleAndAdd(const CloverVector8 &x, const CloverVector8 &u, float a, CloverVector8 &t, CloverVector8 &r)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        check_fused_transposed(x, u, t);
+        if (r.size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        clover_hip::check(clm8_mvm_transposed_scale_and_add(dev_values(), dev_scales(), rows, cols, x.dev_values_ro(), x.dev_scales_ro(),
+                                                            u.dev_values_ro(), u.dev_scales_ro(), a, t.dev_values_wo(), t.dev_scales_wo(),
+                                                            r.dev_values_wo(), r.dev_scales_wo(), nullptr, nullptr),
+                          "CloverMatrix8::mvm_transposed_scaleAndAdd");
+        t.commit();
+        r.commit();
+#else
+        mvm_transposed(x, t);
+        const_cast<CloverVector8 &>(u).scaleAndAdd(t, a, r);
+#endif
+    }
+    /* in place: u = quantize(u + a * (this' * x)) */
+    void mvm_transposed_scaleAndAdd(const CloverVector8 &x, CloverVector8 &u, float a, CloverVector8 &t)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        check_fused_transposed(x, u, t);
+        int8_t *qu = u.dev_values_rw();
+        float *su = u.dev_scales_rw();
+        clover_hip::check(clm8_mvm_transposed_scale_and_add(dev_values(), dev_scales(), rows, cols, x.dev_values_ro(), x.dev_scales_ro(), qu, su, a,
+                                                            t.dev_values_wo(), t.dev_scales_wo(), qu, su, nullptr, nullptr),
+                          "CloverMatrix8::mvm_transposed_scaleAndAdd");
+        t.commit();
+        u.commit();
+#else
+        mvm_transposed(x, t);
+        u.scaleAndAdd(t, a);
+#endif
+    }
+    /* iht_loop with no PhiT (clm8_iht_one_matrix): the bits of iht_loop with PhiT = transpose of this, the same three launches per
+     * iteration.  Half the resident matrix bytes; DESIGN.md 3 has what that costs per iteration.  Deterministic rounding only, as iht_loop. */
+    void iht_loop_one_matrix(CloverVector8 &x, const CloverVector8 &y, CloverVector8 &t1, CloverVector8 &t2, CloverVector8 &t3,
+                             uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    {
+        if (x.size_pad() != getCols() || y.size_pad() != getRows() || t1.size_pad() != getRows() || t2.size_pad() != getRows() ||
+            t3.size_pad() != getCols()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm8_iht_one_matrix(dev_values(), dev_scales(), rows, cols, x.dev_values_wo(), x.dev_scales_wo(), x.size(),
+                                              y.dev_values_ro(), y.dev_scales_ro(), t1.dev_values_wo(), t1.dev_scales_wo(), t2.dev_values_wo(),
+                                              t2.dev_scales_wo(), t3.dev_values_wo(), t3.dev_scales_wo(), iterations, K, mu, thr, nullptr, nullptr),
+                          "CloverMatrix8::iht_loop_one_matrix");
         x.commit();
         if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
     }

@@ -33,7 +33,7 @@
  *    clm4_mvm_scale_and_add, clm4_mvm_transposed, clm4_mvm_transposed_scale_and_add, clm4_iht_one_matrix, clv8_quantize, clv8_scale_and_add,
  *    clm4_mvm_v8, clm4_mvm_v8_scale_and_add, clm4_mvm_v8_transposed, clm4_mvm_v8_transposed_scale_and_add, clm4_iht, clm4_iht_v8,
  *    clm4_iht_v8_one_matrix,
- *    clm8_quantize, clm8_mvm, clm8_mvm_scale_and_add, clm8_iht):
+ *    clm8_quantize, clm8_mvm, clm8_mvm_scale_and_add, clm8_iht, clm8_mvm_transposed, clm8_mvm_transposed_scale_and_add, clm8_iht_one_matrix):
  *      (1) calls that share a state buffer must be STREAM-ORDERED -- the same stream, or an event / sync between them: they consume one
  *          sequential XORShift stream, as the reference's methods do on one object, and each launch reads the state its predecessor left;
  *      (2) such a call must NOT be captured into a hipGraph unless its state is in graph mode (clv_rng_graph_mode): ordinarily every launch
@@ -375,6 +375,26 @@ int  clm8_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols
 /* CloverMatrix8::transpose / transpose_parallel (CloverMatrix8.h:1312-1386): qt(j,i) = q(i,j), the tile scale grid transposed.
  * q is rows x cols, qt is cols x rows; not in place.  Exact. */
 int  clm8_transpose(const int8_t *q, const float *s, uint64_t rows, uint64_t cols, int8_t *qt, float *st, void *stream);
+/* The transposed product r = quantize8(A' x) straight from A (rows x cols, the stored CloverMatrix8 layout: rows*cols bytes, then the
+ * (rows/64) x (cols/64) tile scales): x is a CloverVector8 of rows elements, r of cols elements.  CONTRACT: bit-identical to
+ * clm8_transpose(A -> At) followed by clm8_mvm(At, cols, rows, x -> r) on the same stream; with an rng output block cb takes draws 2 cb,
+ * 2 cb + 1 and the state is left advanced by 2 (cols/64), exactly as clm8_mvm on A' (stream-ordered per state; graph capture as clm8_mvm).
+ * rows and cols are multiples of 128 (rows == 0 or cols == 0: CLV_OK, nothing done), no pointer is NULL, and r / sr overlap none of A, sA,
+ * x, sx: CLV_ERR_INVALID before any device work otherwise.  No allocation, no workspace: the deterministic call captures into a hipGraph. */
+int  clm8_mvm_transposed(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
+                         int8_t *r, float *sr, uint64_t *rng_state_dev, void *stream);
+/* the fused form, arguments as clm8_mvm_scale_and_add: t = quantize8(A' x) (stored if t/st != NULL; both or neither),
+ * r = quantize8(u + a * t); u, t, r: cols elements.  r/sr may alias qu/su; no output may overlap anything else.  Bit-identical to
+ * clm8_mvm_scale_and_add on a stored A', including the second draw window 2 G + 2 cb (G = cols/64) and the state advanced by 4 G. */
+int  clm8_mvm_transposed_scale_and_add(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const int8_t *x, const float *sx,
+                                       const int8_t *qu, const float *su, float a, int8_t *t, float *st, int8_t *r, float *sr,
+                                       uint64_t *rng_state_dev, void *stream);
+/* clm8_iht without the PhiT / sPhiT pair: Phi' t2 is taken from Phi by clm8_mvm_transposed_scale_and_add; the same three launches per
+ * iteration.  Bit-identical to clm8_iht called with PhiT = transpose(Phi): x, t1 .. t3 and the generator state.  Half the resident matrix
+ * bytes; what that costs per iteration is measured in DESIGN.md 3. */
+int  clm8_iht_one_matrix(const int8_t *Phi, const float *sPhi, uint64_t m, uint64_t n, int8_t *x, float *sx, uint64_t x_len,
+                         const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3, float *st3,
+                         uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream);
 /* GEMM with 8-bit operands, build-defined like clm4_gemm (the reference has none): A is M x K, B is N x K (both CloverMatrix8
  * images), C = A * B^T as fp32 M x N row-major; M, N and K are non-zero multiples of 128.  Per element (i, j) and K-block b (64 elements):
  * S_b = the exact integer sum of the 64 byte products, and C[i][j] is ONE sequential chain over b = 0, 1, 2, ... from C = 0:

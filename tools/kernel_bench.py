@@ -619,6 +619,68 @@ if any(selected(r) for r in MVT8_ROWS):
         sys.exit(0)
 
 
+# ---- A' x for a CloverMatrix8 straight from A (matrix8_t.hip): the three rows per size of the two blocks above with clm8_mvm_transposed,
+# clm8_transpose + clm8_mvm and clm8_mvm on a held A', rounds alternated in one session; m8_iht_one_matrix_*: clm8_iht_one_matrix against clm8_iht
+# (launch per step either way: no persistent kernel at this width).
+# KB_ONLY=m8_mvm_transposed,m8_transpose_then_mvm,m8_mvm_held_transpose,m8_iht_one_matrix selects them and the run ends after them.
+M8T_ROWS = tuple(f"{k}_{nb}" for nb in MVT_SIZES for k in ("m8_mvm_transposed", "m8_transpose_then_mvm", "m8_mvm_held_transpose")) + \
+    ("m8_iht_one_matrix_N8192", "m8_iht_one_matrix_gd_32768^2")
+
+if any(selected(r) for r in M8T_ROWS):
+    for nb in MVT_SIZES:
+        if not any(selected(r) for r in M8T_ROWS if r.endswith(f"_{nb}")):
+            continue
+        (tA, tsA), tAt, tsAt = m8_matrix(nb, nb, 61), hip.alloc(nb * nb), hip.alloc(4 * (nb // 64) ** 2)
+        (tx, tsx), (tr, tsr) = vec8_set(1, nb, 310)[0], vec8_set(1, nb, 320)[0]
+        hip.check(lib.clm8_transpose(tA.ptr, tsA.ptr, nb, nb, tAt.ptr, tsAt.ptr, None))
+
+        def direct_m8():
+            hip.check(lib.clm8_mvm_transposed(tA.ptr, tsA.ptr, nb, nb, tx.ptr, tsx.ptr, tr.ptr, tsr.ptr, None, None))
+
+        def pair_m8():
+            hip.check(lib.clm8_transpose(tA.ptr, tsA.ptr, nb, nb, tAt.ptr, tsAt.ptr, None))
+            hip.check(lib.clm8_mvm(tAt.ptr, tsAt.ptr, nb, nb, tx.ptr, tsx.ptr, tr.ptr, tsr.ptr, None, None))
+
+        def held_m8():
+            hip.check(lib.clm8_mvm(tAt.ptr, tsAt.ptr, nb, nb, tx.ptr, tsx.ptr, tr.ptr, tsr.ptr, None, None))
+        d, p, h = alternated((direct_m8, pair_m8, held_m8), reps=20 if nb == 8192 else 10 if nb == 32768 else 4)
+        mat_b = nb * nb + 4 * (nb // 64) ** 2
+        one_b = mat_b + 2 * (nb + nb // 16)
+        md, mp, mh = d[len(d) // 2], p[len(p) // 2], h[len(h) // 2]
+        for name, t, m, nbytes in ((f"m8_mvm_transposed_{nb}", d, md, one_b), (f"m8_transpose_then_mvm_{nb}", p, mp, 2 * mat_b + one_b),
+                                   (f"m8_mvm_held_transpose_{nb}", h, mh, one_b)):
+            res[name] = {"ms": round(m, 5), "rounds_ms": [round(v, 5) for v in t], "spread_ms": round(t[-1] - t[0], 5),
+                         "GB/s": round(nbytes / m / 1e6, 1), "frac_of_8TBs": round(nbytes / m / 1e6 / 8000.0, 4)}
+        res[f"m8_mvm_transposed_{nb}"].update({
+            "speedup_over_transpose_then_mvm": round(mp / md, 3), "faster_than_the_pair_by_more_than_its_spread": bool(mp - md > p[-1] - p[0]),
+            "ratio_to_mvm_on_a_held_transpose": round(md / mh, 3), "within_the_spread_of_the_held_transpose_call": bool(abs(md - mh) <= h[-1] - h[0])})
+        del tA, tsA, tAt, tsAt
+    for name, im, inn, thr, iters in (("m8_iht_one_matrix_N8192", 4096, 8192, 1, 20), ("m8_iht_one_matrix_gd_32768^2", 32768, 32768, 0, 4)):
+        if not selected(name):
+            continue
+        (P, sP), PT, sPT = m8_matrix(im, inn, 63), hip.alloc(im * inn), hip.alloc(4 * (im // 64) * (inn // 64))
+        hip.check(lib.clm8_transpose(P.ptr, sP.ptr, im, inn, PT.ptr, sPT.ptr, None))
+        (vy, vx, vt1, vt2, vt3) = (vec8_set(1, n, seed)[0] for n, seed in ((im, 500), (inn, 600), (im, 700), (im, 800), (inn, 900)))
+        tail = (vx[0].ptr, vx[1].ptr, inn, vy[0].ptr, vy[1].ptr, vt1[0].ptr, vt1[1].ptr, vt2[0].ptr, vt2[1].ptr, vt3[0].ptr, vt3[1].ptr, iters, im // 4,
+                0.002, thr, None, None)
+
+        def two_m8():
+            hip.check(lib.clm8_iht(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, *tail))
+
+        def one_m8():
+            hip.check(lib.clm8_iht_one_matrix(P.ptr, sP.ptr, im, inn, *tail))
+        t2, t1 = ([v / iters for v in t] for t in alternated((two_m8, one_m8), reps=2))
+        m2, m1 = t2[len(t2) // 2], t1[len(t1) // 2]
+        res[name] = {"one_matrix_ms_per_iteration": round(m1, 5), "clm8_iht_ms_per_iteration": round(m2, 5),
+                     "one_matrix_rounds_ms": [round(v, 5) for v in t1], "clm8_iht_rounds_ms": [round(v, 5) for v in t2],
+                     "ratio_to_clm8_iht": round(m1 / m2, 3), "within_the_spread_of_clm8_iht": bool(abs(m1 - m2) <= t2[-1] - t2[0]),
+                     "note": f"calls of {iters} iterations, K = m / 4, threshold = {thr}; both loops are launch per step"}
+        del P, sP, PT, sPT
+    if ONLY and all(any(o in r for r in M8T_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
+
+
 # ---- vector ops at n = 2^30 (4 GiB fp32 source, 512 MiB + 64 MiB quantized) and n = 2^24
 for logn in (24, 30):
     n = 1 << logn
