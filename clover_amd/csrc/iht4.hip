@@ -22,7 +22,7 @@ int clv_internal_v4_clear(int8_t *x, float *sx, uint64_t n_pad, hipStream_t st)
 }
 
 // iht_persist.hip: the whole loop as one persistent launch with Phi and PhiT in LDS (N <= 8192, rounding disabled, threshold FAST or none);
-// 1 = launched, 0 = does not qualify, < 0 = error
+// 1 = launched, 0 = does not qualify, < 0 = a CLV_ERR_* code
 int clm4_iht_persistent(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, int8_t *x,
                         float *sx, uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3,
                         float *st3, uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng, hipStream_t st);
@@ -51,7 +51,7 @@ extern "C" int clm4_iht(const int8_t *Phi, const float *sPhi, const int8_t *PhiT
     {
         const int p = clm4_iht_persistent(Phi, sPhi, PhiT, sPhiT, m, n, x, sx, x_len, y, sy, t1, st1, t2, st2, t3, st3, iterations, K, mu, threshold,
                                           rng_state_dev, st);
-        if (p < 0) return CLV_ERR_HIP;
+        if (p < 0) return p;
         if (p > 0) return CLV_OK;
     }
     int rc = clv_internal_v4_clear(x, sx, n, st);   // x.clear()

@@ -1226,7 +1226,8 @@ template <class Args> static void ihtp_probe_overrides(Args &a)
 }
 #endif
 
-// returns 1 if the persistent kernel was launched, 0 if the problem does not qualify (the caller runs the launch-per-step loop), < 0 on error
+// returns 1 if the persistent kernel was launched, 0 if the problem does not qualify (the caller runs the launch-per-step loop), a CLV_ERR_* code
+// on error
 int clm4_iht_persistent(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, int8_t *x,
                         float *sx, uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3,
                         float *st3, uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng, hipStream_t st)
@@ -1264,10 +1265,10 @@ int clm4_iht_persistent(const int8_t *Phi, const float *sPhi, const int8_t *PhiT
     }
     void *ws = nullptr;
     int rc = clv_internal_workspace(&ws, (m + n) * sizeof(u64), st);
-    if (rc) return -1;
+    if (rc) return rc;                                                  // under capture without scratch: CLV_ERR_INVALID and the advice
     if (hipMemsetAsync(ws, 0, (m + n) * sizeof(u64), st) != hipSuccess) {
         clv_set_error("clm4_iht: hipMemsetAsync failed: %s", hipGetErrorString(hipGetLastError()));
-        return -1;
+        return CLV_ERR_HIP;
     }
     IhtpArgs a;
     a.Phi = (const uint8_t *)Phi; a.sPhi = sPhi; a.PhiT = (const uint8_t *)PhiT; a.sPhiT = sPhiT;
@@ -1280,13 +1281,13 @@ int clm4_iht_persistent(const int8_t *Phi, const float *sPhi, const int8_t *PhiT
     a.seq = 0;
     a.seg_rows = nullptr;
     if (rng) {
-        if (ihtp_jump_matrices((m + n) / 64 * 4, &a.seg_rows, a.jump, a.jump1)) return -1;
+        if (ihtp_jump_matrices((m + n) / 64 * 4, &a.seg_rows, a.jump, a.jump1)) return CLV_ERR_HIP;
     }
     a.nap0 = 14;         // ~0.4 us: measured best of 0 / 6 / 10 / 14 / 18 / 22 / 26 ... 40 at N = 8192 (profiles/r06_iht_persist_notes.txt)
     a.nap = 2;
     CLV_PROBE(ihtp_probe_overrides(a);)
     PersistChain chain(st);
-    if (chain.rc) return -1;
+    if (chain.rc) return CLV_ERR_HIP;
     if (rng) {
         a.seq = clv_rng_seq_for(rng, st);                                  // right in front of the launch, as every stochastic call
         hipLaunchKernelGGL(k_iht4_persist<true>, dim3(grid), dim3(IHTP_THREADS), L.total, st, a);
@@ -1296,7 +1297,7 @@ int clm4_iht_persistent(const int8_t *Phi, const float *sPhi, const int8_t *PhiT
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         clv_set_error("clm4_iht: persistent launch failed: %s", hipGetErrorString(e));
-        return -1;
+        return CLV_ERR_HIP;
     }
     g_persist_launches.fetch_add(1, std::memory_order_relaxed);
     return 1;
@@ -1335,7 +1336,7 @@ bool clm4_iht_v8_persistent_eligible(uint64_t m, uint64_t n, uint64_t iterations
     return ihtp8_eligible(m, n, iterations, threshold, stochastic, nullptr);
 }
 
-// the CloverVector8 loop (clm4_iht_v8): 1 = launched, 0 = does not qualify, < 0 = error
+// the CloverVector8 loop (clm4_iht_v8): 1 = launched, 0 = does not qualify, < 0 = a CLV_ERR_* code
 int clm4_iht_v8_persistent(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, int8_t *x, float *sx,
                            uint64_t x_len, const int8_t *y, const float *sy, int8_t *t1, float *st1, int8_t *t2, float *st2, int8_t *t3, float *st3,
                            uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng, hipStream_t st)
@@ -1360,10 +1361,11 @@ int clm4_iht_v8_persistent(const int8_t *Phi, const float *sPhi, const int8_t *P
         }
     }
     void *ws = nullptr;
-    if (clv_internal_workspace(&ws, (m + n) * sizeof(u64), st)) return -1;
+    int rc = clv_internal_workspace(&ws, (m + n) * sizeof(u64), st);
+    if (rc) return rc;
     if (hipMemsetAsync(ws, 0, (m + n) * sizeof(u64), st) != hipSuccess) {
         clv_set_error("clm4_iht_v8: hipMemsetAsync failed: %s", hipGetErrorString(hipGetLastError()));
-        return -1;
+        return CLV_ERR_HIP;
     }
     Ihtp8Args a;
     a.Phi = (const uint8_t *)Phi; a.sPhi = sPhi; a.PhiT = (const uint8_t *)PhiT; a.sPhiT = sPhiT;
@@ -1378,9 +1380,9 @@ int clm4_iht_v8_persistent(const int8_t *Phi, const float *sPhi, const int8_t *P
     a.rng = rng;
     a.seq = 0;
     a.seg_rows = nullptr;
-    if (rng && ihtp_jump_matrices((m + n) / 64 * 4, &a.seg_rows, a.jump, a.jump1)) return -1;
+    if (rng && ihtp_jump_matrices((m + n) / 64 * 4, &a.seg_rows, a.jump, a.jump1)) return CLV_ERR_HIP;
     PersistChain chain(st);
-    if (chain.rc) return -1;
+    if (chain.rc) return CLV_ERR_HIP;
     if (rng) {
         a.seq = clv_rng_seq_for(rng, st);
         hipLaunchKernelGGL(k_iht8_persist<true>, dim3(grid), dim3(IHTP_THREADS), L.total, st, a);
@@ -1390,7 +1392,7 @@ int clm4_iht_v8_persistent(const int8_t *Phi, const float *sPhi, const int8_t *P
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         clv_set_error("clm4_iht_v8: persistent launch failed: %s", hipGetErrorString(e));
-        return -1;
+        return CLV_ERR_HIP;
     }
     g_persist_launches.fetch_add(1, std::memory_order_relaxed);
     return 1;

@@ -850,7 +850,7 @@ extern "C" int clm4_iht_v8(const int8_t *Phi, const float *sPhi, const int8_t *P
     {
         const int p = clm4_iht_v8_persistent(Phi, sPhi, PhiT, sPhiT, m, n, x, sx, x_len, y, sy, t1, st1, t2, st2, t3, st3, iterations, K, mu, threshold,
                                              rng_state_dev, st);
-        if (p < 0) return CLV_ERR_HIP;
+        if (p < 0) return p;
         if (p > 0) return CLV_OK;
     }
     int rc0 = clv_internal_v8_clear(x, sx, n, st);      // x.clear()

@@ -87,38 +87,57 @@ long long clv_env_int(const char *name, long long dflt)
 // Grow-only scratch, one buffer per (device, stream): used when a caller passes workspace == NULL (clv4_dot, threshold) and by
 // clm4_gemm for the FP6 operand images.  Calls on DIFFERENT streams never share a buffer, so they may overlap; calls on one
 // stream are ordered by the stream.  Growing a buffer waits for that stream only (its old buffer may still be in use there).
+// Under a stream capture nothing is allocated, freed or waited for (all three are illegal there): a capturing stream gets the buffer an
+// ordinary call left it, or CLV_ERR_INVALID.  A buffer handed out under capture is `captured`: a graph holds its address, so when a later
+// call needs more the buffer is retired -- kept until clv_internal_workspace_forget(stream) -- instead of freed.
 struct WsEntry {
     int dev;
     hipStream_t stream;
     void *ptr;
     uint64_t bytes;
+    bool captured;
 };
 static std::mutex g_ws_mutex;
 static std::vector<WsEntry> g_ws;
+static std::vector<WsEntry> g_ws_retired;
 
 int clv_internal_workspace(void **ptr, uint64_t bytes, hipStream_t stream)
 {
     int dev = 0;
     CLV_HIP(hipGetDevice(&dev));
+    // one status query per call, as PersistChain::begin makes it; the legacy default stream cannot be captured and is not asked
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (stream != nullptr && hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    const bool capturing = cs != hipStreamCaptureStatusNone;
     std::lock_guard<std::mutex> lock(g_ws_mutex);
     WsEntry *e = nullptr;
     for (auto &w : g_ws)
         if (w.dev == dev && w.stream == stream) { e = &w; break; }
+    if (capturing && (!e || e->bytes < bytes)) {
+        clv_set_error("this stream is being captured and its library scratch holds %llu bytes where this call needs %llu: make one ordinary call "
+                      "of this size on the stream before hipStreamBeginCapture",
+                      (unsigned long long)(e ? e->bytes : 0), (unsigned long long)bytes);
+        return CLV_ERR_INVALID;
+    }
     if (!e) {
-        g_ws.push_back(WsEntry{dev, stream, nullptr, 0});
+        g_ws.push_back(WsEntry{dev, stream, nullptr, 0, false});
         e = &g_ws.back();
     }
     if (e->bytes < bytes) {
-        if (e->ptr) {
+        if (e->ptr && e->captured) {
+            g_ws_retired.push_back(*e);                  // a graph may replay on it: it lives as long as the stream
+        } else if (e->ptr) {
             CLV_HIP(hipStreamSynchronize(stream));
             CLV_HIP(hipFree(e->ptr));
-            e->ptr = nullptr;
-            e->bytes = 0;
         }
+        e->ptr = nullptr;
+        e->bytes = 0;
+        e->captured = false;
         uint64_t want = bytes < (1ull << 20) ? (1ull << 20) : bytes;
         CLV_HIP(hipMalloc(&e->ptr, want));
         e->bytes = want;
     }
+    if (capturing) e->captured = true;
     *ptr = e->ptr;
     return CLV_OK;
 }
@@ -158,7 +177,7 @@ int clv_internal_sync_slots(void **ptr, uint64_t bytes, hipStream_t stream)
     return CLV_OK;
 }
 
-// a destroyed stream's handle may be re-used by the runtime for a new stream: drop its scratch with it
+// a destroyed stream's handle may be re-used by the runtime for a new stream: drop its scratch with it, the buffers retired under it too
 void clv_internal_workspace_forget(hipStream_t stream)
 {
     std::lock_guard<std::mutex> lock(g_ws_mutex);
@@ -170,12 +189,14 @@ void clv_internal_workspace_forget(hipStream_t stream)
             k++;
         }
     }
-    for (size_t k = 0; k < g_ws.size();) {
-        if (g_ws[k].stream == stream && stream != nullptr) {
-            if (g_ws[k].ptr) (void)hipFree(g_ws[k].ptr);
-            g_ws.erase(g_ws.begin() + (long)k);
-        } else {
-            k++;
+    for (auto *list : {&g_ws, &g_ws_retired}) {
+        for (size_t k = 0; k < list->size();) {
+            if ((*list)[k].stream == stream && stream != nullptr) {
+                if ((*list)[k].ptr) (void)hipFree((*list)[k].ptr);
+                list->erase(list->begin() + (long)k);
+            } else {
+                k++;
+            }
         }
     }
 }

@@ -43,7 +43,14 @@
  *      (3) a state belongs to the process that initialised it (re-key with clv_rng_set after sharing the buffer across processes).
  *  - asynchrony: every call only enqueues work on `stream`; results are valid after clv_stream_sync / an event.
  *    clv4_dot, the threshold functions (when `workspace` is NULL) and clm4_gemm use grow-only scratch owned by the library, one
- *    buffer per (device, stream): calls on different streams never share scratch and may overlap.  clv4_dot / clv8_dot in CLV_DOT_FAST
+ *    buffer per (device, stream): calls on different streams never share scratch and may overlap.  The scratch under a stream capture:
+ *    a call that uses it (clv4_dot / clv8_dot EXACT, the thresholds beyond one workgroup, REFERENCE mode and the heap forms, clm4_gemm,
+ *    the loops and batch calls that contain one of them -- each with `workspace` NULL) must have been made once, AT THAT SIZE, on the stream
+ *    before hipStreamBeginCapture: inside a capture nothing is allocated, freed or waited for, and a call that finds no scratch, or too
+ *    little, returns CLV_ERR_INVALID with that advice and leaves the capture valid (tests/test_capture_base.py).  A buffer that was handed
+ *    out under capture is never freed while its stream lives: when a later, larger call makes the scratch grow, the captured buffer is set
+ *    aside and the graph goes on replaying in it.  It is released by clv_stream_destroy -- do not destroy a stream whose graphs are still
+ *    replayed (on any stream).  clv4_dot / clv8_dot in CLV_DOT_FAST
  *    mode are ONE launch whose workgroups hand their partials over through 64 KiB of zero-initialised slots, also per (device, stream),
  *    allocated (hipMalloc + a memset on the stream) by the first such call there: make one ordinary call on a stream before capturing
  *    it into a hipGraph (tests/test_graph_capture.py; a first call under capture returns CLV_ERR_INVALID with that advice); the kernel
@@ -52,11 +59,17 @@
  *    would share slots); (b) the collecting workgroup (the grid's last) assumes every other workgroup of the grid has been dispatched
  *    when it runs: true of this hardware's dispatchers, not a guarantee of the HIP model -- its wait is bounded (4 s, then a trap) so
  *    that an anomaly is an error, not a hang.
- *  - clm4_iht runs Q_IHT / Q_GD as ONE persistent launch when the problem qualifies (rounding disabled, threshold FAST or none, m and
- *    n <= 8192 and both matrices fit the chip's LDS): every workgroup of its grid must be resident at once, so (a) two such launches on
+ *  - clm4_iht and clm4_iht_v8 run Q_IHT / Q_GD as ONE persistent launch when the problem qualifies (threshold FAST or none, m and
+ *    n <= 8192, both matrices fit the chip's LDS; with an rng also m + n >= 512): every workgroup of its grid must be resident at once, so (a) two such launches on
  *    different streams of one device are chained by an event (the second waits for the first; no host blocking), (b) ANOTHER PROCESS
  *    running such a launch on the same device at the same time is not covered -- the kernel's waits are bounded (4 s, then a trap),
  *    (c) CLV_IHT_PERSISTENT=0 in the environment (read per call) selects the launch-per-step loop.  Same bits either way.
+ *    The persistent form is not meant for a hipGraph: every workgroup of its grid must be resident at once, and the chain of (a), which
+ *    keeps two such grids off the device at the same time, is skipped under capture (the event would become part of the graph), so
+ *    nothing orders a replay against a persistent launch on another stream.  The launch-per-step loop is the capturable form: set
+ *    CLV_IHT_PERSISTENT=0 while the capture is recorded (the graph then holds those kernels whatever the variable says later), with
+ *    or without an rng -- a state in graph mode does NOT keep clm4_iht / clm4_iht_v8 off the persistent kernel -- or call the
+ *    *_one_matrix loops, which never take it (tests/test_capture_base.py).
  */
 #ifndef CLOVER_HIP_H
 #define CLOVER_HIP_H

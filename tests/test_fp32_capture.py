@@ -2,43 +2,14 @@
 eager call bit for bit.  The calls only enqueue; what they need from the library (the stream's scratch, the hand-over slots of dot FAST)
 is allocated by one ordinary call on the stream before the capture, as for the other widths.  Every call is a sequence of launches on one
 stream: the graphs are linear."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from clover_amd.lib_binding import DOT_EXACT, DOT_FAST, SIGNATURES_FP32, THRESHOLD_FAST, THRESHOLD_REFERENCE
+from capture_helpers import Graph, ok
 from fp32_helpers import iht_problem, make_ops, threshold_data
 
 pytestmark = pytest.mark.gpu
-
-
-def ok(rc):
-    assert rc == 0, f"HIP runtime call failed: {rc}"
-
-
-class Graph:
-    def __init__(self):
-        self.rt = C.CDLL("libamdhip64.so")
-        self.stream, self.graph, self.gexec = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        ok(self.rt.hipStreamCreate(C.byref(self.stream)))
-
-    def capture(self, enqueue):
-        enqueue(self.stream)                                           # one ordinary call first
-        ok(self.rt.hipStreamSynchronize(self.stream))
-        ok(self.rt.hipStreamBeginCapture(self.stream, 0))
-        enqueue(self.stream)
-        ok(self.rt.hipStreamEndCapture(self.stream, C.byref(self.graph)))
-        ok(self.rt.hipGraphInstantiate(C.byref(self.gexec), self.graph, None, None, 0))
-
-    def replay(self):
-        ok(self.rt.hipGraphLaunch(self.gexec, self.stream))
-        ok(self.rt.hipStreamSynchronize(self.stream))
-
-    def close(self):
-        ok(self.rt.hipGraphExecDestroy(self.gexec))
-        ok(self.rt.hipGraphDestroy(self.graph))
-        ok(self.rt.hipStreamDestroy(self.stream))
 
 
 N, ROWS, COLS, K = 8192 + 128, 256, 512, 700
@@ -120,7 +91,7 @@ def test_captured_call_replays_to_the_eager_bits(hip, name):
         assert np.array_equal(got, eager.download(np.uint8)), (name, rep)
         results.append(got)
     assert not np.array_equal(results[0], results[1])                  # the replays did compute from the new operands
-    g.close()
+    g.close(hip.lib)                                                   # the stream's scratch goes with it
 
 
 def test_the_case_list_covers_every_fp32_entry_point():

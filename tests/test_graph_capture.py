@@ -115,8 +115,10 @@ def test_captured_matrix_stochastic_calls_walk_the_stream_on_every_replay(hip, o
     """one stochastic call of each matrix-level entry and of the 8-bit vector calls, captured into ONE linear stream on one state in
     graph mode: clm8_quantize, clm8_mvm, clm4_quantize (its public entry always has rows / 64 >= 2: the <2> strip kernel, sequence
     number in the argument list), clm4_mvm, clm4_mvm_v8, clm4_mvm_scale_and_add, clv8_quantize, clv8_scale_and_add.  Every replay gives
-    the next part of the oracle's walk, and ordinary calls continue from where the replays left the state.  (clm4_iht* and the large-n
-    threshold are not captured: their persistent kernels spin-wait on each other and need every workgroup co-resident.)"""
+    the next part of the oracle's walk, and ordinary calls continue from where the replays left the state.  (The persistent one-launch
+    form of clm4_iht* is not captured: its workgroups spin-wait on each other and need to be co-resident; tests/test_capture_base.py
+    captures the launch-per-step loops, CLV_IHT_PERSISTENT=0.  The large-n threshold, whose middle launch is persistent too, IS captured:
+    tests/test_threshold_large3.py and the first-large rows of tests/test_capture_base.py.)"""
     from conftest import random_packed
     from matrix8_helpers import build_restate
     m8 = build_restate(tmp_path_factory.getbasetemp(), parallel=False)

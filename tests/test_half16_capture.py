@@ -1,43 +1,14 @@
 """Every half-precision entry point captured once into a hipGraph and replayed on changing operands: the replay equals the eager call bit
 for bit.  The calls only enqueue; what they need from the library (the stream's scratch, the hand-over slots of dot FAST) is allocated by
 one ordinary call on the stream before the capture, as for the other widths."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from clover_amd.lib_binding import DOT_EXACT, DOT_FAST, THRESHOLD_FAST, THRESHOLD_REFERENCE
+from capture_helpers import Graph, ok
 from half16_helpers import random_f16_bits
 
 pytestmark = pytest.mark.gpu
-
-
-def ok(rc):
-    assert rc == 0, f"HIP runtime call failed: {rc}"
-
-
-class Graph:
-    def __init__(self):
-        self.rt = C.CDLL("libamdhip64.so")
-        self.stream, self.graph, self.gexec = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        ok(self.rt.hipStreamCreate(C.byref(self.stream)))
-
-    def capture(self, enqueue):
-        enqueue(self.stream)                                           # one ordinary call first
-        ok(self.rt.hipStreamSynchronize(self.stream))
-        ok(self.rt.hipStreamBeginCapture(self.stream, 0))
-        enqueue(self.stream)
-        ok(self.rt.hipStreamEndCapture(self.stream, C.byref(self.graph)))
-        ok(self.rt.hipGraphInstantiate(C.byref(self.gexec), self.graph, None, None, 0))
-
-    def replay(self):
-        ok(self.rt.hipGraphLaunch(self.gexec, self.stream))
-        ok(self.rt.hipStreamSynchronize(self.stream))
-
-    def close(self):
-        ok(self.rt.hipGraphExecDestroy(self.gexec))
-        ok(self.rt.hipGraphDestroy(self.graph))
-        ok(self.rt.hipStreamDestroy(self.stream))
 
 
 N, ROWS, COLS, K = 8192 + 128, 192, 512, 700
@@ -121,7 +92,7 @@ def test_captured_call_replays_to_the_eager_bits(hip, name):
         assert np.array_equal(got, eager.download(np.uint8)), (name, rep)
         results.append(got)
     assert not np.array_equal(results[0], results[1])                  # the replays did compute from the new operands
-    g.close()
+    g.close(hip.lib)                                                   # the stream's scratch goes with it
 
 
 def test_the_case_list_covers_every_f16_entry_point():
