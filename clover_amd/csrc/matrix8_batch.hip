@@ -76,7 +76,7 @@ __global__ __launch_bounds__(M8B_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t st_seq = 0;
     uint64_t *st_next = nullptr;
-    if constexpr (ST) st_next = mvmb_rng_prologue<NV, NW>(rs, nv, rb, sbase, st_seq);
+    if constexpr (ST) st_next = mvmb_rng_prologue<NV, NW>(rs, nv, rb, gridDim.x, sbase, st_seq);
 
     const int p = tid & 3, rho = tid >> 2;
     const uint64_t row = rb * 64 + rho;
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(M8B_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
 
 // ---- dispatch ----------------------------------------------------------------------------------------------------------------
 // what the host driver (mvm_batch_host.h) needs to know of this family
-struct M8Batch {
+struct M8Batch : MvmBatchByRows {
     template <int NV> using Args = M8BatchArgs<NV>;
     template <int NV> using Fuse = M8BatchFuse<NV>;
     static uint64_t matrix_bytes(uint64_t rows, uint64_t cols) { return rows * cols; }
@@ -194,7 +194,7 @@ struct M8Batch {
     // so the rule of the fused mvm holds (mvm_batch_selected)
     static bool iht_prefers_single(uint64_t, uint64_t, uint64_t, int, bool, uint64_t) { return false; }
     template <int NV, bool NT, bool FUSE, bool ST>
-    static void launch(dim3 grid, hipStream_t st, const uint8_t *A, const float *sA, uint64_t cols, int nv, const Args<NV> &arg, const Fuse<NV> &fuse,
+    static void launch(dim3 grid, hipStream_t st, const uint8_t *A, const float *sA, uint64_t, uint64_t cols, int nv, const Args<NV> &arg, const Fuse<NV> &fuse,
                        const MvmBatchRng &rs)
     {
         hipLaunchKernelGGL((k_m8_mvm_batch<NV, M8B_U, NT, FUSE, ST>), grid, dim3(M8B_THREADS), M8B_LDS_BYTES(NV, ST, FUSE), st, A, sA, cols, nv, arg, fuse,

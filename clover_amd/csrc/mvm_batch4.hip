@@ -6,6 +6,9 @@
 // sequence is the one of mvm_device.h, so the results equal the single calls bit for bit.
 #include "mvm_batch_host.h"
 #include "mvm_device.h"
+#include "mvm_t4_batch.h"
+
+#include "clover_hip_batch_t.h"
 
 #include <algorithm>
 #include <atomic>
@@ -16,23 +19,8 @@
 #define MVMB_THREADS 256
 #define MVMB_U(NV) ((NV) <= 4 ? 8 : 4)          // 4 accumulators per vector + 4 U registers of matrix words
 
-// the vectors of one pass, BY VALUE in the kernel arguments: no pointer table in device memory, nothing to allocate, captures into a graph.
-// Slots >= nv are absent: NULL, never dereferenced.
-template <int NV>
-struct MvmBatchArgs {
-    const uint8_t *x[NV];
-    const float *sx[NV];
-    uint32_t *r[NV];         // all NULL: the mvm result is not stored (FUSE only)
-    float *sr[NV];
-};
-template <int NV>
-struct MvmBatchFuse {        // see MvmFuse
-    const uint32_t *qu[NV];
-    const float *su[NV];
-    uint32_t *r2[NV];        // may be qu (in place)
-    float *sr2[NV];
-    float a;
-};
+// MvmBatchArgs / MvmBatchFuse (the vectors of one pass, by value in the kernel arguments): mvm_device.h, shared with the transposed batched
+// kernel (mvm_t4_batch.hip)
 
 // MvmBatchRng (where the draws of a launch lie in the XORShift stream), wave_pow_apply_many, mvmb_noise and the jump-ahead prologue:
 // mvm_batch_device.h, shared with the mixed batched kernel (mvm_batch8.hip)
@@ -68,7 +56,7 @@ __global__ __launch_bounds__(MVMB_THREADS) __attribute__((amdgpu_waves_per_eu(4,
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t st_seq = 0;
     uint64_t *st_next = nullptr;
-    if constexpr (ST) st_next = mvmb_rng_prologue<NV, NW>(rs, nv, rb, sbase, st_seq);
+    if constexpr (ST) st_next = mvmb_rng_prologue<NV, NW>(rs, nv, rb, gridDim.x, sbase, st_seq);
 
     const int q = tid & 3, rho = tid >> 2;
     const uint64_t row = rb * 64 + rho;
@@ -205,7 +193,7 @@ uint64_t clv_internal_first_bad_window(uint64_t nvec, uint64_t draw_base, uint64
 }
 
 // what the host driver (mvm_batch_host.h) needs to know of this family
-struct Mvm4Batch {
+struct Mvm4Batch : MvmBatchByRows {
     template <int NV> using Args = MvmBatchArgs<NV>;
     template <int NV> using Fuse = MvmBatchFuse<NV>;
     static uint64_t matrix_bytes(uint64_t rows, uint64_t cols) { return rows * (cols / 2); }
@@ -228,7 +216,7 @@ struct Mvm4Batch {
         return g < CLM4_MVM_BATCH_MAX && threshold <= 1 && iterations && m <= 8192 && n <= 8192 && clv_env_int("CLV_IHT_PERSISTENT", 1) != 0;
     }
     template <int NV, bool NT, bool FUSE, bool ST>
-    static void launch(dim3 grid, hipStream_t st, const uint8_t *A, const float *sA, uint64_t cols, int nv, const Args<NV> &arg, const Fuse<NV> &fuse,
+    static void launch(dim3 grid, hipStream_t st, const uint8_t *A, const float *sA, uint64_t, uint64_t cols, int nv, const Args<NV> &arg, const Fuse<NV> &fuse,
                        const MvmBatchRng &rs)
     {
         hipLaunchKernelGGL((k_m4_mvm_batch<NV, MVMB_U(NV), NT, FUSE, ST>), grid, dim3(MVMB_THREADS), MVMB_LDS_BYTES(NV, ST, FUSE), st, A, sA, cols, nv,
@@ -283,4 +271,15 @@ extern "C" int clm4_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t
 {
     return mvm_batch_iht<Mvm4Batch>("clm4_iht_batch", Phi, sPhi, PhiT, sPhiT, m, n, nvec, x, sx, x_len, y, sy, t1, st1, t2, st2, t3, st3, iterations, K,
                                     mu, threshold, rng_state_dev, stream);
+}
+
+// The same loop with ONE matrix (include/clover_hip_batch_t.h): step 1 is this family's fused launch on Phi, step 2 the transposed
+// family's (mvm_t4_batch.hip) on the same bytes; the draws lie where the two-matrix loop has them.
+extern "C" int clm4_iht_batch_one_matrix(const int8_t *Phi, const float *sPhi, uint64_t m, uint64_t n, uint64_t nvec, int8_t *const *x,
+                                         float *const *sx, uint64_t x_len, const int8_t *const *y, const float *const *sy, int8_t *const *t1,
+                                         float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
+                                         uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream)
+{
+    return mvm_batch_iht<Mvm4Batch, MvmT4Batch>("clm4_iht_batch_one_matrix", Phi, sPhi, nullptr, nullptr, m, n, nvec, x, sx, x_len, y, sy, t1, st1, t2,
+                                                st2, t3, st3, iterations, K, mu, threshold, rng_state_dev, stream);
 }

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(MVMB8_THREADS) __attribute__((amdgpu_waves_per_eu(4
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t st_seq = 0;
     uint64_t *st_next = nullptr;
-    if constexpr (ST) st_next = mvmb_rng_prologue<NV, NW>(rs, nv, rb, sbase, st_seq);
+    if constexpr (ST) st_next = mvmb_rng_prologue<NV, NW>(rs, nv, rb, gridDim.x, sbase, st_seq);
 
     const int m = tid & 3, rho = tid >> 2;
     const uint64_t row = rb * 64 + rho;
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(MVMB8_THREADS) __attribute__((amdgpu_waves_per_eu(4
 
 // ---- dispatch ----------------------------------------------------------------------------------------------------------------
 // what the host driver (mvm_batch_host.h) needs to know of this family
-struct Mvm8Batch {
+struct Mvm8Batch : MvmBatchByRows {
     template <int NV> using Args = Mvm8BatchArgs<NV>;
     template <int NV> using Fuse = Mvm8BatchFuse<NV>;
     static uint64_t matrix_bytes(uint64_t rows, uint64_t cols) { return rows * (cols / 2); }
@@ -191,7 +191,7 @@ struct Mvm8Batch {
         return !(stochastic && g == CLM4_MVM_BATCH_MAX) && clm4_iht_v8_persistent_eligible(m, n, iterations, threshold, stochastic);
     }
     template <int NV, bool NT, bool FUSE, bool ST>
-    static void launch(dim3 grid, hipStream_t st, const uint8_t *A, const float *sA, uint64_t cols, int nv, const Args<NV> &arg, const Fuse<NV> &fuse,
+    static void launch(dim3 grid, hipStream_t st, const uint8_t *A, const float *sA, uint64_t, uint64_t cols, int nv, const Args<NV> &arg, const Fuse<NV> &fuse,
                        const MvmBatchRng &rs)
     {
         hipLaunchKernelGGL((k_m4_mvm8_batch<NV, MVMB8_U(NV), NT, FUSE, ST>), grid, dim3(MVMB8_THREADS), MVMB8_LDS_BYTES(NV, ST, FUSE), st, A, sA, cols,

@@ -1,6 +1,7 @@
 // mvm_batch_host.h -- the host side of the batched mvm families, written once: group policy, launch, the two group loops, the argument
 // and overlap check and the batched IHT / GD loop.  Included by mvm_batch4.hip (CloverMatrix4 x CloverVector4), mvm_batch8.hip
-// (CloverMatrix4 x CloverVector8) and matrix8_batch.hip (CloverMatrix8 x CloverVector8) and by nothing else.  Each of them defines its
+// (CloverMatrix4 x CloverVector8), matrix8_batch.hip (CloverMatrix8 x CloverVector8) and mvm_t4_batch.hip (CloverMatrix4' x CloverVector4
+// straight from the matrix's own bytes) and by nothing else.  Each of them defines its
 // kernel and a traits struct F with exactly what differs between the families:
 //   Args<NV>, Fuse<NV>                        the kernel's by-value argument structs (their pointer types decide the casts)
 //   matrix_bytes(rows, cols), vector_bytes(n) sizes for the overlap check; the matrix streams (NT) above the 256 MiB Infinity Cache
@@ -10,11 +11,15 @@
 //   clear, threshold_batch                    x.clear() of one vector, the threshold of a group
 //   iht_prefers_single(...)                   whether a group of the IHT loop is better off as single calls (measured per family)
 //   launch<NV, NT, FUSE, ST>(...)             the hipLaunchKernelGGL of the family's kernel, with its U and LDS bytes
+//   x_len, r_len, grid, batched_by_rule       which dimension sizes x and which r, the grid of a launch and the measured dispatch rule:
+//                                             MvmBatchByRows (below) for the three families that walk the matrix by rows
 #pragma once
 
 #include "mvm_batch_device.h"
 
 #include <stdlib.h>
+
+#include <type_traits>
 
 // CLV_MVM_BATCH, read on every call (as CLV_IHT_PERSISTENT: the tests and tools/kernel_bench.py flip it inside one process):
 // 1 = always batched, 0 = never, -1 = unset
@@ -23,6 +28,15 @@ static inline int mvm_batch_forced()
     const char *e = clv_env("CLV_MVM_BATCH");
     return e && *e ? (atoi(e) != 0) : -1;
 }
+
+// what the three row-major families share: r = A x has `rows` elements, x `cols`; one workgroup per 64-row block; every group of two
+// or more runs batched (measured, see mvm_batch_selected)
+struct MvmBatchByRows {
+    static uint64_t x_len(uint64_t, uint64_t cols) { return cols; }
+    static uint64_t r_len(uint64_t rows, uint64_t) { return rows; }
+    static dim3 grid(uint64_t rows, uint64_t) { return dim3((unsigned)(rows / 64)); }
+    static bool batched_by_rule(uint64_t g, uint64_t, uint64_t, bool, bool) { return g >= 2; }
+};
 
 // Whether a group of g vectors runs as one batched launch or as g single launches.  Forced to 1, with an rng a remainder group of ONE vector
 // (nvec = 9, 17, ...) runs batched too: a forced call then hands the state from batched launch to batched launch throughout, which is what
@@ -34,11 +48,13 @@ static inline int mvm_batch_forced()
 //           batched launch beat the single calls by more than their spread in every row -- 65536^2 and 32768^2 (streaming), fused at
 //           8192 x 4096 (cache-resident) and at 65536^2, the IHT loop at N = 8192, either rounding.  Not measured: groups of 3 and 5-7,
 //           matrices between 32 MiB and 1 GiB or below 32 MiB.
-static inline bool mvm_batch_selected(uint64_t g, bool stochastic)
+// The transposed family has a rule of its own (MvmT4Batch::batched_by_rule, mvm_t4_batch.hip).
+template <class F>
+static inline bool mvm_batch_selected(uint64_t g, uint64_t rows, uint64_t cols, bool fused, bool stochastic)
 {
     if (g < 2 && !stochastic) return false;
     const int force = mvm_batch_forced();
-    return force >= 0 ? force != 0 : g >= 2;
+    return force >= 0 ? force != 0 : F::batched_by_rule(g, rows, cols, fused, stochastic);
 }
 
 // the vectors of a batch call (host arrays of device pointers) in the kernel's terms: r / sr NULL = the mvm result is not stored (fused
@@ -96,20 +112,20 @@ static int mvm_batch_launch(const int8_t *A, const float *sA, uint64_t rows, uin
         // every launch takes a number of its own, committing or not: it is what picks the slot to read
         rs = MvmBatchRng{dr.rng, clv_rng_seq_for(dr.rng, st), T.pow_rows, dr.base, dr.stride, dr.commit};
     }
-    const dim3 grid((unsigned)(rows / 64));
+    const dim3 grid = F::grid(rows, cols);
     const uint8_t *Au = (const uint8_t *)A;
     const int nv = (int)g;
     // nontemporal loads by the rule of the single calls: once the matrix cannot live in the 256 MiB Infinity Cache
     const bool nt = F::matrix_bytes(rows, cols) > (256ull << 20), fused = v.qu != nullptr, st_ = dr.rng != nullptr;
     switch (4 * nt + 2 * fused + st_) {
-    case 7: F::template launch<NV, true, true, true>(grid, st, Au, sA, cols, nv, arg, fuse, rs); break;
-    case 6: F::template launch<NV, true, true, false>(grid, st, Au, sA, cols, nv, arg, fuse, rs); break;
-    case 5: F::template launch<NV, true, false, true>(grid, st, Au, sA, cols, nv, arg, fuse, rs); break;
-    case 4: F::template launch<NV, true, false, false>(grid, st, Au, sA, cols, nv, arg, fuse, rs); break;
-    case 3: F::template launch<NV, false, true, true>(grid, st, Au, sA, cols, nv, arg, fuse, rs); break;
-    case 2: F::template launch<NV, false, true, false>(grid, st, Au, sA, cols, nv, arg, fuse, rs); break;
-    case 1: F::template launch<NV, false, false, true>(grid, st, Au, sA, cols, nv, arg, fuse, rs); break;
-    default: F::template launch<NV, false, false, false>(grid, st, Au, sA, cols, nv, arg, fuse, rs); break;
+    case 7: F::template launch<NV, true, true, true>(grid, st, Au, sA, rows, cols, nv, arg, fuse, rs); break;
+    case 6: F::template launch<NV, true, true, false>(grid, st, Au, sA, rows, cols, nv, arg, fuse, rs); break;
+    case 5: F::template launch<NV, true, false, true>(grid, st, Au, sA, rows, cols, nv, arg, fuse, rs); break;
+    case 4: F::template launch<NV, true, false, false>(grid, st, Au, sA, rows, cols, nv, arg, fuse, rs); break;
+    case 3: F::template launch<NV, false, true, true>(grid, st, Au, sA, rows, cols, nv, arg, fuse, rs); break;
+    case 2: F::template launch<NV, false, true, false>(grid, st, Au, sA, rows, cols, nv, arg, fuse, rs); break;
+    case 1: F::template launch<NV, false, false, true>(grid, st, Au, sA, rows, cols, nv, arg, fuse, rs); break;
+    default: F::template launch<NV, false, false, false>(grid, st, Au, sA, rows, cols, nv, arg, fuse, rs); break;
     }
     CLV_LAUNCH_CHECK();
     clv_internal_mvm_batch_count();
@@ -127,17 +143,17 @@ static int mvm_batch_launch_group(const int8_t *A, const float *sA, uint64_t row
 }
 
 // The checked arguments of the family's mvm batch call (qu == NULL) / fused batch call on the stream, group by group.  With an rng every
-// group starts at the state the group before it left: a batched group's windows lie 2 G (fused: 4 G) draws apart from position 0 and its
+// group starts at the state the group before it left (G = output blocks): a batched group's windows lie 2 G (fused: 4 G) draws apart from position 0 and its
 // launch commits all of them, a forwarded group's single calls advance the state themselves -- so the two kinds mix freely.
 template <class F>
 static int mvm_batch_run(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const MvmBatchVectors &v, uint64_t *rng,
                          void *stream)
 {
-    const uint64_t per_vector = (v.qu ? 4ull : 2ull) * (rows / 64);
+    const uint64_t per_vector = (v.qu ? 4ull : 2ull) * (F::r_len(rows, cols) / 64);
     for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
         const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
         int rc = CLV_OK;
-        if (!mvm_batch_selected(g, rng != nullptr)) {
+        if (!mvm_batch_selected<F>(g, rows, cols, v.qu != nullptr, rng != nullptr)) {
             for (uint64_t j = j0; j < j0 + g && !rc; j++)
                 rc = v.qu ? F::scale_and_add(A, sA, rows, cols, v.x[j], v.sx[j], v.qu[j], v.su[j], v.a, v.r ? v.r[j] : nullptr,
                                              v.r ? v.sr[j] : nullptr, v.r2[j], v.sr2[j], rng, stream)
@@ -167,7 +183,8 @@ static int mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_
     return CLV_OK;
 }
 
-// the positions of a *_mvm_batch_at call with a generator: everything below 2^55, the exponents the jump-ahead has table levels for
+// the positions of a *_mvm_batch_at call with a generator: everything below 2^55, the exponents the jump-ahead has table levels for.
+// rows = the elements of a result (the transposed family passes its columns)
 static inline int mvm_batch_check_draws(const char *fn, uint64_t rows, uint64_t nvec, uint64_t draw_base, uint64_t draw_stride, uint64_t commit_draws)
 {
     CLV_REQUIRE(commit_draws < (1ull << (RNG_POW_LEVELS - 1)), "%s: commit_draws=%llu must stay below 2^55", fn, (unsigned long long)commit_draws);
@@ -199,25 +216,25 @@ static int mvm_batch_check_args(const char *fn, const int8_t *A, const float *sA
                         "%s: the result of vector %llu must not alias the vector being multiplied", fn, (unsigned long long)j);
     std::vector<ClvRange> rg;
     rg.reserve(8 * nvec + 2);
-    const uint64_t sc = sizeof(float), xb = F::vector_bytes(cols), rb = F::vector_bytes(rows);
+    const uint64_t sc = sizeof(float), xl = F::x_len(rows, cols), rl = F::r_len(rows, cols), xb = F::vector_bytes(xl), rb = F::vector_bytes(rl);
     rg.push_back(clv_range(A, F::matrix_bytes(rows, cols), false, ~0ull, "A"));
     rg.push_back(clv_range(sA, (rows / 64) * (cols / 64) * sc, false, ~0ull, "sA"));
     for (uint64_t j = 0; j < nvec; j++) {
         rg.push_back(clv_range(x[j], xb, false, j, "x"));
-        rg.push_back(clv_range(sx[j], cols / 64 * sc, false, j, "sx"));
+        rg.push_back(clv_range(sx[j], xl / 64 * sc, false, j, "sx"));
         rg.push_back(clv_range(r[j], rb, true, j, "r"));
-        rg.push_back(clv_range(sr[j], rows / 64 * sc, true, j, "sr"));
+        rg.push_back(clv_range(sr[j], rl / 64 * sc, true, j, "sr"));
         if (fused) {
-            // the in-place form r[j] == qu[j], sr[j] == su[j]: the result IS the input, only workgroup rb touches block rb of either
+            // the in-place form r[j] == qu[j], sr[j] == su[j]: the result IS the input, only the workgroup that owns a block touches it in either
             const bool in_place = (const void *)r[j] == (const void *)qu[j] && (const void *)sr[j] == (const void *)su[j];
             if (!in_place) {
                 rg.push_back(clv_range(qu[j], rb, false, j, "qu"));
-                rg.push_back(clv_range(su[j], rows / 64 * sc, false, j, "su"));
+                rg.push_back(clv_range(su[j], rl / 64 * sc, false, j, "su"));
             }
         }
         if (t) {
             rg.push_back(clv_range(t[j], rb, true, j, "t"));
-            rg.push_back(clv_range(st_[j], rows / 64 * sc, true, j, "st"));
+            rg.push_back(clv_range(st_[j], rl / 64 * sc, true, j, "st"));
         }
     }
     return clv_internal_check_ranges(fn, rg);
@@ -225,14 +242,16 @@ static int mvm_batch_check_args(const char *fn, const int8_t *A, const float *sA
 
 // Q_IHT / Q_GD for nvec signals with one Phi: the loop of the family's single call F::iht with every step batched.  Arrays are HOST arrays
 // of nvec device pointers.  Bit-identical to F::iht per vector (where that takes a persistent kernel: it equals the launch-per-step loop
-// bit for bit).
-template <class F>
+// bit for bit).  FT = the family that takes step 2, t3 = Phi' t2: F itself on the held PhiT, or the transposed family on Phi's own bytes
+// (PhiT / sPhiT are then NULL and unused, the single call is FT::iht_one_matrix, which never takes a persistent kernel).
+template <class F, class FT = F>
 static int mvm_batch_iht(const char *fn, const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n,
                          uint64_t nvec, int8_t *const *x, float *const *sx, uint64_t x_len, const int8_t *const *y, const float *const *sy,
                          int8_t *const *t1, float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
                          uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng, void *stream)
 {
-    CLV_REQUIRE(Phi && sPhi && PhiT && sPhiT, "%s: null pointer", fn);
+    constexpr bool one_matrix = !std::is_same<F, FT>::value;
+    CLV_REQUIRE(Phi && sPhi && (one_matrix || (PhiT && sPhiT)), "%s: null pointer", fn);
     CLV_REQUIRE(m % 128 == 0 && n % 128 == 0 && x_len <= n, "%s: m=%llu n=%llu x_len=%llu", fn, (unsigned long long)m, (unsigned long long)n,
                 (unsigned long long)x_len);
     CLV_REQUIRE(m / 64 <= 0x7FFFFFFFull && n / 64 <= 0x7FFFFFFFull, "%s: too many rows", fn);
@@ -247,8 +266,10 @@ static int mvm_batch_iht(const char *fn, const int8_t *Phi, const float *sPhi, c
         const uint64_t sc = sizeof(float), tiles = (m / 64) * (n / 64), mb = F::vector_bytes(m), nb = F::vector_bytes(n);
         rg.push_back(clv_range(Phi, F::matrix_bytes(m, n), false, ~0ull, "Phi"));
         rg.push_back(clv_range(sPhi, tiles * sc, false, ~0ull, "sPhi"));
-        rg.push_back(clv_range(PhiT, F::matrix_bytes(m, n), false, ~0ull, "PhiT"));
-        rg.push_back(clv_range(sPhiT, tiles * sc, false, ~0ull, "sPhiT"));
+        if (!one_matrix) {
+            rg.push_back(clv_range(PhiT, F::matrix_bytes(m, n), false, ~0ull, "PhiT"));
+            rg.push_back(clv_range(sPhiT, tiles * sc, false, ~0ull, "sPhiT"));
+        }
         for (uint64_t j = 0; j < nvec; j++) {
             rg.push_back(clv_range(y[j], mb, false, j, "y"));
             rg.push_back(clv_range(sy[j], m / 64 * sc, false, j, "sy"));
@@ -274,11 +295,16 @@ static int mvm_batch_iht(const char *fn, const int8_t *Phi, const float *sPhi, c
     const int mode = threshold == 2 ? CLV_THRESHOLD_REFERENCE : CLV_THRESHOLD_FAST;
     for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
         const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        bool batched = g >= 2 && m && n && force != 0 && (force == 1 || !F::iht_prefers_single(m, n, iterations, threshold, rng != nullptr, g));
+        bool batched = g >= 2 && m && n && force != 0 && (force == 1 || !FT::iht_prefers_single(m, n, iterations, threshold, rng != nullptr, g));
         if (rng && g * P && iterations > ((1ull << 55) - 1) / (g * P)) batched = false;      // positions beyond the jump-ahead tables
         if (!batched) {
             for (uint64_t j = j0; j < j0 + g; j++) {
-                int rc = F::iht(Phi, sPhi, PhiT, sPhiT, m, n, x[j], sx[j], x_len, y[j], sy[j], t1[j], st1[j], t2[j], st2[j], t3[j], st3[j], iterations, K,
+                int rc;
+                if constexpr (one_matrix)
+                    rc = FT::iht_one_matrix(Phi, sPhi, m, n, x[j], sx[j], x_len, y[j], sy[j], t1[j], st1[j], t2[j], st2[j], t3[j], st3[j], iterations, K, mu,
+                                            threshold, rng, stream);
+                else
+                    rc = F::iht(Phi, sPhi, PhiT, sPhiT, m, n, x[j], sx[j], x_len, y[j], sy[j], t1[j], st1[j], t2[j], st2[j], t3[j], st3[j], iterations, K,
                                 mu, threshold, rng, stream);
                 if (rc) return rc;
             }
@@ -295,7 +321,9 @@ static int mvm_batch_iht(const char *fn, const int8_t *Phi, const float *sPhi, c
             // t1 = Phi * x, t2 = y - t1;  t3 = Phi' * t2, x += mu * t3;  keep the K largest: three launches for the group
             const uint64_t commit = it + 1 == iterations ? g * stride : 0;
             int rc = mvm_batch_at<F>(Phi, sPhi, m, n, g, step1, rng, it * P, stride, 0, stream);
-            if (!rc) rc = mvm_batch_at<F>(PhiT, sPhiT, n, m, g, step2, rng, it * P + 4 * (m / 64), stride, commit, stream);
+            if (!rc)
+                rc = one_matrix ? mvm_batch_at<FT>(Phi, sPhi, m, n, g, step2, rng, it * P + 4 * (m / 64), stride, commit, stream)
+                                : mvm_batch_at<F>(PhiT, sPhiT, n, m, g, step2, rng, it * P + 4 * (m / 64), stride, commit, stream);
             if (!rc && threshold) rc = F::threshold_batch(x + j0, sx + j0, g, x_len, n, K, mode, stream);
             if (rc) return rc;
         }

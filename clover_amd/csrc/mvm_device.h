@@ -94,3 +94,21 @@ struct MvmFuse {
     float *sr2;
 };
 
+// the vectors of one batched pass (k_m4_mvm_batch, k_m4_mvm_t_batch), BY VALUE in the kernel arguments: no pointer table in device memory,
+// nothing to allocate, captures into a graph.  Slots >= nv are absent: NULL, never dereferenced.
+template <int NV>
+struct MvmBatchArgs {
+    const uint8_t *x[NV];
+    const float *sx[NV];
+    uint32_t *r[NV];         // all NULL: the mvm result is not stored (FUSE only)
+    float *sr[NV];
+};
+template <int NV>
+struct MvmBatchFuse {        // see MvmFuse
+    const uint32_t *qu[NV];
+    const float *su[NV];
+    uint32_t *r2[NV];        // may be qu (in place)
+    float *sr2[NV];
+    float a;
+};
+

@@ -189,6 +189,16 @@ SIGNATURES_FP32 = {
     "clm_f32_iht": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
 }
 
+# name -> (restype, argtypes); everything include/clover_hip_batch_t.h declares (the batched transposed 4-bit mvm, the one-matrix batched
+# IHT / GD loop): the signatures of the clm4_*_batch family, clm4_iht_batch_one_matrix without the PhiT / sPhiT pair
+SIGNATURES_BATCH_T = {
+    "clm4_mvm_transposed_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm4_mvm_transposed_batch_at": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp]),
+    "clm4_mvm_transposed_scale_and_add_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm4_iht_batch_one_matrix": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
+                                           C.c_float, C.c_int, _vp, _vp]),
+}
+
 
 class CloverHipError(RuntimeError):
     pass
@@ -203,7 +213,7 @@ def load_library(path: str | Path | None = None, allow_probe: bool = False) -> C
             f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = C.CDLL(str(p))
-    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -419,9 +429,9 @@ class CloverHip:
 
     def m4_iht_batch(self, qPhi, sPhi, qPhiT, sPhiT, m, n, ys, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
                      rng: DevBuf | None = None, prefill: int = 0x55):
-        """clm4_iht_batch on buffers prefilled with `prefill` bytes; ys: list of (qy, sy); returns per vector
-        {"x": (q, s), "t1": ..., "t2": ..., "t3": ...}"""
-        b = [self.to_device(v) for v in (qPhi, sPhi, qPhiT, sPhiT)]
+        """clm4_iht_batch on buffers prefilled with `prefill` bytes -- or, with qPhiT None, clm4_iht_batch_one_matrix; ys: list of (qy, sy);
+        returns per vector {"x": (q, s), "t1": ..., "t2": ..., "t3": ...}"""
+        b = [self.to_device(v) for v in ((qPhi, sPhi) if qPhiT is None else (qPhi, sPhi, qPhiT, sPhiT))]
         dy = [(self.to_device(q), self.to_device(s)) for q, s in ys]
         lens = {"x": n, "t1": m, "t2": m, "t3": n}
         v = {name: [(self.alloc(ln // 2), self.alloc(ln // 16)) for _ in ys] for name, ln in lens.items()}
@@ -431,9 +441,13 @@ class CloverHip:
                     self.check(self.lib.clv_memset(d.ptr, prefill, d.nbytes, None))
         pa = self.ptr_array
         arr = {name: (pa([d[0] for d in bufs]), pa([d[1] for d in bufs])) for name, bufs in v.items()}
-        self.check(self.lib.clm4_iht_batch(b[0].ptr, b[1].ptr, b[2].ptr, b[3].ptr, m, n, len(ys), arr["x"][0], arr["x"][1], n if x_len is None else x_len,
-                                           pa([d[0] for d in dy]), pa([d[1] for d in dy]), arr["t1"][0], arr["t1"][1], arr["t2"][0], arr["t2"][1],
-                                           arr["t3"][0], arr["t3"][1], iterations, K, mu, threshold, rng.ptr if rng else None, None))
+        tail = (m, n, len(ys), arr["x"][0], arr["x"][1], n if x_len is None else x_len, pa([d[0] for d in dy]), pa([d[1] for d in dy]),
+                arr["t1"][0], arr["t1"][1], arr["t2"][0], arr["t2"][1], arr["t3"][0], arr["t3"][1], iterations, K, mu, threshold,
+                rng.ptr if rng else None, None)
+        if qPhiT is None:
+            self.check(self.lib.clm4_iht_batch_one_matrix(b[0].ptr, b[1].ptr, *tail))
+        else:
+            self.check(self.lib.clm4_iht_batch(b[0].ptr, b[1].ptr, b[2].ptr, b[3].ptr, *tail))
         return [{name: (v[name][j][0].download(np.uint8, ln // 2), v[name][j][1].download(np.float32, ln // 64)) for name, ln in lens.items()}
                 for j in range(len(ys))]
 
@@ -513,6 +527,51 @@ class CloverHip:
                                                               rng.ptr if rng else None, None))
         t = (dt.download(np.uint8, cols // 2), dst.download(np.float32, cols // 64)) if want_t else (None, None)
         return t[0], t[1], dr.download(np.uint8, cols // 2), dsr.download(np.float32, cols // 64)
+
+    def m4_mvm_transposed_batch(self, qA, sA, rows, cols, xs, rng: DevBuf | None = None, at=None):
+        """xs: list of (qx, sx) of `rows` elements; returns the list of (r, sr), `cols` elements each, of clm4_mvm_transposed_batch -- or,
+        with at = (draw_base, draw_stride, commit_draws), of clm4_mvm_transposed_batch_at.  qA may be a DevBuf (a matrix uploaded once);
+        an x that is the same object twice is uploaded once (a repeated input pointer)"""
+        dA, dsA = (qA, sA) if isinstance(qA, DevBuf) else (self.to_device(qA), self.to_device(sA))
+        dx = self._upload_pairs(xs)
+        dr = [(self.alloc(max(cols // 2, 1)), self.alloc(max(cols // 16, 4))) for _ in xs]
+        pa = self.ptr_array
+        args = (dA.ptr, dsA.ptr, rows, cols, len(xs), pa([d[0] for d in dx]), pa([d[1] for d in dx]), pa([d[0] for d in dr]), pa([d[1] for d in dr]),
+                rng.ptr if rng else None)
+        if at is None:
+            self.check(self.lib.clm4_mvm_transposed_batch(*args, None))
+        else:
+            self.check(self.lib.clm4_mvm_transposed_batch_at(*args, *at, None))
+        return [(r.download(np.uint8, cols // 2), sr.download(np.float32, cols // 64)) for r, sr in dr]
+
+    def m4_mvm_transposed_scale_and_add_batch(self, qA, sA, rows, cols, xs, us, a: float, rng: DevBuf | None = None, in_place: bool = False,
+                                              want_t: bool = True):
+        """xs: list of (q, s) of `rows` elements, us: of `cols`; returns the list of (t, st, r, sr) of
+        clm4_mvm_transposed_scale_and_add_batch; t/st are None when want_t is False"""
+        dA, dsA = (qA, sA) if isinstance(qA, DevBuf) else (self.to_device(qA), self.to_device(sA))
+        dx = self._upload_pairs(xs)
+        du = [(self.to_device(q), self.to_device(s)) for q, s in us]
+        dt = [(self.alloc(cols // 2), self.alloc(cols // 16)) for _ in xs] if want_t else None
+        dr = du if in_place else [(self.alloc(cols // 2), self.alloc(cols // 16)) for _ in xs]
+        pa = self.ptr_array
+        self.check(self.lib.clm4_mvm_transposed_scale_and_add_batch(
+            dA.ptr, dsA.ptr, rows, cols, len(xs), pa([d[0] for d in dx]), pa([d[1] for d in dx]), pa([d[0] for d in du]), pa([d[1] for d in du]), a,
+            pa([d[0] for d in dt]) if dt else None, pa([d[1] for d in dt]) if dt else None, pa([d[0] for d in dr]), pa([d[1] for d in dr]),
+            rng.ptr if rng else None, None))
+        out = []
+        for j in range(len(xs)):
+            t = (dt[j][0].download(np.uint8, cols // 2), dt[j][1].download(np.float32, cols // 64)) if want_t else (None, None)
+            out.append((t[0], t[1], dr[j][0].download(np.uint8, cols // 2), dr[j][1].download(np.float32, cols // 64)))
+        return out
+
+    def _upload_pairs(self, pairs):
+        """device copies of a list of (q, s); a pair whose q is the same object as an earlier one shares that pair's buffers"""
+        seen, out = {}, []
+        for q, s in pairs:
+            if id(q) not in seen:
+                seen[id(q)] = (self.to_device(q), self.to_device(s))
+            out.append(seen[id(q)])
+        return out
 
     def m4_iht(self, qPhi, sPhi, qPhiT, sPhiT, m, n, qy, sy, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
                rng: DevBuf | None = None, prefill: int = 0x55):

@@ -164,6 +164,52 @@ inline void Q_GD_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 *c
 }
 
 
+/* Not in the reference: Q_IHT_batch / Q_GD_batch with ONE matrix -- the gradient step of every group takes Phi' t2[j] straight from Phi
+ * (CloverMatrix4::mvm_transposed_batch_at -> clm4_mvm_transposed_batch_at, clover_hip_batch_t.h), so no PhiT is built or held.  x[j],
+ * t1[j], t2[j], t3[j] end as Q_IHT_one_matrix(Phi, *x[j], *y[j], ...) called for signal 0, then 1, ... leaves them, bit for bit, and so does
+ * Phi's generator.  Rounding disabled: CloverMatrix4::iht_loop_batch_one_matrix -> clm4_iht_batch_one_matrix.  Stochastic: BOTH products
+ * draw from Phi's generator, as in Q_IHT_one_matrix: with dm = 2 (m / 64) and dn = 2 (n / 64) signal j's iteration `it` has its Phi window
+ * at (j * iterations + it) * (dm + dn) and its Phi' window dm further on; the last iteration advances the generator by everything. */
+namespace clover_hip {
+inline void q_iht_batch_one_matrix_stochastic(CloverMatrix4 &Phi, CloverVector4 *const *x, CloverVector4 *const *y, CloverVector4 *const *t1,
+                                              CloverVector4 *const *t2, CloverVector4 *const *t3, const uint64_t count, const uint64_t iterations,
+                                              const uint64_t K, const float mu, const bool with_threshold)
+{
+    for (uint64_t j = 0; j < count; j++) x[j]->clear();
+    const uint64_t dm = 2 * (Phi.getRows() >> 6), dn = 2 * (Phi.getCols() >> 6), P = dm + dn;
+    for (uint64_t it = 0; it < iterations; it++) {
+        const bool last = it + 1 == iterations;
+        Phi.mvm_batch_at(x, t1, count, it * P, iterations * P, 0);
+        for (uint64_t j = 0; j < count; j++) y[j]->scaleAndAdd_parallel(*t1[j], -1.0f, *t2[j]);
+        Phi.mvm_transposed_batch_at(t2, t3, count, it * P + dm, iterations * P, last ? count * iterations * P : 0);
+        for (uint64_t j = 0; j < count; j++) x[j]->scaleAndAdd_parallel(*t3[j], mu);
+        if (with_threshold) CloverVector4::threshold_batch(x, count, K);
+    }
+}
+}
+
+inline void Q_IHT_batch_one_matrix(CloverMatrix4 &Phi, CloverVector4 *const *x, CloverVector4 *const *y, CloverVector4 *const *t1,
+                                   CloverVector4 *const *t2, CloverVector4 *const *t3, const uint64_t count, const uint64_t iterations,
+                                   const uint64_t K, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch_one_matrix(x, y, t1, t2, t3, count, iterations, K, mu, true);
+#else
+    clover_hip::q_iht_batch_one_matrix_stochastic(Phi, x, y, t1, t2, t3, count, iterations, K, mu, true);
+#endif
+}
+
+inline void Q_GD_batch_one_matrix(CloverMatrix4 &Phi, CloverVector4 *const *x, CloverVector4 *const *y, CloverVector4 *const *t1,
+                                  CloverVector4 *const *t2, CloverVector4 *const *t3, const uint64_t count, const uint64_t iterations, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch_one_matrix(x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#else
+    clover_hip::q_iht_batch_one_matrix_stochastic(Phi, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#endif
+}
+
+
 /* CloverMatrix4 with CloverVector8 vectors: the configuration the reference measures and publishes as the 4-bit IHT / GD
  * (test/performance/02_bit04.cpp:140; "the 4-bit version uses the mixed precision MVM", doc/results/performance.txt:597-606) */
 inline void Q_IHT(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector8 &x, CloverVector8 &y, CloverVector8 &t1, CloverVector8 &t2,

@@ -31,6 +31,7 @@
 #include "CloverMatrix8.h"          /* the 8-bit operand of gemm(); CloverMatrix8.h does not include this header */
 #include "CloverVector4.h"
 #include "CloverVector8.h"
+#include "clover_hip_batch_t.h"   /* the batched transposed calls: a header of their own beside clover_hip.h */
 
 class CloverMatrix4 {
 protected:
@@ -559,6 +560,157 @@ public:
         x.commit();
         if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
     }
+    /* Not in the reference: this' * x[j] for `count` vectors in ONE pass over this matrix's own bytes per group of CLM4_MVM_BATCH_MAX
+     * (clm4_mvm_transposed_batch, clover_hip_batch_t.h); r[j] equals what mvm_transposed(*x[j], *r[j]) gives, bit for bit.  The x[j] may
+     * repeat; the r[j] are distinct vectors, none of them an x.  With stochastic rounding enabled the vectors draw from the matrix's
+     * generator one after another, as the single calls in order do, and the generator ends where those calls leave it. */
+    void mvm_transposed_batch(const CloverVector4 *const *x, CloverVector4 *const *r, uint64_t count)
+    {
+        mvm_transposed_batch_at_impl(x, r, count, 0, 0, 0, false);
+    }
+    /* mvm_transposed_batch with the place of every vector's draws chosen by the caller (clm4_mvm_transposed_batch_at), counted in draws --
+     * mvm_transposed consumes 2 (cols / 64) -- from where the matrix's generator stands: vector j draws from draw_base + j * draw_stride on,
+     * and the generator is advanced by commit_draws afterwards (0: left as it is).  For callers whose stream order is not vector after
+     * vector (Q_IHT_batch_one_matrix, CloverIHT.h).  With rounding disabled the three numbers are ignored. */
+    void mvm_transposed_batch_at(const CloverVector4 *const *x, CloverVector4 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
+                                 uint64_t commit_draws)
+    {
+        mvm_transposed_batch_at_impl(x, r, count, draw_base, draw_stride, commit_draws, true);
+    }
+    /* mvm_transposed_scaleAndAdd for `count` vectors: t[j] = this' * x[j], r[j] = quantize(u[j] + a * t[j]).  Rounding disabled: one launch
+     * per group (clm4_mvm_transposed_scale_and_add_batch).  Stochastic: one mvm_transposed_batch and the scaleAndAdd calls, which draw from
+     * their u[j]'s own generators -- the bits of the loop of mvm_transposed_scaleAndAdd. */
+    void mvm_transposed_scaleAndAdd_batch(const CloverVector4 *const *x, const CloverVector4 *const *u, float a, CloverVector4 *const *t,
+                                          CloverVector4 *const *r, uint64_t count)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        std::vector<const int8_t *> px(count), pu(count);
+        std::vector<const float *> psx(count), psu(count);
+        std::vector<int8_t *> pt(count), pr(count);
+        std::vector<float *> pst(count), psr(count);
+        for (uint64_t j = 0; j < count; j++) {
+            check_fused_transposed(*x[j], *u[j], *t[j]);
+            if (r[j]->size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+            px[j] = x[j]->dev_values_ro();
+            psx[j] = x[j]->dev_scales_ro();
+            pu[j] = u[j]->dev_values_ro();
+            psu[j] = u[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) {
+            pt[j] = t[j]->dev_values_wo();
+            pst[j] = t[j]->dev_scales_wo();
+            pr[j] = r[j]->dev_values_wo();
+            psr[j] = r[j]->dev_scales_wo();
+        }
+        clover_hip::check(clm4_mvm_transposed_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(),
+                                                                  psu.data(), a, pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
+                          "CloverMatrix4::mvm_transposed_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
+#else
+        for (uint64_t j = 0; j < count; j++) check_fused_transposed(*x[j], *u[j], *t[j]);
+        mvm_transposed_batch(x, t, count);
+        for (uint64_t j = 0; j < count; j++) const_cast<CloverVector4 *>(u[j])->scaleAndAdd(*t[j], a, *r[j]);
+#endif
+    }
+    /* in place: u[j] = quantize(u[j] + a * (this' * x[j])) */
+    void mvm_transposed_scaleAndAdd_batch(const CloverVector4 *const *x, CloverVector4 *const *u, float a, CloverVector4 *const *t, uint64_t count)
+    {
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        std::vector<const int8_t *> px(count), pu(count);
+        std::vector<const float *> psx(count), psu(count);
+        std::vector<int8_t *> pt(count), pr(count);
+        std::vector<float *> pst(count), psr(count);
+        for (uint64_t j = 0; j < count; j++) {
+            check_fused_transposed(*x[j], *u[j], *t[j]);
+            px[j] = x[j]->dev_values_ro();
+            psx[j] = x[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) {
+            pu[j] = pr[j] = u[j]->dev_values_rw();
+            psu[j] = psr[j] = u[j]->dev_scales_rw();
+            pt[j] = t[j]->dev_values_wo();
+            pst[j] = t[j]->dev_scales_wo();
+        }
+        clover_hip::check(clm4_mvm_transposed_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(),
+                                                                  psu.data(), a, pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
+                          "CloverMatrix4::mvm_transposed_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
+#else
+        for (uint64_t j = 0; j < count; j++) check_fused_transposed(*x[j], *u[j], *t[j]);
+        mvm_transposed_batch(x, t, count);
+        for (uint64_t j = 0; j < count; j++) u[j]->scaleAndAdd(*t[j], a);
+#endif
+    }
+    /* iht_loop_one_matrix for `count` signals with this matrix as Phi and no PhiT (clm4_iht_batch_one_matrix): per iteration every step
+     * runs once for a group of signals, t3 = Phi' t2 from this matrix's own bytes; x[j], t1[j], t2[j], t3[j] end as
+     * iht_loop_one_matrix(*x[j], *y[j], ...) leaves them.  Deterministic rounding only, as iht_loop_one_matrix. */
+    void iht_loop_batch_one_matrix(CloverVector4 *const *x, const CloverVector4 *const *y, CloverVector4 *const *t1, CloverVector4 *const *t2,
+                                   CloverVector4 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    {
+        std::vector<const int8_t *> py(count);
+        std::vector<const float *> psy(count);
+        std::vector<int8_t *> px(count), p1(count), p2(count), p3(count);
+        std::vector<float *> psx(count), ps1(count), ps2(count), ps3(count);
+        for (uint64_t j = 0; j < count; j++) {
+            if (x[j]->size_pad() != getCols() || y[j]->size_pad() != getRows() || t1[j]->size_pad() != getRows() || t2[j]->size_pad() != getRows() ||
+                t3[j]->size_pad() != getCols() || x[j]->size() != x[0]->size()) {
+                std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+                exit(1);
+            }
+            py[j] = y[j]->dev_values_ro();
+            psy[j] = y[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) {
+            px[j] = x[j]->dev_values_wo();
+            psx[j] = x[j]->dev_scales_wo();
+            p1[j] = t1[j]->dev_values_wo();
+            ps1[j] = t1[j]->dev_scales_wo();
+            p2[j] = t2[j]->dev_values_wo();
+            ps2[j] = t2[j]->dev_scales_wo();
+            p3[j] = t3[j]->dev_values_wo();
+            ps3[j] = t3[j]->dev_scales_wo();
+        }
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm4_iht_batch_one_matrix(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), count ? x[0]->size() : 0,
+                                                    py.data(), psy.data(), p1.data(), ps1.data(), p2.data(), ps2.data(), p3.data(), ps3.data(),
+                                                    iterations, K, mu, thr, nullptr, nullptr),
+                          "CloverMatrix4::iht_loop_batch_one_matrix");
+        for (uint64_t j = 0; j < count; j++) {
+            x[j]->commit();
+            if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }
+        }
+    }
+
+private:
+    void mvm_transposed_batch_at_impl(const CloverVector4 *const *x, CloverVector4 *const *r, uint64_t count, uint64_t draw_base,
+                                      uint64_t draw_stride, uint64_t commit_draws, bool positioned)
+    {
+        std::vector<const int8_t *> px(count);
+        std::vector<const float *> psx(count);
+        std::vector<int8_t *> pr(count);
+        std::vector<float *> psr(count);
+        for (uint64_t j = 0; j < count; j++) {
+            if (x[j]->size() != getRows() || r[j]->size_pad() != getCols()) {
+                std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+                exit(1);
+            }
+            px[j] = x[j]->dev_values_ro();
+            psx[j] = x[j]->dev_scales_ro();
+        }
+        for (uint64_t j = 0; j < count; j++) { pr[j] = r[j]->dev_values_wo(); psr[j] = r[j]->dev_scales_wo(); }
+        uint64_t *rng = clover_hip::rng_or_null(random);
+        if (positioned)
+            clover_hip::check(clm4_mvm_transposed_batch_at(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(),
+                                                           rng, draw_base, draw_stride, commit_draws, nullptr),
+                              "CloverMatrix4::mvm_transposed_batch_at");
+        else      /* the launcher may forward groups to the single calls where those were measured faster */
+            clover_hip::check(clm4_mvm_transposed_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng,
+                                                        nullptr),
+                              "CloverMatrix4::mvm_transposed_batch");
+        for (uint64_t j = 0; j < count; j++) r[j]->commit();
+    }
+
+public:
     /* in place: u = quantize(u + a * (this * x)) */
     void mvm_scaleAndAdd(const CloverVector4 &x, CloverVector4 &u, float a, CloverVector4 &t)
     {
