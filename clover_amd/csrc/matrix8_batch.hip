@@ -7,6 +7,9 @@
 // the re-quantisation and the scaleAndAdd behind it are mvm8_requantize_wave (mvm8_device.h), the same arithmetic as k_m8_mvm_saa's.
 #include "mvm_batch_host.h"
 #include "mvm8_device.h"
+#include "matrix8_t_batch.h"
+
+#include "clover_hip_batch_t8.h"
 
 // Columns of x staged in LDS per pass: 4 KiB of int8 + 256 B of block factors + 256 B of row dots per vector, 36 KiB at NV = 8 (36.5 KiB
 // with the generator starts of the fused stochastic form): four workgroups per CU, the budget of mvm_batch8.hip.
@@ -17,22 +20,8 @@
 // the size rules of clm8_mvm (matrix8.hip)
 int clv_internal_m8_check_mvm(const char *fn, const void *A, const void *sA, uint64_t rows, uint64_t cols, const void *x, const void *r);
 
-// the vectors of one pass, BY VALUE in the kernel arguments (see MvmBatchArgs, mvm_batch4.hip).  Slots >= nv are absent: NULL, never dereferenced.
-template <int NV>
-struct M8BatchArgs {
-    const int8_t *x[NV];
-    const float *sx[NV];
-    int8_t *r[NV];           // all NULL: the mvm result is not stored (FUSE only)
-    float *sr[NV];
-};
-template <int NV>
-struct M8BatchFuse {         // see M8Fuse
-    const int8_t *qu[NV];
-    const float *su[NV];
-    int8_t *r2[NV];          // may be qu (in place)
-    float *sr2[NV];
-    float a;
-};
+// M8BatchArgs / M8BatchFuse (the vectors of one pass, by value in the kernel arguments): mvm8_device.h, shared with the transposed batched
+// kernel (matrix8_t_batch.hip)
 
 #define M8B_X_BYTES(NV) ((NV) * (M8B_CHUNK + (M8B_CHUNK / 64) * sizeof(float) + 64 * sizeof(float)))
 // ST: behind the row dots, per vector and window the start of each of the 4 generator lanes (32 B): 512 B at NV = 8 fused
@@ -248,4 +237,15 @@ extern "C" int clm8_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t
 {
     return mvm_batch_iht<M8Batch>("clm8_iht_batch", Phi, sPhi, PhiT, sPhiT, m, n, nvec, x, sx, x_len, y, sy, t1, st1, t2, st2, t3, st3, iterations, K, mu,
                                   threshold, rng_state_dev, stream);
+}
+
+// The same loop with ONE matrix (include/clover_hip_batch_t8.h): step 1 is this family's fused launch on Phi, step 2 the transposed
+// family's (matrix8_t_batch.hip) on the same bytes; the draws lie where the two-matrix loop has them.
+extern "C" int clm8_iht_batch_one_matrix(const int8_t *Phi, const float *sPhi, uint64_t m, uint64_t n, uint64_t nvec, int8_t *const *x,
+                                         float *const *sx, uint64_t x_len, const int8_t *const *y, const float *const *sy, int8_t *const *t1,
+                                         float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
+                                         uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream)
+{
+    return mvm_batch_iht<M8Batch, M8TBatch>("clm8_iht_batch_one_matrix", Phi, sPhi, nullptr, nullptr, m, n, nvec, x, sx, x_len, y, sy, t1, st1, t2,
+                                            st2, t3, st3, iterations, K, mu, threshold, rng_state_dev, stream);
 }

@@ -25,7 +25,7 @@
 // Stochastic rounding: output block cb takes the draws clm8_mvm gives row group cb of a stored A': 2 cb, 2 cb + 1 and, fused,
 // 2 G + 2 cb, 2 G + 2 cb + 1 (G = cols / 64); the state is left advanced by 2 G (4 G).  The four waves are the four generator lanes.
 #include "rng_device.h"
-#include "mvm8_device.h"
+#include "matrix8_t_device.h"      // m8t_transpose4x4, m8t_load, m8t_link: shared with k_m8_mvm_t_batch (matrix8_t_batch.hip)
 
 #define M8T_CHUNK 16384u    // rows staged in LDS per pass
 #define M8T_STEP 64u        // rows per block: every thread takes part in every block
@@ -34,17 +34,6 @@
 
 static_assert(M8T_W == 2, "the lane map (32 column quads x 8 chains) assumes 128 columns: cols % 128 == 0 makes every workgroup whole");
 static_assert(M8T_CHUNK % (64 * 256) == 0 && (M8T_CHUNK / M8T_STEP) % (2 * M8T_U) == 0, "a chunk is whole pairs of load groups and whole rounds of 256 staging threads");
-
-// 4 x 4 bytes: d[i] = row i, byte k = column k  ->  c[k] = column k, byte i = row i
-__device__ __forceinline__ void m8t_transpose4x4(const uint32_t *d, uint32_t (&c)[4])
-{
-    const uint32_t l01 = __builtin_amdgcn_perm(d[1], d[0], 0x05010400u), h01 = __builtin_amdgcn_perm(d[1], d[0], 0x07030602u);   // [d0.b0 d1.b0 d0.b1 d1.b1], [.. b2 .. b3]
-    const uint32_t l23 = __builtin_amdgcn_perm(d[3], d[2], 0x05010400u), h23 = __builtin_amdgcn_perm(d[3], d[2], 0x07030602u);
-    c[0] = __builtin_amdgcn_perm(l23, l01, 0x05040100u);
-    c[1] = __builtin_amdgcn_perm(l23, l01, 0x07060302u);
-    c[2] = __builtin_amdgcn_perm(h23, h01, 0x05040100u);
-    c[3] = __builtin_amdgcn_perm(h23, h01, 0x07060302u);
-}
 
 // stage x and c[b][tile] of the chunk that starts at row r0: all loads first (one round trip), then the LDS writes (as mvt8_stage, mvm_t8.hip)
 __device__ __forceinline__ void m8t_stage(char *stage, float *cs, const float *__restrict__ sA, const int8_t *__restrict__ x,
@@ -74,23 +63,6 @@ __device__ __forceinline__ void m8t_stage(char *stage, float *cs, const float *_
     __syncthreads();
 }
 
-// this thread's 8 loads of each of the U blocks of group g (beyond the last block: the last block again).  Aq: the thread's column quad in
-// row 4 L of block 0
-template <int U, bool NT>
-__device__ __forceinline__ void m8t_load(const uint32_t *__restrict__ Aq, uint64_t stride, uint32_t g, uint32_t nblk, uint32_t (&a)[U][8])
-{
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const uint32_t blk = g * U + u < nblk ? g * U + u : nblk - 1;
-        const uint32_t *p0 = Aq + (uint64_t)blk * 64 * stride;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const uint32_t *p = p0 + (uint64_t)((i & 3) + 32 * (i >> 2)) * stride;
-            a[u][i] = NT ? __builtin_nontemporal_load(p) : *p;
-        }
-    }
-}
-
 // the chain link of one block for the thread's 4 columns: xs / cs = the block's x dwords and factors in LDS
 __device__ __forceinline__ void m8t_block(const uint32_t (&a)[8], const uint32_t *xs, const float *cs, int L, int tile, float (&acc)[4])
 {
@@ -99,8 +71,7 @@ __device__ __forceinline__ void m8t_block(const uint32_t (&a)[8], const uint32_t
     uint32_t lo[4], hi[4];
     m8t_transpose4x4(a, lo);
     m8t_transpose4x4(a + 4, hi);
-#pragma unroll
-    for (int k = 0; k < 4; k++) acc[k] = __builtin_fmaf(c, (float)sdot4(hi[k], xh, sdot4(lo[k], xl, 0)), acc[k]);
+    m8t_link(lo, hi, xl, xh, c, acc);
 }
 
 // group g of the walk from `cur` (loaded a group ago) while the next group's loads go to `nxt` -- issued UNCONDITIONALLY (beyond the last

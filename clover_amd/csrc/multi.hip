@@ -773,6 +773,13 @@ extern "C" int clm4_sharded_gemm_enqueue(clm4_shard_ctx *c, int step, int timed)
                                        hipMemcpyDeviceToDevice, c->cs[d]));
             }
         }
+        // to_root: the other shards exchange nothing, but the events recorded on their exchange streams below (the step's slot 2, gdone)
+        // must still lie behind their own kernel, as in the multi-device branch: without the wait slot 2 can precede slot 1 and
+        // clm4_sharded_step_timing reports a negative exchange time
+        for (int d = 1; to_root && d < n; d++) {
+            CLV_HIP(hipSetDevice(c->dev[d]));
+            CLV_HIP(hipStreamWaitEvent(c->cs[d], c->kdone[2 * d + b], 0));
+        }
     } else {
         for (int d = 0; d < n; d++) {
             CLV_HIP(hipSetDevice(c->dev[d]));

@@ -199,6 +199,16 @@ SIGNATURES_BATCH_T = {
                                            C.c_float, C.c_int, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); everything include/clover_hip_batch_t8.h declares (the batched transposed 8-bit mvm, the one-matrix batched
+# 8-bit IHT / GD loop): the signatures of the clm8_*_batch family, clm8_iht_batch_one_matrix without the PhiT / sPhiT pair
+SIGNATURES_BATCH_T8 = {
+    "clm8_mvm_transposed_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm8_mvm_transposed_batch_at": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp]),
+    "clm8_mvm_transposed_scale_and_add_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm8_iht_batch_one_matrix": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
+                                           C.c_float, C.c_int, _vp, _vp]),
+}
+
 
 class CloverHipError(RuntimeError):
     pass
@@ -213,7 +223,7 @@ def load_library(path: str | Path | None = None, allow_probe: bool = False) -> C
             f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = C.CDLL(str(p))
-    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items(), *SIGNATURES_BATCH_T8.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

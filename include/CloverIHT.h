@@ -171,9 +171,10 @@ inline void Q_GD_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 *c
  * draw from Phi's generator, as in Q_IHT_one_matrix: with dm = 2 (m / 64) and dn = 2 (n / 64) signal j's iteration `it` has its Phi window
  * at (j * iterations + it) * (dm + dn) and its Phi' window dm further on; the last iteration advances the generator by everything. */
 namespace clover_hip {
-inline void q_iht_batch_one_matrix_stochastic(CloverMatrix4 &Phi, CloverVector4 *const *x, CloverVector4 *const *y, CloverVector4 *const *t1,
-                                              CloverVector4 *const *t2, CloverVector4 *const *t3, const uint64_t count, const uint64_t iterations,
-                                              const uint64_t K, const float mu, const bool with_threshold)
+template <class QMatrix, class QVector>       /* CloverMatrix4 with CloverVector4, CloverMatrix8 with CloverVector8: the products draw 2 (m / 64) and 2 (n / 64) */
+inline void q_iht_batch_one_matrix_stochastic(QMatrix &Phi, QVector *const *x, QVector *const *y, QVector *const *t1, QVector *const *t2,
+                                              QVector *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K, const float mu,
+                                              const bool with_threshold)
 {
     for (uint64_t j = 0; j < count; j++) x[j]->clear();
     const uint64_t dm = 2 * (Phi.getRows() >> 6), dn = 2 * (Phi.getCols() >> 6), P = dm + dn;
@@ -183,7 +184,7 @@ inline void q_iht_batch_one_matrix_stochastic(CloverMatrix4 &Phi, CloverVector4 
         for (uint64_t j = 0; j < count; j++) y[j]->scaleAndAdd_parallel(*t1[j], -1.0f, *t2[j]);
         Phi.mvm_transposed_batch_at(t2, t3, count, it * P + dm, iterations * P, last ? count * iterations * P : 0);
         for (uint64_t j = 0; j < count; j++) x[j]->scaleAndAdd_parallel(*t3[j], mu);
-        if (with_threshold) CloverVector4::threshold_batch(x, count, K);
+        if (with_threshold) QVector::threshold_batch(x, count, K);
     }
 }
 }
@@ -386,6 +387,30 @@ inline void Q_GD_batch(CloverMatrix8 &Phi, CloverMatrix8 &PhiT, CloverVector8 *c
     Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
 #else
     clover_hip::q_iht_batch_stochastic(Phi, PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#endif
+}
+
+/* the one-matrix loops for `count` signals with ONE 8-bit Phi and no PhiT (clm8_iht_batch_one_matrix, clover_hip_batch_t8.h; stochastic:
+ * CloverMatrix8::mvm_batch_at and mvm_transposed_batch_at per step, both on Phi's generator): bit-identical to calling Q_IHT_one_matrix /
+ * Q_GD_one_matrix above signal after signal, Phi's generator included */
+inline void Q_IHT_batch_one_matrix(CloverMatrix8 &Phi, CloverVector8 *const *x, CloverVector8 *const *y, CloverVector8 *const *t1,
+                                   CloverVector8 *const *t2, CloverVector8 *const *t3, const uint64_t count, const uint64_t iterations,
+                                   const uint64_t K, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch_one_matrix(x, y, t1, t2, t3, count, iterations, K, mu, true);
+#else
+    clover_hip::q_iht_batch_one_matrix_stochastic(Phi, x, y, t1, t2, t3, count, iterations, K, mu, true);
+#endif
+}
+
+inline void Q_GD_batch_one_matrix(CloverMatrix8 &Phi, CloverVector8 *const *x, CloverVector8 *const *y, CloverVector8 *const *t1,
+                                  CloverVector8 *const *t2, CloverVector8 *const *t3, const uint64_t count, const uint64_t iterations, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch_one_matrix(x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#else
+    clover_hip::q_iht_batch_one_matrix_stochastic(Phi, x, y, t1, t2, t3, count, iterations, 0, mu, false);
 #endif
 }
 

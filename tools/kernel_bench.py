@@ -660,6 +660,112 @@ if any(selected(r) for r in MVTB_ROWS):
         sys.exit(0)
 
 
+# ---- A' x for several CloverVector8 straight from a CloverMatrix8 (matrix8_t_batch.hip): the rows of the block above for the pure 8-bit
+# pair.  Per row the calls come from ONE session on the same matrix and vectors, their rounds ALTERNATED: the batch call on the batched kernel
+# (CLV_MVM_BATCH=1), the same vectors as g single clm8_mvm_transposed (clm8_mvm_transposed_scale_and_add) calls, clm8_mvm_batch
+# (clm8_mvm_scale_and_add_batch) on a held A' and, in the plain rows, clm8_transpose + clm8_mvm_batch.  The *_st_* twins run with a generator.
+# m8_iht_batch_one_matrix_N8192: clm8_iht_batch_one_matrix against 8 x clm8_iht_one_matrix and clm8_iht_batch, ms per iteration for 8 signals.
+# KB_ONLY=m8_mvm_transposed_batch,m8_mvm_transposed_saa_batch,m8_iht_batch_one_matrix selects them and the run ends after them.
+M8TB_ROWS = tuple(f"m8_mvm_transposed_batch{g}_{t}{nb}" for nb in (32768, 65536) for g in (2, 4, 8) for t in ("", "st_")) + \
+    tuple(f"m8_mvm_transposed_saa_batch{g}_{t}{shape}" for shape in ("8192x4096", "65536^2") for g in (2, 4, 8) for t in ("", "st_")) + \
+    ("m8_iht_batch_one_matrix_N8192", "m8_iht_batch_one_matrix_st_N8192")
+
+if any(selected(r) for r in M8TB_ROWS):
+    def rec_m8tb(name, g, singles, batch, held, reps, per=1, pair=None):
+        """rec_three with, where pair is given, a fourth alternated call: the transpose followed by the held batch"""
+        if not selected(name):
+            return
+        os.environ.pop("CLV_MVM_BATCH", None)
+        fns = (singles, forced_batch(batch), forced_batch(held)) + ((forced_batch(pair),) if pair else ())
+        ts = [[t / per for t in r] for r in alternated(fns, reps=reps)]
+        one, many, hold = ts[:3]
+        o, m, h = one[len(one) // 2], many[len(many) // 2], hold[len(hold) // 2]
+        spread = (one[-1] - one[0]) + (many[-1] - many[0])
+        res[name] = {"vectors": g, "batch_ms": round(m, 5), "single_calls_ms": round(o, 5), "batch_on_a_held_transpose_ms": round(h, 5),
+                     "batch_rounds_ms": [round(t, 5) for t in many], "single_calls_rounds_ms": [round(t, 5) for t in one],
+                     "batch_on_a_held_transpose_rounds_ms": [round(t, 5) for t in hold], "spread_of_both_ms": round(spread, 5),
+                     "speedup_over_single_calls": round(o / m, 3), "batch_faster_by_more_than_the_spread_of_both": bool(o - m > spread),
+                     "ratio_to_batch_on_a_held_transpose": round(m / h, 3)}
+        if pair:
+            p = ts[3]
+            res[name].update({"transpose_then_batch_ms": round(p[len(p) // 2], 5), "transpose_then_batch_rounds_ms": [round(t, 5) for t in p]})
+
+    def m8tb_rows(tag, rows, cols, reps):
+        """the plain rows (tag = the size) or the fused ones (tag = the shape's name) of one matrix of rows x cols"""
+        fusedf = not tag.isdigit()
+        stem = "m8_mvm_transposed_saa_batch" if fusedf else "m8_mvm_transposed_batch"
+        if not any(selected(f"{stem}{g}_{t}{tag}") for g in (2, 4, 8) for t in ("", "st_")):
+            return
+        (tA, tsA), tAt, tsAt = m8_matrix(rows, cols, 65), hip.alloc(rows * cols), hip.alloc(4 * (rows // 64) * (cols // 64))
+        hip.check(lib.clm8_transpose(tA.ptr, tsA.ptr, rows, cols, tAt.ptr, tsAt.ptr, None))
+        vx, vu, vt, vr = vec8_set(8, rows, 330), vec8_set(8, cols, 340), vec8_set(8, cols, 350), vec8_set(8, cols, 360)
+        for g in (2, 4, 8):
+            a = {k: (ptrs([p[0] for p in v[:g]]), ptrs([p[1] for p in v[:g]])) for k, v in dict(x=vx, u=vu, t=vt, r=vr).items()}
+            for t, st in (("", None), ("st_", hip.new_rng(1, 2))):
+                sp = st.ptr if st else None
+                pair = None
+                if fusedf:
+                    def singles(g=g, sp=sp):
+                        for j in range(g):
+                            hip.check(lib.clm8_mvm_transposed_scale_and_add(tA.ptr, tsA.ptr, rows, cols, vx[j][0].ptr, vx[j][1].ptr, vu[j][0].ptr,
+                                                                            vu[j][1].ptr, 0.002, vt[j][0].ptr, vt[j][1].ptr, vr[j][0].ptr, vr[j][1].ptr, sp, None))
+
+                    def batch(g=g, a=a, sp=sp):
+                        hip.check(lib.clm8_mvm_transposed_scale_and_add_batch(tA.ptr, tsA.ptr, rows, cols, g, a["x"][0], a["x"][1], a["u"][0], a["u"][1],
+                                                                              0.002, a["t"][0], a["t"][1], a["r"][0], a["r"][1], sp, None))
+
+                    def held(g=g, a=a, sp=sp):
+                        hip.check(lib.clm8_mvm_scale_and_add_batch(tAt.ptr, tsAt.ptr, cols, rows, g, a["x"][0], a["x"][1], a["u"][0], a["u"][1], 0.002,
+                                                                   a["t"][0], a["t"][1], a["r"][0], a["r"][1], sp, None))
+                else:
+                    def singles(g=g, sp=sp):
+                        for j in range(g):
+                            hip.check(lib.clm8_mvm_transposed(tA.ptr, tsA.ptr, rows, cols, vx[j][0].ptr, vx[j][1].ptr, vr[j][0].ptr, vr[j][1].ptr, sp, None))
+
+                    def batch(g=g, a=a, sp=sp):
+                        hip.check(lib.clm8_mvm_transposed_batch(tA.ptr, tsA.ptr, rows, cols, g, a["x"][0], a["x"][1], a["r"][0], a["r"][1], sp, None))
+
+                    def held(g=g, a=a, sp=sp):
+                        hip.check(lib.clm8_mvm_batch(tAt.ptr, tsAt.ptr, cols, rows, g, a["x"][0], a["x"][1], a["r"][0], a["r"][1], sp, None))
+
+                    def pair(held=held):
+                        hip.check(lib.clm8_transpose(tA.ptr, tsA.ptr, rows, cols, tAt.ptr, tsAt.ptr, None))
+                        held()
+                rec_m8tb(f"{stem}{g}_{t}{tag}", g, singles, batch, held, reps, pair=pair)
+        del tA, tsA, tAt, tsAt
+
+    m8tb_rows("32768", 32768, 32768, 10)
+    m8tb_rows("65536", 65536, 65536, 4)
+    m8tb_rows("8192x4096", 4096, 8192, 20)          # the IHT shape's step 2: Phi is 4096 x 8192, t3 = Phi' t2
+    m8tb_rows("65536^2", 65536, 65536, 4)
+    im, inn, ig, iters = 4096, 8192, 8, 20
+    if selected("m8_iht_batch_one_matrix_N8192") or selected("m8_iht_batch_one_matrix_st_N8192"):
+        (P, sP), PT, sPT = m8_matrix(im, inn, 67), hip.alloc(im * inn), hip.alloc(4 * (im // 64) * (inn // 64))
+        hip.check(lib.clm8_transpose(P.ptr, sP.ptr, im, inn, PT.ptr, sPT.ptr, None))
+        vy, vx, vt1, vt2, vt3 = vec8_set(ig, im, 500), vec8_set(ig, inn, 600), vec8_set(ig, im, 700), vec8_set(ig, im, 800), vec8_set(ig, inn, 900)
+        A = {k: (ptrs([p[0] for p in v]), ptrs([p[1] for p in v])) for k, v in dict(y=vy, x=vx, t1=vt1, t2=vt2, t3=vt3).items()}
+        for t, st in (("", None), ("st_", hip.new_rng(1, 2))):
+            sp = st.ptr if st else None
+            tail = (im, inn, ig, A["x"][0], A["x"][1], inn, A["y"][0], A["y"][1], A["t1"][0], A["t1"][1], A["t2"][0], A["t2"][1], A["t3"][0], A["t3"][1],
+                    iters, im // 4, 0.002, 1, sp, None)
+
+            def singles(sp=sp):
+                for j in range(ig):
+                    hip.check(lib.clm8_iht_one_matrix(P.ptr, sP.ptr, im, inn, vx[j][0].ptr, vx[j][1].ptr, inn, vy[j][0].ptr, vy[j][1].ptr, vt1[j][0].ptr,
+                                                      vt1[j][1].ptr, vt2[j][0].ptr, vt2[j][1].ptr, vt3[j][0].ptr, vt3[j][1].ptr, iters, im // 4, 0.002, 1, sp,
+                                                      None))
+            name = f"m8_iht_batch_one_matrix_{t}N8192"
+            rec_m8tb(name, ig, singles, lambda tail=tail: hip.check(lib.clm8_iht_batch_one_matrix(P.ptr, sP.ptr, *tail)),
+                     lambda tail=tail: hip.check(lib.clm8_iht_batch(P.ptr, sP.ptr, PT.ptr, sPT.ptr, *tail)), reps=2, per=iters)
+            if name in res:
+                res[name]["note"] = (f"ms per iteration for all 8 signals, calls of {iters} iterations, K = m / 4, FAST threshold; the single calls are "
+                                     "8 x clm8_iht_one_matrix, the held-transpose column is clm8_iht_batch under CLV_MVM_BATCH=1")
+        del P, sP, PT, sPT, vy, vx, vt1, vt2, vt3
+    if ONLY and all(any(o in r for r in M8TB_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
+
+
 # ---- A' x for CloverVector8 straight from A (mvm_t8.hip): the three rows per size of the block above with clm4_mvm_v8_transposed, clm4_transpose +
 # clm4_mvm_v8 and clm4_mvm_v8 on a held A', rounds alternated in one session; iht_v8_one_matrix_*: clm4_iht_v8_one_matrix against clm4_iht_v8.
 # KB_ONLY=mvm_v8_transposed,transpose_then_mvm_v8,mvm_v8_held_transpose,iht_v8_one_matrix selects them and the run ends after them.
