@@ -1,5 +1,5 @@
 // mvm8_device.h -- device helpers shared by the mvm kernels with CloverVector8 vectors: the mixed ones (4-bit matrix: k_m4_mvm8, mixed8.hip;
-// k_m4_mvm8_batch, mvm_batch8.hip; k_m4_mvm8_t, mvm_t8.hip) and, for the factor, the noise maps, the tree and the re-quantisation, the
+// k_m4_mvm8_batch, mvm_batch8.hip; k_m4_mvm8_t, mvm_t8.hip; k_m4_mvm8_t_batch, mvm_t8_batch.hip) and, for the factor, the noise maps, the tree and the re-quantisation, the
 // CloverMatrix8 ones (k_m8_mvm, matrix8.hip; k_m8_mvm_t, matrix8_t.hip; k_m8_mvm_batch, matrix8_batch.hip; k_m8_mvm_t_batch, matrix8_t_batch.hip).  The bits of a result are fixed by this instruction sequence, so
 // the kernels take it from here (as mvm_device.h does for the 4-bit pair).
 #pragma once
@@ -86,6 +86,24 @@ struct Mvm8Fuse {
     float a;
     int8_t *r2;              // may alias qu (the in-place overload)
     float *sr2;
+};
+
+// the vectors of one batched CloverMatrix4 x CloverVector8 pass (k_m4_mvm8_batch, mvm_batch8.hip; k_m4_mvm8_t_batch, mvm_t8_batch.hip), BY
+// VALUE in the kernel arguments (see MvmBatchArgs, mvm_device.h).  Slots >= nv are absent: NULL, never dereferenced.
+template <int NV>
+struct Mvm8BatchArgs {
+    const int8_t *x[NV];
+    const float *sx[NV];
+    int8_t *r[NV];           // all NULL: the mvm result is not stored (FUSE only)
+    float *sr[NV];
+};
+template <int NV>
+struct Mvm8BatchFuse {       // see Mvm8Fuse
+    const int8_t *qu[NV];
+    const float *su[NV];
+    int8_t *r2[NV];          // may be qu (in place)
+    float *sr2[NV];
+    float a;
 };
 
 // the vectors of one batched CloverMatrix8 pass (k_m8_mvm_batch, matrix8_batch.hip; k_m8_mvm_t_batch, matrix8_t_batch.hip), BY VALUE in the

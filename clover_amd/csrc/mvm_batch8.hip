@@ -7,6 +7,9 @@
 // vector of the group.  Each vector's instruction sequence is the one of mvm8_device.h, so the results equal the single calls bit for bit.
 #include "mvm_batch_host.h"
 #include "mvm8_device.h"
+#include "mvm_t8_batch.h"
+
+#include "clover_hip_batch_t_v8.h"
 
 // Columns of x staged in LDS per pass.  The single-vector kernel stages 32768 (32 KiB + factors); NV vectors at that size would not fit.
 // 4096 columns are 4 KiB of int8 + 256 B of block factors + 256 B of row dots per vector: 36 KiB at NV = 8 (36.5 KiB with the generator
@@ -15,22 +18,8 @@
 #define MVMB8_THREADS 256
 #define MVMB8_U(NV) ((NV) <= 4 ? 8 : 4)         // 16-byte matrix loads in flight per lane: 2 accumulators per vector + 4 U registers of matrix words
 
-// the vectors of one pass, BY VALUE in the kernel arguments (see MvmBatchArgs, mvm_batch4.hip).  Slots >= nv are absent: NULL, never dereferenced.
-template <int NV>
-struct Mvm8BatchArgs {
-    const int8_t *x[NV];
-    const float *sx[NV];
-    int8_t *r[NV];           // all NULL: the mvm result is not stored (FUSE only)
-    float *sr[NV];
-};
-template <int NV>
-struct Mvm8BatchFuse {       // see Mvm8Fuse
-    const int8_t *qu[NV];
-    const float *su[NV];
-    int8_t *r2[NV];          // may be qu (in place)
-    float *sr2[NV];
-    float a;
-};
+// Mvm8BatchArgs / Mvm8BatchFuse (the vectors of one pass, by value in the kernel arguments): mvm8_device.h, shared with the transposed batched
+// kernel (mvm_t8_batch.hip)
 
 #define MVMB8_X_BYTES(NV) ((NV) * (MVMB8_CHUNK + (MVMB8_CHUNK / 64) * sizeof(float) + 64 * sizeof(float)))
 // ST: behind the row dots, per vector and window the start of each of the 4 generator lanes (32 B): 512 B at NV = 8 fused
@@ -246,4 +235,15 @@ extern "C" int clm4_iht_v8_batch(const int8_t *Phi, const float *sPhi, const int
 {
     return mvm_batch_iht<Mvm8Batch>("clm4_iht_v8_batch", Phi, sPhi, PhiT, sPhiT, m, n, nvec, x, sx, x_len, y, sy, t1, st1, t2, st2, t3, st3, iterations,
                                     K, mu, threshold, rng_state_dev, stream);
+}
+
+// The same loop with ONE matrix (include/clover_hip_batch_t_v8.h): step 1 is this family's fused launch on Phi, step 2 the transposed
+// family's (mvm_t8_batch.hip) on the same bytes; the draws lie where the two-matrix loop has them.
+extern "C" int clm4_iht_v8_batch_one_matrix(const int8_t *Phi, const float *sPhi, uint64_t m, uint64_t n, uint64_t nvec, int8_t *const *x,
+                                            float *const *sx, uint64_t x_len, const int8_t *const *y, const float *const *sy, int8_t *const *t1,
+                                            float *const *st1, int8_t *const *t2, float *const *st2, int8_t *const *t3, float *const *st3,
+                                            uint64_t iterations, uint64_t K, float mu, int threshold, uint64_t *rng_state_dev, void *stream)
+{
+    return mvm_batch_iht<Mvm8Batch, MvmT8Batch>("clm4_iht_v8_batch_one_matrix", Phi, sPhi, nullptr, nullptr, m, n, nvec, x, sx, x_len, y, sy, t1, st1,
+                                                t2, st2, t3, st3, iterations, K, mu, threshold, rng_state_dev, stream);
 }

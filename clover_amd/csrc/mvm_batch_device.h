@@ -1,5 +1,5 @@
 // mvm_batch_device.h -- the stochastic-rounding plumbing shared by the batched mvm kernels: k_m4_mvm_batch (mvm_batch4.hip),
-// k_m4_mvm8_batch (mvm_batch8.hip), k_m8_mvm_batch (matrix8_batch.hip), k_m4_mvm_t_batch (mvm_t4_batch.hip) and k_m8_mvm_t_batch (matrix8_t_batch.hip).  All place a vector's draws where the sequence of single calls has them, by the same jump-ahead.
+// k_m4_mvm8_batch (mvm_batch8.hip), k_m8_mvm_batch (matrix8_batch.hip), k_m4_mvm_t_batch (mvm_t4_batch.hip), k_m4_mvm8_t_batch (mvm_t8_batch.hip) and k_m8_mvm_t_batch (matrix8_t_batch.hip).  All place a vector's draws where the sequence of single calls has them, by the same jump-ahead.
 #pragma once
 
 #include "rng_device.h"
@@ -62,7 +62,7 @@ __device__ __forceinline__ float mvmb_noise(const uint64_t *base, int grp, int j
 // the state the launch reads, for every vector and window in one walk over the table levels (NV = 8 fused: two), the starts left in
 // sbase[(v * NW + w) * 4 + k]; nothing of it lives in registers across the column loop.  NW = windows per vector (the mvm's draws,
 // the scaleAndAdd's).  rb = the workgroup's (first) output block, G = the output blocks of the launch: one block per workgroup in the
-// row-major kernels (G = gridDim.x), MVT_W / M8TB_W consecutive ones in the transposed kernels (mvm_t4_batch.hip, matrix8_t_batch.hip), whose starts are those of rb.  Returns, in workgroup 0 of a committing launch, the slot whose state this wave has written -- the caller stamps
+// row-major kernels (G = gridDim.x), MVT_W / MVT8B_W / M8TB_W consecutive ones in the transposed kernels (mvm_t4_batch.hip, mvm_t8_batch.hip, matrix8_t_batch.hip), whose starts are those of rb.  Returns, in workgroup 0 of a committing launch, the slot whose state this wave has written -- the caller stamps
 // it with st_seq behind its last barrier (mvmb_rng_stamp) -- and NULL elsewhere.
 template <int NV, int NW>
 __device__ __forceinline__ uint64_t *mvmb_rng_prologue(const MvmBatchRng &rs, int nv, uint64_t rb, uint64_t G, uint64_t *sbase, uint64_t &st_seq)

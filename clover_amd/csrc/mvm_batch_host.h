@@ -1,7 +1,8 @@
 // mvm_batch_host.h -- the host side of the batched mvm families, written once: group policy, launch, the two group loops, the argument
 // and overlap check and the batched IHT / GD loop.  Included by mvm_batch4.hip (CloverMatrix4 x CloverVector4), mvm_batch8.hip
 // (CloverMatrix4 x CloverVector8), matrix8_batch.hip (CloverMatrix8 x CloverVector8), mvm_t4_batch.hip (CloverMatrix4' x CloverVector4
-// straight from the matrix's own bytes) and matrix8_t_batch.hip (CloverMatrix8' x CloverVector8, likewise) and by nothing else.  Each of them defines its
+// straight from the matrix's own bytes), mvm_t8_batch.hip (CloverMatrix4' x CloverVector8, likewise) and matrix8_t_batch.hip (CloverMatrix8' x
+// CloverVector8, likewise) and by nothing else.  Each of them defines its
 // kernel and a traits struct F with exactly what differs between the families:
 //   Args<NV>, Fuse<NV>                        the kernel's by-value argument structs (their pointer types decide the casts)
 //   matrix_bytes(rows, cols), vector_bytes(n) sizes for the overlap check; the matrix streams (NT) above the 256 MiB Infinity Cache
@@ -48,7 +49,8 @@ struct MvmBatchByRows {
 //           batched launch beat the single calls by more than their spread in every row -- 65536^2 and 32768^2 (streaming), fused at
 //           8192 x 4096 (cache-resident) and at 65536^2, the IHT loop at N = 8192, either rounding.  Not measured: groups of 3 and 5-7,
 //           matrices between 32 MiB and 1 GiB or below 32 MiB.
-// The transposed families have rules of their own (MvmT4Batch::batched_by_rule, mvm_t4_batch.h; M8TBatch::batched_by_rule, matrix8_t_batch.h).
+// The transposed families have rules of their own (MvmT4Batch::batched_by_rule, mvm_t4_batch.h; MvmT8Batch::batched_by_rule, mvm_t8_batch.h;
+// M8TBatch::batched_by_rule, matrix8_t_batch.h).
 template <class F>
 static inline bool mvm_batch_selected(uint64_t g, uint64_t rows, uint64_t cols, bool fused, bool stochastic)
 {

@@ -30,8 +30,7 @@
 // Stochastic rounding: output block cb takes the draws clm4_mvm_v8 gives row group cb of a stored A' (mvm8_prologue, mixed8.hip): 2 cb,
 // 2 cb + 1 and, fused, 2 G + 2 cb, 2 G + 2 cb + 1 (G = cols / 64); the state is left advanced by 2 G (4 G).
 #include "rng_device.h"
-#include "mvm8_device.h"
-#include "nibble_transpose.h"
+#include "mvm_t8_device.h"         // mvt8_load, mvt8_int: shared with k_m4_mvm8_t_batch (mvm_t8_batch.hip)
 
 #include <vector>
 
@@ -46,16 +45,8 @@ static_assert(MVT8_W == 2 && MVT8_STEP == 64 * 4, "the lane map (four waves, one
 static_assert(MVT8_CHUNK % (64 * 256) == 0 && MVT8_CHUNK % (2 * MVT8_STEP) == 0, "the staging loops assume whole rounds of 256 threads");
 static_assert(MVT8_U == 1, "mvt8_round keeps exactly one round of loads ahead");
 
-// this lane's 16 loads of one row block: rows 8 m + i (lo) and 32 + 8 m + i (hi).  Ap: the lane's column group in row 8 m of the block
-template <bool NT>
-__device__ __forceinline__ void mvt8_load(const uint32_t *__restrict__ Ap, uint64_t stride, uint32_t (&a)[16])
-{
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const uint32_t *p = Ap + (uint64_t)((i & 7) + 32 * (i >> 3)) * stride;
-        a[i] = NT ? __builtin_nontemporal_load(p) : *p;
-    }
-}
+// this lane's 16 loads of one row block -- rows 8 m + i (lo) and 32 + 8 m + i (hi); Ap: the lane's column group in row 8 m of the block --
+// are mvt8_load<8, 2, NT> (mvm_t8_device.h)
 
 // the block integers of chains 2 m, 2 m + 1 for the lane's 8 columns, packed as int16 pairs into the hand-over.  xb: the block's x in LDS
 __device__ __forceinline__ void mvt8_produce(const uint32_t (&a)[16], const u32x2 *xb, int m, uint32_t *out)
@@ -73,8 +64,8 @@ __device__ __forceinline__ void mvt8_produce(const uint32_t (&a)[16], const u32x
         uint32_t f03, f47, s03, s47;
         widen8(Olo[e], f03, f47);
         widen8(Ohi[e], s03, s47);
-        const int ie = sdot4(s03, x1.x, sdot4(f03, x0.x, 0)) >> 4;      // chain 2 m   (exact: the sum is a multiple of 16)
-        const int io = sdot4(s47, x1.y, sdot4(f47, x0.y, 0)) >> 4;      // chain 2 m + 1
+        const int ie = mvt8_int(f03, x0.x, s03, x1.x);                  // chain 2 m   (exact: the sum is a multiple of 16)
+        const int io = mvt8_int(f47, x0.y, s47, x1.y);                  // chain 2 m + 1
         out[16 * e] = ((uint32_t)ie & 0xFFFFu) | ((uint32_t)io << 16);
     }
 }
@@ -128,7 +119,7 @@ __device__ __forceinline__ void mvt8_round(const uint32_t (&cur)[16], uint32_t (
 {
     constexpr uint32_t CB = MVT8_CHUNK / 64;                                   // blocks per chunk
     const uint32_t blk = 4 * R + wave, next = blk + 4 < nblk ? blk + 4 : nblk - 1, buf = (R & 1) * (4 * MVT8_HAND_BLOCK);
-    mvt8_load<NT>(Acol + (uint64_t)next * 64 * stride, stride, nxt);
+    mvt8_load<8, 2, NT>(Acol + (uint64_t)next * 64 * stride, stride, nxt);
     if (blk < nblk) mvt8_produce(cur, xs + 8 * (blk % CB), m, hand_out + buf); // wave-uniform
     __syncthreads();
     const float *c = cs + MVT8_W * (4 * R % CB) + tile;
@@ -191,7 +182,7 @@ __global__ __launch_bounds__(256) void k_m4_mvm8_t(const uint8_t *__restrict__ A
     constexpr uint32_t CR = MVT8_CHUNK / MVT8_STEP;
     const uint32_t nblk = (uint32_t)(rows / 64), nrounds = (nblk + 3) / 4;
     uint32_t a[16], b[16];
-    mvt8_load<NT>(Acol + (uint64_t)((uint32_t)wave < nblk ? wave : nblk - 1) * 64 * stride, stride, a);
+    mvt8_load<8, 2, NT>(Acol + (uint64_t)((uint32_t)wave < nblk ? wave : nblk - 1) * 64 * stride, stride, a);
     uint32_t R = 0;
     for (; R + 1 < nrounds; R += 2) {
         if (R % CR == 0) mvt8_stage(stage, cs, sA, x, sx, rows, (uint64_t)R * MVT8_STEP, G, cb0, tid);

@@ -209,6 +209,17 @@ SIGNATURES_BATCH_T8 = {
                                            C.c_float, C.c_int, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); everything include/clover_hip_batch_t_v8.h declares (the batched transposed mixed mvm, CloverMatrix4 x
+# CloverVector8, and the one-matrix batched mixed IHT / GD loop): the signatures of the clm4_*_v8_batch family, clm4_iht_v8_batch_one_matrix
+# without the PhiT / sPhiT pair
+SIGNATURES_BATCH_T_V8 = {
+    "clm4_mvm_v8_transposed_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm4_mvm_v8_transposed_batch_at": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp]),
+    "clm4_mvm_v8_transposed_scale_and_add_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "clm4_iht_v8_batch_one_matrix": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
+                                              C.c_float, C.c_int, _vp, _vp]),
+}
+
 
 class CloverHipError(RuntimeError):
     pass
@@ -223,7 +234,7 @@ def load_library(path: str | Path | None = None, allow_probe: bool = False) -> C
             f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = C.CDLL(str(p))
-    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items(), *SIGNATURES_BATCH_T8.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items(), *SIGNATURES_BATCH_T8.items(), *SIGNATURES_BATCH_T_V8.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -641,6 +652,30 @@ class CloverHip:
         else:
             self.check(self.lib.clm4_iht_v8(b[0].ptr, b[1].ptr, b[4].ptr, b[5].ptr, m, n, *tail))
         return {name: (v[name][0].download(np.int8, ln), v[name][1].download(np.float32, ln // 64)) for name, ln in lens.items()}
+
+    def m4_iht_v8_batch(self, qPhi, sPhi, qPhiT, sPhiT, m, n, ys, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+                        rng: DevBuf | None = None, prefill: int = 0x55):
+        """clm4_iht_v8_batch on buffers prefilled with `prefill` bytes -- or, with qPhiT None, clm4_iht_v8_batch_one_matrix; ys: list of
+        (qy, sy); returns per vector {"x": (q, s), "t1": ..., "t2": ..., "t3": ...}"""
+        b = [self.to_device(v) for v in ((qPhi, sPhi) if qPhiT is None else (qPhi, sPhi, qPhiT, sPhiT))]
+        dy = [(self.to_device(q), self.to_device(s)) for q, s in ys]
+        lens = {"x": n, "t1": m, "t2": m, "t3": n}
+        v = {name: [(self.alloc(ln), self.alloc(ln // 16)) for _ in ys] for name, ln in lens.items()}
+        for bufs in v.values():
+            for pair in bufs:
+                for d in pair:
+                    self.check(self.lib.clv_memset(d.ptr, prefill, d.nbytes, None))
+        pa = self.ptr_array
+        arr = {name: (pa([d[0] for d in bufs]), pa([d[1] for d in bufs])) for name, bufs in v.items()}
+        tail = (m, n, len(ys), arr["x"][0], arr["x"][1], n if x_len is None else x_len, pa([d[0] for d in dy]), pa([d[1] for d in dy]),
+                arr["t1"][0], arr["t1"][1], arr["t2"][0], arr["t2"][1], arr["t3"][0], arr["t3"][1], iterations, K, mu, threshold,
+                rng.ptr if rng else None, None)
+        if qPhiT is None:
+            self.check(self.lib.clm4_iht_v8_batch_one_matrix(b[0].ptr, b[1].ptr, *tail))
+        else:
+            self.check(self.lib.clm4_iht_v8_batch(b[0].ptr, b[1].ptr, b[2].ptr, b[3].ptr, *tail))
+        return [{name: (v[name][j][0].download(np.int8, ln), v[name][j][1].download(np.float32, ln // 64)) for name, ln in lens.items()}
+                for j in range(len(ys))]
 
     def m4_mvm_f32(self, qA, sA, rows, cols, x) -> np.ndarray:
         b = [self.to_device(a) for a in (qA, sA, np.ascontiguousarray(x, dtype=np.float32))]

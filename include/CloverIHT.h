@@ -171,7 +171,7 @@ inline void Q_GD_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector4 *c
  * draw from Phi's generator, as in Q_IHT_one_matrix: with dm = 2 (m / 64) and dn = 2 (n / 64) signal j's iteration `it` has its Phi window
  * at (j * iterations + it) * (dm + dn) and its Phi' window dm further on; the last iteration advances the generator by everything. */
 namespace clover_hip {
-template <class QMatrix, class QVector>       /* CloverMatrix4 with CloverVector4, CloverMatrix8 with CloverVector8: the products draw 2 (m / 64) and 2 (n / 64) */
+template <class QMatrix, class QVector>       /* CloverMatrix4 with CloverVector4 or CloverVector8, CloverMatrix8 with CloverVector8: the products draw 2 (m / 64) and 2 (n / 64) */
 inline void q_iht_batch_one_matrix_stochastic(QMatrix &Phi, QVector *const *x, QVector *const *y, QVector *const *t1, QVector *const *t2,
                                               QVector *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K, const float mu,
                                               const bool with_threshold)
@@ -209,6 +209,32 @@ inline void Q_GD_batch_one_matrix(CloverMatrix4 &Phi, CloverVector4 *const *x, C
     clover_hip::q_iht_batch_one_matrix_stochastic(Phi, x, y, t1, t2, t3, count, iterations, 0, mu, false);
 #endif
 }
+
+/* the same for `count` CloverVector8 signals with ONE CloverMatrix4 Phi and no PhiT -- the published "4-bit" configuration
+ * (clm4_iht_v8_batch_one_matrix, clover_hip_batch_t_v8.h; stochastic: the CloverVector8 overloads of CloverMatrix4::mvm_batch_at and
+ * mvm_transposed_batch_at per step, both on Phi's generator): bit-identical to calling the CloverVector8 overloads of Q_IHT_one_matrix /
+ * Q_GD_one_matrix signal after signal, Phi's generator included */
+inline void Q_IHT_batch_one_matrix(CloverMatrix4 &Phi, CloverVector8 *const *x, CloverVector8 *const *y, CloverVector8 *const *t1,
+                                   CloverVector8 *const *t2, CloverVector8 *const *t3, const uint64_t count, const uint64_t iterations,
+                                   const uint64_t K, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch_one_matrix(x, y, t1, t2, t3, count, iterations, K, mu, true);
+#else
+    clover_hip::q_iht_batch_one_matrix_stochastic(Phi, x, y, t1, t2, t3, count, iterations, K, mu, true);
+#endif
+}
+
+inline void Q_GD_batch_one_matrix(CloverMatrix4 &Phi, CloverVector8 *const *x, CloverVector8 *const *y, CloverVector8 *const *t1,
+                                  CloverVector8 *const *t2, CloverVector8 *const *t3, const uint64_t count, const uint64_t iterations, const float mu)
+{
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+    Phi.iht_loop_batch_one_matrix(x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#else
+    clover_hip::q_iht_batch_one_matrix_stochastic(Phi, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+#endif
+}
+
 
 
 /* CloverMatrix4 with CloverVector8 vectors: the configuration the reference measures and publishes as the 4-bit IHT / GD

@@ -32,6 +32,7 @@
 #include "CloverVector4.h"
 #include "CloverVector8.h"
 #include "clover_hip_batch_t.h"   /* the batched transposed calls: a header of their own beside clover_hip.h */
+#include "clover_hip_batch_t_v8.h" /* the same for CloverVector8 vectors */
 
 class CloverMatrix4 {
 protected:
@@ -860,6 +861,134 @@ public:
         x.commit();
         if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
     }
+    /* Not in the reference: this' * x[j] for `count` CloverVector8 in ONE pass over this matrix's own bytes per group of
+     * CLM4_MVM_BATCH_MAX (clm4_mvm_v8_transposed_batch, clover_hip_batch_t_v8.h); r[j] equals what mvm_transposed(*x[j], *r[j]) gives, bit
+     * for bit.  The x[j] may repeat; the r[j] are distinct vectors, none of them an x.  With stochastic rounding enabled the vectors draw
+     * from the matrix's generator one after another, as the single calls in order do, and the generator ends where those calls leave it. */
+    void mvm_transposed_batch(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count)
+    {
+        mvm_v8_transposed_batch_at_impl(x, r, count, 0, 0, 0, false);
+    }
+    /* mvm_transposed_batch with the place of every vector's draws chosen by the caller (clm4_mvm_v8_transposed_batch_at), counted in draws
+     * -- mvm_transposed consumes 2 (cols / 64) -- from where the matrix's generator stands: vector j draws from draw_base + j * draw_stride
+     * on, and the generator is advanced by commit_draws afterwards (0: left as it is).  For callers whose stream order is not vector after
+     * vector (Q_IHT_batch_one_matrix, CloverIHT.h).  With rounding disabled the three numbers are ignored. */
+    void mvm_transposed_batch_at(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
+                                 uint64_t commit_draws)
+    {
+        mvm_v8_transposed_batch_at_impl(x, r, count, draw_base, draw_stride, commit_draws, true);
+    }
+    /* mvm_transposed_scaleAndAdd for `count` CloverVector8: t[j] = this' * x[j], r[j] = quantize(u[j] + a * t[j]).  Rounding disabled: one
+     * launch per group (clm4_mvm_v8_transposed_scale_and_add_batch).  Stochastic: one mvm_transposed_batch and the scaleAndAdd calls, which
+     * draw from their u[j]'s own generators -- the bits of the loop of mvm_transposed_scaleAndAdd. */
+    void mvm_transposed_scaleAndAdd_batch(const CloverVector8 *const *x, const CloverVector8 *const *u, float a, CloverVector8 *const *t,
+                                          CloverVector8 *const *r, uint64_t count)
+    {
+        for (uint64_t j = 0; j < count; j++) {
+            check_fused_transposed(*x[j], *u[j], *t[j]);
+            if (r[j]->size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        }
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        const DevArrays8 px = dev_inputs8(x, count), pu = dev_inputs8(u, count), pt = dev_outputs8(t, count, false), pr = dev_outputs8(r, count, false);
+        clover_hip::check(clm4_mvm_v8_transposed_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.q.data(), px.s.data(),
+                                                                     pu.q.data(), pu.s.data(), a, pt.q.data(), pt.s.data(), pr.q.data(), pr.s.data(),
+                                                                     nullptr, nullptr),
+                          "CloverMatrix4::mvm_transposed_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
+#else
+        mvm_transposed_batch(x, t, count);
+        for (uint64_t j = 0; j < count; j++) const_cast<CloverVector8 *>(u[j])->scaleAndAdd(*t[j], a, *r[j]);
+#endif
+    }
+    /* in place: u[j] = quantize(u[j] + a * (this' * x[j])) */
+    void mvm_transposed_scaleAndAdd_batch(const CloverVector8 *const *x, CloverVector8 *const *u, float a, CloverVector8 *const *t, uint64_t count)
+    {
+        for (uint64_t j = 0; j < count; j++) check_fused_transposed(*x[j], *u[j], *t[j]);
+#ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
+        const DevArrays8 px = dev_inputs8(x, count), pu = dev_outputs8(u, count, true), pt = dev_outputs8(t, count, false);
+        clover_hip::check(clm4_mvm_v8_transposed_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.q.data(), px.s.data(),
+                                                                     pu.q.data(), pu.s.data(), a, pt.q.data(), pt.s.data(), pu.q.data(), pu.s.data(),
+                                                                     nullptr, nullptr),
+                          "CloverMatrix4::mvm_transposed_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
+#else
+        mvm_transposed_batch(x, t, count);
+        for (uint64_t j = 0; j < count; j++) u[j]->scaleAndAdd(*t[j], a);
+#endif
+    }
+    /* iht_loop_one_matrix for `count` CloverVector8 signals with this matrix as Phi and no PhiT (clm4_iht_v8_batch_one_matrix): per
+     * iteration every step runs once for a group of signals, t3 = Phi' t2 from this matrix's own bytes; x[j], t1[j], t2[j], t3[j] end as
+     * iht_loop_one_matrix(*x[j], *y[j], ...) leaves them.  Deterministic rounding only, as iht_loop_one_matrix. */
+    void iht_loop_batch_one_matrix(CloverVector8 *const *x, const CloverVector8 *const *y, CloverVector8 *const *t1, CloverVector8 *const *t2,
+                                   CloverVector8 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    {
+        for (uint64_t j = 0; j < count; j++)
+            if (x[j]->size_pad() != getCols() || y[j]->size_pad() != getRows() || t1[j]->size_pad() != getRows() || t2[j]->size_pad() != getRows() ||
+                t3[j]->size_pad() != getCols() || x[j]->size() != x[0]->size()) {
+                std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+                exit(1);
+            }
+        const DevArrays8 py = dev_inputs8(y, count), px = dev_outputs8(x, count, false), p1 = dev_outputs8(t1, count, false),
+                         p2 = dev_outputs8(t2, count, false), p3 = dev_outputs8(t3, count, false);
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm4_iht_v8_batch_one_matrix(dev_values(), dev_scales(), rows, cols, count, px.q.data(), px.s.data(),
+                                                       count ? x[0]->size() : 0, py.q.data(), py.s.data(), p1.q.data(), p1.s.data(), p2.q.data(),
+                                                       p2.s.data(), p3.q.data(), p3.s.data(), iterations, K, mu, thr, nullptr, nullptr),
+                          "CloverMatrix4::iht_loop_batch_one_matrix");
+        for (uint64_t j = 0; j < count; j++) {
+            x[j]->commit();
+            if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }
+        }
+    }
+
+private:
+    /* the device pointers of `count` CloverVector8 as the batch calls take them: values and scales.  Inputs are mapped before outputs, as
+     * the single methods do; the pointers of inputs are stored without their const and handed on as const again (int8_t ** converts to
+     * const int8_t *const *) */
+    struct DevArrays8 {
+        std::vector<int8_t *> q;
+        std::vector<float *> s;
+    };
+    static DevArrays8 dev_inputs8(const CloverVector8 *const *v, uint64_t count)
+    {
+        DevArrays8 a;
+        for (uint64_t j = 0; j < count; j++) {
+            a.q.push_back(const_cast<int8_t *>(v[j]->dev_values_ro()));
+            a.s.push_back(const_cast<float *>(v[j]->dev_scales_ro()));
+        }
+        return a;
+    }
+    static DevArrays8 dev_outputs8(CloverVector8 *const *v, uint64_t count, bool read_too)
+    {
+        DevArrays8 a;
+        for (uint64_t j = 0; j < count; j++) {
+            a.q.push_back(read_too ? v[j]->dev_values_rw() : v[j]->dev_values_wo());
+            a.s.push_back(read_too ? v[j]->dev_scales_rw() : v[j]->dev_scales_wo());
+        }
+        return a;
+    }
+    void mvm_v8_transposed_batch_at_impl(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count, uint64_t draw_base,
+                                         uint64_t draw_stride, uint64_t commit_draws, bool positioned)
+    {
+        for (uint64_t j = 0; j < count; j++)
+            if (x[j]->size() != getRows() || r[j]->size_pad() != getCols()) {
+                std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+                exit(1);
+            }
+        const DevArrays8 px = dev_inputs8(x, count), pr = dev_outputs8(r, count, false);
+        uint64_t *rng = clover_hip::rng_or_null(random);
+        if (positioned)
+            clover_hip::check(clm4_mvm_v8_transposed_batch_at(dev_values(), dev_scales(), rows, cols, count, px.q.data(), px.s.data(), pr.q.data(),
+                                                              pr.s.data(), rng, draw_base, draw_stride, commit_draws, nullptr),
+                              "CloverMatrix4::mvm_transposed_batch_at");
+        else      /* the launcher may forward groups to the single calls where those were measured faster */
+            clover_hip::check(clm4_mvm_v8_transposed_batch(dev_values(), dev_scales(), rows, cols, count, px.q.data(), px.s.data(), pr.q.data(),
+                                                           pr.s.data(), rng, nullptr),
+                              "CloverMatrix4::mvm_transposed_batch");
+        for (uint64_t j = 0; j < count; j++) r[j]->commit();
+    }
+
+public:
 
     /* mixed precision: fp32 vector in, fp32 vector out (CloverMatrix4.h:1451-1547; _parallel :2397-2505) */
     void mvm(const CloverVector32 &productVector, CloverVector32 &resultVector)

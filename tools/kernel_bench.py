@@ -838,6 +838,95 @@ if any(selected(r) for r in MVT8_ROWS):
         sys.exit(0)
 
 
+# ---- A' x for several CloverVector8 straight from a CloverMatrix4 (mvm_t8_batch.hip): the rows of the MVTB_ROWS / M8TB_ROWS blocks for the
+# mixed pair.  Per row three calls from ONE session on the same matrix and vectors, their rounds ALTERNATED (rec_three): the batch call on
+# the batched kernel (CLV_MVM_BATCH=1), the same vectors as g single clm4_mvm_v8_transposed (clm4_mvm_v8_transposed_scale_and_add) calls, and
+# clm4_mvm_v8_batch (clm4_mvm_v8_scale_and_add_batch) on a held A'.  The *_st_* twins run with a generator.
+# m4_iht_v8_batch_one_matrix_N8192: clm4_iht_v8_batch_one_matrix against 8 x clm4_iht_v8_one_matrix and clm4_iht_v8_batch, ms per iteration
+# for 8 signals.  KB_ONLY=m4_mvm_v8_transposed_batch,m4_mvm_v8_transposed_saa_batch,m4_iht_v8_batch_one_matrix selects them and the run
+# ends after them.
+MVT8B_ROWS = tuple(f"m4_mvm_v8_transposed_batch{g}_{t}{nb}" for nb in (32768, 65536) for g in (2, 4, 8) for t in ("", "st_")) + \
+    tuple(f"m4_mvm_v8_transposed_saa_batch{g}_{t}{shape}" for shape in ("8192x4096", "65536^2") for g in (2, 4, 8) for t in ("", "st_")) + \
+    ("m4_iht_v8_batch_one_matrix_N8192", "m4_iht_v8_batch_one_matrix_st_N8192")
+
+if any(selected(r) for r in MVT8B_ROWS):
+    def mvt8b_rows(tag, rows, cols, reps):
+        """the plain rows (tag = the size) or the fused ones (tag = the shape's name) of one matrix of rows x cols"""
+        fusedf = not tag.isdigit()
+        stem = "m4_mvm_v8_transposed_saa_batch" if fusedf else "m4_mvm_v8_transposed_batch"
+        if not any(selected(f"{stem}{g}_{t}{tag}") for g in (2, 4, 8) for t in ("", "st_")):
+            return
+        tA, tsA, tAt, tsAt = (hip.alloc(rows * cols // 2), hip.alloc(4 * (rows // 64) * (cols // 64)), hip.alloc(rows * cols // 2),
+                              hip.alloc(4 * (rows // 64) * (cols // 64)))
+        hip.check(lib.clv_fill_random_nibbles(tA.ptr, tA.nbytes, 65, 0, None))
+        hip.check(lib.clv_fill_random_scales(tsA.ptr, tsA.nbytes // 4, 66, 0, None))
+        hip.check(lib.clm4_transpose(tA.ptr, tsA.ptr, rows, cols, tAt.ptr, tsAt.ptr, None))
+        vx, vu, vt, vr = vec8_set(8, rows, 330), vec8_set(8, cols, 340), vec8_set(8, cols, 350), vec8_set(8, cols, 360)
+        for g in (2, 4, 8):
+            a = {k: (ptrs([p[0] for p in v[:g]]), ptrs([p[1] for p in v[:g]])) for k, v in dict(x=vx, u=vu, t=vt, r=vr).items()}
+            for t, st in (("", None), ("st_", hip.new_rng(1, 2))):
+                sp = st.ptr if st else None
+                if fusedf:
+                    def singles(g=g, sp=sp):
+                        for j in range(g):
+                            hip.check(lib.clm4_mvm_v8_transposed_scale_and_add(tA.ptr, tsA.ptr, rows, cols, vx[j][0].ptr, vx[j][1].ptr, vu[j][0].ptr,
+                                                                               vu[j][1].ptr, 0.002, vt[j][0].ptr, vt[j][1].ptr, vr[j][0].ptr, vr[j][1].ptr, sp,
+                                                                               None))
+
+                    def batch(g=g, a=a, sp=sp):
+                        hip.check(lib.clm4_mvm_v8_transposed_scale_and_add_batch(tA.ptr, tsA.ptr, rows, cols, g, a["x"][0], a["x"][1], a["u"][0], a["u"][1],
+                                                                                 0.002, a["t"][0], a["t"][1], a["r"][0], a["r"][1], sp, None))
+
+                    def held(g=g, a=a, sp=sp):
+                        hip.check(lib.clm4_mvm_v8_scale_and_add_batch(tAt.ptr, tsAt.ptr, cols, rows, g, a["x"][0], a["x"][1], a["u"][0], a["u"][1], 0.002,
+                                                                      a["t"][0], a["t"][1], a["r"][0], a["r"][1], sp, None))
+                else:
+                    def singles(g=g, sp=sp):
+                        for j in range(g):
+                            hip.check(lib.clm4_mvm_v8_transposed(tA.ptr, tsA.ptr, rows, cols, vx[j][0].ptr, vx[j][1].ptr, vr[j][0].ptr, vr[j][1].ptr, sp, None))
+
+                    def batch(g=g, a=a, sp=sp):
+                        hip.check(lib.clm4_mvm_v8_transposed_batch(tA.ptr, tsA.ptr, rows, cols, g, a["x"][0], a["x"][1], a["r"][0], a["r"][1], sp, None))
+
+                    def held(g=g, a=a, sp=sp):
+                        hip.check(lib.clm4_mvm_v8_batch(tAt.ptr, tsAt.ptr, cols, rows, g, a["x"][0], a["x"][1], a["r"][0], a["r"][1], sp, None))
+                rec_three(f"{stem}{g}_{t}{tag}", g, singles, batch, held, reps)
+        del tA, tsA, tAt, tsAt
+
+    mvt8b_rows("32768", 32768, 32768, 10)
+    mvt8b_rows("65536", 65536, 65536, 4)
+    mvt8b_rows("8192x4096", 4096, 8192, 20)         # the IHT shape's step 2: Phi is 4096 x 8192, t3 = Phi' t2
+    mvt8b_rows("65536^2", 65536, 65536, 4)
+    im, inn, ig, iters = 4096, 8192, 8, 20
+    if selected("m4_iht_v8_batch_one_matrix_N8192") or selected("m4_iht_v8_batch_one_matrix_st_N8192"):
+        P, sP, PT, sPT = hip.alloc(im * inn // 2), hip.alloc(4 * (im // 64) * (inn // 64)), hip.alloc(im * inn // 2), hip.alloc(4 * (im // 64) * (inn // 64))
+        hip.check(lib.clv_fill_random_nibbles(P.ptr, P.nbytes, 67, 0, None))
+        hip.check(lib.clv_fill_random_scales(sP.ptr, sP.nbytes // 4, 68, 0, None))
+        hip.check(lib.clm4_transpose(P.ptr, sP.ptr, im, inn, PT.ptr, sPT.ptr, None))
+        vy, vx, vt1, vt2, vt3 = vec8_set(ig, im, 500), vec8_set(ig, inn, 600), vec8_set(ig, im, 700), vec8_set(ig, im, 800), vec8_set(ig, inn, 900)
+        A = {k: (ptrs([p[0] for p in v]), ptrs([p[1] for p in v])) for k, v in dict(y=vy, x=vx, t1=vt1, t2=vt2, t3=vt3).items()}
+        for t, st in (("", None), ("st_", hip.new_rng(1, 2))):
+            sp = st.ptr if st else None
+            tail = (im, inn, ig, A["x"][0], A["x"][1], inn, A["y"][0], A["y"][1], A["t1"][0], A["t1"][1], A["t2"][0], A["t2"][1], A["t3"][0], A["t3"][1],
+                    iters, im // 4, 0.002, 1, sp, None)
+
+            def singles(sp=sp):
+                for j in range(ig):
+                    hip.check(lib.clm4_iht_v8_one_matrix(P.ptr, sP.ptr, im, inn, vx[j][0].ptr, vx[j][1].ptr, inn, vy[j][0].ptr, vy[j][1].ptr, vt1[j][0].ptr,
+                                                         vt1[j][1].ptr, vt2[j][0].ptr, vt2[j][1].ptr, vt3[j][0].ptr, vt3[j][1].ptr, iters, im // 4, 0.002, 1,
+                                                         sp, None))
+            name = f"m4_iht_v8_batch_one_matrix_{t}N8192"
+            rec_three(name, ig, singles, lambda tail=tail: hip.check(lib.clm4_iht_v8_batch_one_matrix(P.ptr, sP.ptr, *tail)),
+                      lambda tail=tail: hip.check(lib.clm4_iht_v8_batch(P.ptr, sP.ptr, PT.ptr, sPT.ptr, *tail)), reps=2, per=iters)
+            if name in res:
+                res[name]["note"] = (f"ms per iteration for all 8 signals, calls of {iters} iterations, K = m / 4, FAST threshold; the single calls are "
+                                     "8 x clm4_iht_v8_one_matrix, the held-transpose column is clm4_iht_v8_batch under CLV_MVM_BATCH=1")
+        del P, sP, PT, sPT, vy, vx, vt1, vt2, vt3
+    if ONLY and all(any(o in r for r in MVT8B_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
+
+
 # ---- A' x for a CloverMatrix8 straight from A (matrix8_t.hip): the three rows per size of the two blocks above with clm8_mvm_transposed,
 # clm8_transpose + clm8_mvm and clm8_mvm on a held A', rounds alternated in one session; m8_iht_one_matrix_*: clm8_iht_one_matrix against clm8_iht
 # (launch per step either way: no persistent kernel at this width).
