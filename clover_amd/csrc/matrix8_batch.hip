@@ -195,39 +195,23 @@ struct M8Batch : MvmBatchByRows {
 extern "C" int clm8_mvm_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
                               const float *const *sx, int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, void *stream)
 {
-    int rc = mvm_batch_check_args<M8Batch>("clm8_mvm_batch", A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
-    if (rc) return rc;
-    if (!nvec || !rows) return CLV_OK;
-    if (nvec == 1) return clm8_mvm(A, sA, rows, cols, x[0], sx[0], r[0], sr[0], rng_state_dev, stream);
-    return mvm_batch_run<M8Batch>(A, sA, rows, cols, nvec, {x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr}, rng_state_dev, stream);
+    return mvm_batch_entry<M8Batch>("clm8_mvm_batch", A, sA, rows, cols, nvec, x, sx, r, sr, rng_state_dev, stream);
 }
 
 extern "C" int clm8_mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
                                  const float *const *sx, int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, uint64_t draw_base,
                                  uint64_t draw_stride, uint64_t commit_draws, void *stream)
 {
-    const char *fn = "clm8_mvm_batch_at";
-    int rc = mvm_batch_check_args<M8Batch>(fn, A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
-    if (rc) return rc;
-    if (!rng_state_dev) return clm8_mvm_batch(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, stream);
-    rc = mvm_batch_check_draws(fn, rows, nvec, draw_base, draw_stride, commit_draws);
-    if (rc) return rc;
-    if (!nvec || !rows) return CLV_OK;
-    return mvm_batch_at<M8Batch>(A, sA, rows, cols, nvec, {x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr}, rng_state_dev, draw_base, draw_stride,
-                                 commit_draws, stream);
+    return mvm_batch_at_entry<M8Batch>("clm8_mvm_batch_at", "clm8_mvm_batch", A, sA, rows, cols, nvec, x, sx, r, sr,
+                                       rng_state_dev, draw_base, draw_stride, commit_draws, stream);
 }
 
 extern "C" int clm8_mvm_scale_and_add_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
                                             const float *const *sx, const int8_t *const *qu, const float *const *su, float a, int8_t *const *t,
                                             float *const *st_, int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, void *stream)
 {
-    int rc = mvm_batch_check_args<M8Batch>("clm8_mvm_scale_and_add_batch", A, sA, rows, cols, nvec, x, sx, qu, su, t, st_, r, sr, true);
-    if (rc) return rc;
-    if (!nvec || !rows) return CLV_OK;
-    if (nvec == 1)
-        return clm8_mvm_scale_and_add(A, sA, rows, cols, x[0], sx[0], qu[0], su[0], a, t ? t[0] : nullptr, t ? st_[0] : nullptr, r[0], sr[0],
-                                      rng_state_dev, stream);
-    return mvm_batch_run<M8Batch>(A, sA, rows, cols, nvec, {x, sx, t, st_, qu, su, a, r, sr}, rng_state_dev, stream);
+    return mvm_batch_fused_entry<M8Batch>("clm8_mvm_scale_and_add_batch", A, sA, rows, cols, nvec, x, sx, qu, su, a, t, st_, r, sr,
+                                          rng_state_dev, stream);
 }
 
 extern "C" int clm8_iht_batch(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, uint64_t nvec,

@@ -192,26 +192,15 @@ struct Mvm8Batch : MvmBatchByRows {
 extern "C" int clm4_mvm_v8_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
                                  const float *const *sx, int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, void *stream)
 {
-    int rc = mvm_batch_check_args<Mvm8Batch>("clm4_mvm_v8_batch", A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
-    if (rc) return rc;
-    if (!nvec || !rows) return CLV_OK;
-    if (nvec == 1) return clm4_mvm_v8(A, sA, rows, cols, x[0], sx[0], r[0], sr[0], rng_state_dev, stream);
-    return mvm_batch_run<Mvm8Batch>(A, sA, rows, cols, nvec, {x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr}, rng_state_dev, stream);
+    return mvm_batch_entry<Mvm8Batch>("clm4_mvm_v8_batch", A, sA, rows, cols, nvec, x, sx, r, sr, rng_state_dev, stream);
 }
 
 extern "C" int clm4_mvm_v8_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
                                     const float *const *sx, int8_t *const *r, float *const *sr, uint64_t *rng_state_dev, uint64_t draw_base,
                                     uint64_t draw_stride, uint64_t commit_draws, void *stream)
 {
-    const char *fn = "clm4_mvm_v8_batch_at";
-    int rc = mvm_batch_check_args<Mvm8Batch>(fn, A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
-    if (rc) return rc;
-    if (!rng_state_dev) return clm4_mvm_v8_batch(A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, stream);
-    rc = mvm_batch_check_draws(fn, rows, nvec, draw_base, draw_stride, commit_draws);
-    if (rc) return rc;
-    if (!nvec || !rows) return CLV_OK;
-    return mvm_batch_at<Mvm8Batch>(A, sA, rows, cols, nvec, {x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr}, rng_state_dev, draw_base,
-                                   draw_stride, commit_draws, stream);
+    return mvm_batch_at_entry<Mvm8Batch>("clm4_mvm_v8_batch_at", "clm4_mvm_v8_batch", A, sA, rows, cols, nvec, x, sx, r, sr,
+                                         rng_state_dev, draw_base, draw_stride, commit_draws, stream);
 }
 
 extern "C" int clm4_mvm_v8_scale_and_add_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
@@ -219,13 +208,8 @@ extern "C" int clm4_mvm_v8_scale_and_add_batch(const int8_t *A, const float *sA,
                                                float a, int8_t *const *t, float *const *st_, int8_t *const *r, float *const *sr,
                                                uint64_t *rng_state_dev, void *stream)
 {
-    int rc = mvm_batch_check_args<Mvm8Batch>("clm4_mvm_v8_scale_and_add_batch", A, sA, rows, cols, nvec, x, sx, qu, su, t, st_, r, sr, true);
-    if (rc) return rc;
-    if (!nvec || !rows) return CLV_OK;
-    if (nvec == 1)
-        return clm4_mvm_v8_scale_and_add(A, sA, rows, cols, x[0], sx[0], qu[0], su[0], a, t ? t[0] : nullptr, t ? st_[0] : nullptr, r[0], sr[0],
-                                         rng_state_dev, stream);
-    return mvm_batch_run<Mvm8Batch>(A, sA, rows, cols, nvec, {x, sx, t, st_, qu, su, a, r, sr}, rng_state_dev, stream);
+    return mvm_batch_fused_entry<Mvm8Batch>("clm4_mvm_v8_scale_and_add_batch", A, sA, rows, cols, nvec, x, sx, qu, su, a, t, st_, r, sr,
+                                            rng_state_dev, stream);
 }
 
 extern "C" int clm4_iht_v8_batch(const int8_t *Phi, const float *sPhi, const int8_t *PhiT, const float *sPhiT, uint64_t m, uint64_t n, uint64_t nvec,

@@ -14,6 +14,9 @@
 //   launch<NV, NT, FUSE, ST>(...)             the hipLaunchKernelGGL of the family's kernel, with its U and LDS bytes
 //   x_len, r_len, grid, batched_by_rule       which dimension sizes x and which r, the grid of a launch and the measured dispatch rule:
 //                                             MvmBatchByRows (below) for the three families that walk the matrix by rows
+//   nothing_to_do(nvec, rows, cols)           the empty-call rule of the three mvm batch entry points: checked arguments, no device work
+// The extern "C" mvm batch entry points of a family forward to mvm_batch_entry, mvm_batch_at_entry and mvm_batch_fused_entry (below) with
+// their own names, which the messages quote.
 #pragma once
 
 #include "mvm_batch_device.h"
@@ -37,6 +40,7 @@ struct MvmBatchByRows {
     static uint64_t r_len(uint64_t rows, uint64_t) { return rows; }
     static dim3 grid(uint64_t rows, uint64_t) { return dim3((unsigned)(rows / 64)); }
     static bool batched_by_rule(uint64_t g, uint64_t, uint64_t, bool, bool) { return g >= 2; }
+    static bool nothing_to_do(uint64_t nvec, uint64_t rows, uint64_t) { return !nvec || !rows; }
 };
 
 // Whether a group of g vectors runs as one batched launch or as g single launches.  Forced to 1, with an rng a remainder group of ONE vector
@@ -186,7 +190,7 @@ static int mvm_batch_at(const int8_t *A, const float *sA, uint64_t rows, uint64_
 }
 
 // the positions of a *_mvm_batch_at call with a generator: everything below 2^55, the exponents the jump-ahead has table levels for.
-// rows = the elements of a result (the transposed family passes its columns)
+// rows = the elements of a result, F::r_len(rows, cols)
 static inline int mvm_batch_check_draws(const char *fn, uint64_t rows, uint64_t nvec, uint64_t draw_base, uint64_t draw_stride, uint64_t commit_draws)
 {
     CLV_REQUIRE(commit_draws < (1ull << (RNG_POW_LEVELS - 1)), "%s: commit_draws=%llu must stay below 2^55", fn, (unsigned long long)commit_draws);
@@ -240,6 +244,49 @@ static int mvm_batch_check_args(const char *fn, const int8_t *A, const float *sA
         }
     }
     return clv_internal_check_ranges(fn, rg);
+}
+
+// ---- the bodies of a family's three extern "C" mvm batch entry points; fn = the name of the entry point that was called -----------------
+// *_batch: r[j] = quantize(A x[j]) (the transposed families: A' x[j]); one vector is the single call
+template <class F>
+static int mvm_batch_entry(const char *fn, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
+                           const float *const *sx, int8_t *const *r, float *const *sr, uint64_t *rng, void *stream)
+{
+    int rc = mvm_batch_check_args<F>(fn, A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
+    if (rc) return rc;
+    if (F::nothing_to_do(nvec, rows, cols)) return CLV_OK;
+    if (nvec == 1) return F::mvm(A, sA, rows, cols, x[0], sx[0], r[0], sr[0], rng, stream);
+    return mvm_batch_run<F>(A, sA, rows, cols, nvec, {x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr}, rng, stream);
+}
+
+// *_batch_at: the same with the place of every vector's draws chosen by the caller; without an rng it is the plain call, fn_plain
+template <class F>
+static int mvm_batch_at_entry(const char *fn, const char *fn_plain, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec,
+                              const int8_t *const *x, const float *const *sx, int8_t *const *r, float *const *sr, uint64_t *rng, uint64_t draw_base,
+                              uint64_t draw_stride, uint64_t commit_draws, void *stream)
+{
+    int rc = mvm_batch_check_args<F>(fn, A, sA, rows, cols, nvec, x, sx, nullptr, nullptr, nullptr, nullptr, r, sr, false);
+    if (rc) return rc;
+    if (!rng) return mvm_batch_entry<F>(fn_plain, A, sA, rows, cols, nvec, x, sx, r, sr, nullptr, stream);
+    rc = mvm_batch_check_draws(fn, F::r_len(rows, cols), nvec, draw_base, draw_stride, commit_draws);
+    if (rc) return rc;
+    if (F::nothing_to_do(nvec, rows, cols)) return CLV_OK;
+    return mvm_batch_at<F>(A, sA, rows, cols, nvec, {x, sx, r, sr, nullptr, nullptr, 0.0f, nullptr, nullptr}, rng, draw_base, draw_stride,
+                           commit_draws, stream);
+}
+
+// *_scale_and_add_batch: t[j] = quantize(A x[j]) (stored if t != NULL), r[j] = quantize(qu[j] + a * t[j]); one vector is the single call
+template <class F>
+static int mvm_batch_fused_entry(const char *fn, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,
+                                 const float *const *sx, const int8_t *const *qu, const float *const *su, float a, int8_t *const *t,
+                                 float *const *st_, int8_t *const *r, float *const *sr, uint64_t *rng, void *stream)
+{
+    int rc = mvm_batch_check_args<F>(fn, A, sA, rows, cols, nvec, x, sx, qu, su, t, st_, r, sr, true);
+    if (rc) return rc;
+    if (F::nothing_to_do(nvec, rows, cols)) return CLV_OK;
+    if (nvec == 1)
+        return F::scale_and_add(A, sA, rows, cols, x[0], sx[0], qu[0], su[0], a, t ? t[0] : nullptr, t ? st_[0] : nullptr, r[0], sr[0], rng, stream);
+    return mvm_batch_run<F>(A, sA, rows, cols, nvec, {x, sx, t, st_, qu, su, a, r, sr}, rng, stream);
 }
 
 // Q_IHT / Q_GD for nvec signals with one Phi: the loop of the family's single call F::iht with every step batched.  Arrays are HOST arrays

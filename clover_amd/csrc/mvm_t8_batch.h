@@ -29,6 +29,8 @@ struct MvmT8Batch {
         CLV_REQUIRE(rows / 64 <= 0x7FFFFFFFull, "%s: too many rows", fn);
         return CLV_OK;
     }
+    // a matrix without rows has nothing to multiply, one without columns nothing to write
+    static bool nothing_to_do(uint64_t nvec, uint64_t rows, uint64_t cols) { return !nvec || !rows || !cols; }
     static bool result_may_not_alias_x(bool) { return false; }
     static constexpr auto mvm = clm4_mvm_v8_transposed;
     static constexpr auto scale_and_add = clm4_mvm_v8_transposed_scale_and_add;

@@ -44,7 +44,7 @@
 #include "CloverMatrix32.h"
 #include "CloverVector32.h"
 #include "CloverVector8.h"
-#include "clover_hip_batch_t8.h"   /* the batched transposed calls: a header of their own beside clover_hip.h */
+#include "clover_batch.h"          /* what the batch methods share with CloverMatrix4's: the marshalling into the batched C calls */
 
 class CloverMatrix4;
 
@@ -59,6 +59,14 @@ protected:
 
     const int8_t *dev_values() const { return reinterpret_cast<const int8_t *>(mem.dev_ro()); }
     const float *dev_scales() const { return reinterpret_cast<const float *>(mem.dev_ro() + value_bytes); }
+    /* the bodies of the batch methods (clover_batch.h) and this matrix as they take it */
+    typedef clover_hip::Batch<CloverMatrix8, clover_hip::BATCH_FORWARD> BatchForward;
+    typedef clover_hip::Batch<CloverMatrix8, clover_hip::BATCH_TRANSPOSED> BatchTransposed;
+    clover_hip::BatchMatrix batch_view() const
+    {
+        const clover_hip::BatchMatrix m = {dev_values(), dev_scales(), rows, cols};
+        return m;
+    }
 
     void check_same_size(const CloverMatrix32 &m) const
     {
@@ -330,7 +338,7 @@ public:
      * one pass: the kernel jumps to every vector's place in the stream -- and the generator ends where those calls leave it. */
     void mvm_batch(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count)
     {
-        mvm_batch_at_impl(x, r, count, 0, 2 * (rows >> 6), count * 2 * (rows >> 6), false);
+        BatchForward::mvm(batch_view(), x, r, count, clover_hip::rng_or_null(random), false, 0, 0, 0, "CloverMatrix8::mvm_batch");
     }
     /* mvm_batch with the place of every vector's draws chosen by the caller (clm8_mvm_batch_at), counted in draws -- mvm consumes
      * 2 (rows / 64) -- from where the matrix's generator stands: vector j draws from draw_base + j * draw_stride on, and the generator is
@@ -339,7 +347,8 @@ public:
     void mvm_batch_at(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
                       uint64_t commit_draws)
     {
-        mvm_batch_at_impl(x, r, count, draw_base, draw_stride, commit_draws, true);
+        BatchForward::mvm(batch_view(), x, r, count, clover_hip::rng_or_null(random), true, draw_base, draw_stride, commit_draws,
+                          "CloverMatrix8::mvm_batch_at");
     }
     /* mvm_scaleAndAdd for `count` vectors: t[j] = this * x[j], r[j] = quantize(u[j] + a * t[j]).  Rounding disabled: one launch per group
      * (clm8_mvm_scale_and_add_batch).  Stochastic: the mvm draws from the matrix's generator and every scaleAndAdd from its u[j]'s own, so
@@ -347,32 +356,10 @@ public:
     void mvm_scaleAndAdd_batch(const CloverVector8 *const *x, const CloverVector8 *const *u, float a, CloverVector8 *const *t,
                                CloverVector8 *const *r, uint64_t count)
     {
-        for (uint64_t j = 0; j < count; j++) {
-            check_fused(*x[j], *u[j], *t[j]);
-            if (r[j]->size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
-        }
 #ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
-        std::vector<const int8_t *> px(count), pu(count);
-        std::vector<const float *> psx(count), psu(count);
-        std::vector<int8_t *> pt(count), pr(count);
-        std::vector<float *> pst(count), psr(count);
-        for (uint64_t j = 0; j < count; j++) {
-            px[j] = x[j]->dev_values_ro();
-            psx[j] = x[j]->dev_scales_ro();
-            pu[j] = u[j]->dev_values_ro();
-            psu[j] = u[j]->dev_scales_ro();
-        }
-        for (uint64_t j = 0; j < count; j++) {
-            pt[j] = t[j]->dev_values_wo();
-            pst[j] = t[j]->dev_scales_wo();
-            pr[j] = r[j]->dev_values_wo();
-            psr[j] = r[j]->dev_scales_wo();
-        }
-        clover_hip::check(clm8_mvm_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(), psu.data(), a,
-                                                       pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
-                          "CloverMatrix8::mvm_scaleAndAdd_batch");
-        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
+        BatchForward::fused(batch_view(), x, u, a, t, r, count, "CloverMatrix8::mvm_scaleAndAdd_batch");
 #else
+        clover_hip::batch_check_fused<CloverVector8>(cols, rows, x, u, t, r, count);
         mvm_batch(x, t, count);
         for (uint64_t j = 0; j < count; j++) const_cast<CloverVector8 *>(u[j])->scaleAndAdd(*t[j], a, *r[j]);
 #endif
@@ -380,27 +367,10 @@ public:
     /* in place: u[j] = quantize(u[j] + a * (this * x[j])) */
     void mvm_scaleAndAdd_batch(const CloverVector8 *const *x, CloverVector8 *const *u, float a, CloverVector8 *const *t, uint64_t count)
     {
-        for (uint64_t j = 0; j < count; j++) check_fused(*x[j], *u[j], *t[j]);
 #ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
-        std::vector<const int8_t *> px(count), pu(count);
-        std::vector<const float *> psx(count), psu(count);
-        std::vector<int8_t *> pt(count), pr(count);
-        std::vector<float *> pst(count), psr(count);
-        for (uint64_t j = 0; j < count; j++) {
-            px[j] = x[j]->dev_values_ro();
-            psx[j] = x[j]->dev_scales_ro();
-        }
-        for (uint64_t j = 0; j < count; j++) {
-            pu[j] = pr[j] = u[j]->dev_values_rw();
-            psu[j] = psr[j] = u[j]->dev_scales_rw();
-            pt[j] = t[j]->dev_values_wo();
-            pst[j] = t[j]->dev_scales_wo();
-        }
-        clover_hip::check(clm8_mvm_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pu.data(), psu.data(), a,
-                                                       pt.data(), pst.data(), pr.data(), psr.data(), nullptr, nullptr),
-                          "CloverMatrix8::mvm_scaleAndAdd_batch");
-        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
+        BatchForward::fused_in_place(batch_view(), x, u, a, t, count, "CloverMatrix8::mvm_scaleAndAdd_batch");
 #else
+        clover_hip::batch_check_fused<CloverVector8>(cols, rows, x, u, t, nullptr, count);
         mvm_batch(x, t, count);
         for (uint64_t j = 0; j < count; j++) u[j]->scaleAndAdd(*t[j], a);
 #endif
@@ -411,38 +381,8 @@ public:
                         CloverVector8 *const *t2, CloverVector8 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu,
                         bool with_threshold)
     {
-        std::vector<const int8_t *> py(count);
-        std::vector<const float *> psy(count);
-        std::vector<int8_t *> px(count), p1(count), p2(count), p3(count);
-        std::vector<float *> psx(count), ps1(count), ps2(count), ps3(count);
-        for (uint64_t j = 0; j < count; j++) {
-            if (PhiT.getRows() != getCols() || PhiT.getCols() != getRows() || x[j]->size_pad() != getCols() || y[j]->size_pad() != getRows() ||
-                t1[j]->size_pad() != getRows() || t2[j]->size_pad() != getRows() || t3[j]->size_pad() != getCols() || x[j]->size() != x[0]->size()) {
-                std::cout << "MVM can not be performed. Exiting ..." << std::endl;
-                exit(1);
-            }
-            py[j] = y[j]->dev_values_ro();
-            psy[j] = y[j]->dev_scales_ro();
-        }
-        for (uint64_t j = 0; j < count; j++) {
-            px[j] = x[j]->dev_values_wo();
-            psx[j] = x[j]->dev_scales_wo();
-            p1[j] = t1[j]->dev_values_wo();
-            ps1[j] = t1[j]->dev_scales_wo();
-            p2[j] = t2[j]->dev_values_wo();
-            ps2[j] = t2[j]->dev_scales_wo();
-            p3[j] = t3[j]->dev_values_wo();
-            ps3[j] = t3[j]->dev_scales_wo();
-        }
-        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
-        clover_hip::check(clm8_iht_batch(dev_values(), dev_scales(), PhiT.dev_values(), PhiT.dev_scales(), rows, cols, count, px.data(), psx.data(),
-                                         count ? x[0]->size() : 0, py.data(), psy.data(), p1.data(), ps1.data(), p2.data(), ps2.data(), p3.data(),
-                                         ps3.data(), iterations, K, mu, thr, nullptr, nullptr),
-                          "CloverMatrix8::iht_loop_batch");
-        for (uint64_t j = 0; j < count; j++) {
-            x[j]->commit();
-            if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }
-        }
+        BatchForward::iht_loop(batch_view(), PhiT.batch_view(), x, y, t1, t2, t3, count, iterations, K, mu, with_threshold,
+                               "CloverMatrix8::iht_loop_batch");
     }
     /* Not in the reference: this' * x[j] for `count` vectors in ONE pass over this matrix's own bytes per group of CLM4_MVM_BATCH_MAX
      * (clm8_mvm_transposed_batch, clover_hip_batch_t8.h); r[j] equals what mvm_transposed(*x[j], *r[j]) gives, bit for bit.  The x[j] may
@@ -450,7 +390,7 @@ public:
      * generator one after another, as the single calls in order do, and the generator ends where those calls leave it. */
     void mvm_transposed_batch(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count)
     {
-        mvm_transposed_batch_at_impl(x, r, count, 0, 0, 0, false);
+        BatchTransposed::mvm(batch_view(), x, r, count, clover_hip::rng_or_null(random), false, 0, 0, 0, "CloverMatrix8::mvm_transposed_batch");
     }
     /* mvm_transposed_batch with the place of every vector's draws chosen by the caller (clm8_mvm_transposed_batch_at), counted in draws --
      * mvm_transposed consumes 2 (cols / 64) -- from where the matrix's generator stands: vector j draws from draw_base + j * draw_stride on,
@@ -459,7 +399,8 @@ public:
     void mvm_transposed_batch_at(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
                                  uint64_t commit_draws)
     {
-        mvm_transposed_batch_at_impl(x, r, count, draw_base, draw_stride, commit_draws, true);
+        BatchTransposed::mvm(batch_view(), x, r, count, clover_hip::rng_or_null(random), true, draw_base, draw_stride, commit_draws,
+                             "CloverMatrix8::mvm_transposed_batch_at");
     }
     /* mvm_transposed_scaleAndAdd for `count` vectors: t[j] = this' * x[j], r[j] = quantize(u[j] + a * t[j]).  Rounding disabled: one launch
      * per group (clm8_mvm_transposed_scale_and_add_batch).  Stochastic: one mvm_transposed_batch and the scaleAndAdd calls, which draw from
@@ -467,17 +408,10 @@ public:
     void mvm_transposed_scaleAndAdd_batch(const CloverVector8 *const *x, const CloverVector8 *const *u, float a, CloverVector8 *const *t,
                                           CloverVector8 *const *r, uint64_t count)
     {
-        for (uint64_t j = 0; j < count; j++) {
-            check_fused_transposed(*x[j], *u[j], *t[j]);
-            if (r[j]->size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
-        }
 #ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
-        const DevArrays px = dev_inputs(x, count), pu = dev_inputs(u, count), pt = dev_outputs(t, count, false), pr = dev_outputs(r, count, false);
-        clover_hip::check(clm8_mvm_transposed_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.q.data(), px.s.data(), pu.q.data(),
-                                                                  pu.s.data(), a, pt.q.data(), pt.s.data(), pr.q.data(), pr.s.data(), nullptr, nullptr),
-                          "CloverMatrix8::mvm_transposed_scaleAndAdd_batch");
-        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
+        BatchTransposed::fused(batch_view(), x, u, a, t, r, count, "CloverMatrix8::mvm_transposed_scaleAndAdd_batch");
 #else
+        clover_hip::batch_check_fused<CloverVector8>(rows, cols, x, u, t, r, count);
         mvm_transposed_batch(x, t, count);
         for (uint64_t j = 0; j < count; j++) const_cast<CloverVector8 *>(u[j])->scaleAndAdd(*t[j], a, *r[j]);
 #endif
@@ -485,14 +419,10 @@ public:
     /* in place: u[j] = quantize(u[j] + a * (this' * x[j])) */
     void mvm_transposed_scaleAndAdd_batch(const CloverVector8 *const *x, CloverVector8 *const *u, float a, CloverVector8 *const *t, uint64_t count)
     {
-        for (uint64_t j = 0; j < count; j++) check_fused_transposed(*x[j], *u[j], *t[j]);
 #ifdef CLOVER_STOCHASTIC_ROUNDING_DISABLED
-        const DevArrays px = dev_inputs(x, count), pu = dev_outputs(u, count, true), pt = dev_outputs(t, count, false);
-        clover_hip::check(clm8_mvm_transposed_scale_and_add_batch(dev_values(), dev_scales(), rows, cols, count, px.q.data(), px.s.data(), pu.q.data(),
-                                                                  pu.s.data(), a, pt.q.data(), pt.s.data(), pu.q.data(), pu.s.data(), nullptr, nullptr),
-                          "CloverMatrix8::mvm_transposed_scaleAndAdd_batch");
-        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
+        BatchTransposed::fused_in_place(batch_view(), x, u, a, t, count, "CloverMatrix8::mvm_transposed_scaleAndAdd_batch");
 #else
+        clover_hip::batch_check_fused<CloverVector8>(rows, cols, x, u, t, nullptr, count);
         mvm_transposed_batch(x, t, count);
         for (uint64_t j = 0; j < count; j++) u[j]->scaleAndAdd(*t[j], a);
 #endif
@@ -503,101 +433,10 @@ public:
     void iht_loop_batch_one_matrix(CloverVector8 *const *x, const CloverVector8 *const *y, CloverVector8 *const *t1, CloverVector8 *const *t2,
                                    CloverVector8 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu, bool with_threshold)
     {
-        for (uint64_t j = 0; j < count; j++)
-            if (x[j]->size_pad() != getCols() || y[j]->size_pad() != getRows() || t1[j]->size_pad() != getRows() || t2[j]->size_pad() != getRows() ||
-                t3[j]->size_pad() != getCols() || x[j]->size() != x[0]->size()) {
-                std::cout << "MVM can not be performed. Exiting ..." << std::endl;
-                exit(1);
-            }
-        const DevArrays py = dev_inputs(y, count), px = dev_outputs(x, count, false), p1 = dev_outputs(t1, count, false),
-                        p2 = dev_outputs(t2, count, false), p3 = dev_outputs(t3, count, false);
-        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
-        clover_hip::check(clm8_iht_batch_one_matrix(dev_values(), dev_scales(), rows, cols, count, px.q.data(), px.s.data(), count ? x[0]->size() : 0,
-                                                    py.q.data(), py.s.data(), p1.q.data(), p1.s.data(), p2.q.data(), p2.s.data(), p3.q.data(),
-                                                    p3.s.data(), iterations, K, mu, thr, nullptr, nullptr),
-                          "CloverMatrix8::iht_loop_batch_one_matrix");
-        for (uint64_t j = 0; j < count; j++) {
-            x[j]->commit();
-            if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }
-        }
+        BatchTransposed::iht_loop(batch_view(), clover_hip::no_transpose(), x, y, t1, t2, t3, count, iterations, K, mu, with_threshold,
+                                  "CloverMatrix8::iht_loop_batch_one_matrix");
     }
 
-private:
-    /* the device pointers of `count` vectors as the batch calls take them: values and scales.  Inputs are mapped before outputs, as the
-     * single methods do; the pointers of inputs are stored without their const and handed on as const again (int8_t ** converts to
-     * const int8_t *const *) */
-    struct DevArrays {
-        std::vector<int8_t *> q;
-        std::vector<float *> s;
-    };
-    static DevArrays dev_inputs(const CloverVector8 *const *v, uint64_t count)
-    {
-        DevArrays a;
-        for (uint64_t j = 0; j < count; j++) {
-            a.q.push_back(const_cast<int8_t *>(v[j]->dev_values_ro()));
-            a.s.push_back(const_cast<float *>(v[j]->dev_scales_ro()));
-        }
-        return a;
-    }
-    static DevArrays dev_outputs(CloverVector8 *const *v, uint64_t count, bool read_too)
-    {
-        DevArrays a;
-        for (uint64_t j = 0; j < count; j++) {
-            a.q.push_back(read_too ? v[j]->dev_values_rw() : v[j]->dev_values_wo());
-            a.s.push_back(read_too ? v[j]->dev_scales_rw() : v[j]->dev_scales_wo());
-        }
-        return a;
-    }
-    void check_fused(const CloverVector8 &x, const CloverVector8 &u, const CloverVector8 &t) const
-    {
-        if (x.size() != getCols() || t.size_pad() != getRows()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
-        if (u.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
-    }
-    void mvm_batch_at_impl(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count, uint64_t draw_base, uint64_t draw_stride,
-                           uint64_t commit_draws, bool positioned)
-    {
-        std::vector<const int8_t *> px(count);
-        std::vector<const float *> psx(count);
-        std::vector<int8_t *> pr(count);
-        std::vector<float *> psr(count);
-        for (uint64_t j = 0; j < count; j++) {
-            check_mvm(*x[j], *r[j]);
-            px[j] = x[j]->dev_values_ro();
-            psx[j] = x[j]->dev_scales_ro();
-        }
-        for (uint64_t j = 0; j < count; j++) { pr[j] = r[j]->dev_values_wo(); psr[j] = r[j]->dev_scales_wo(); }
-        uint64_t *rng = clover_hip::rng_or_null(random);
-        if (positioned)
-            clover_hip::check(clm8_mvm_batch_at(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng,
-                                                draw_base, draw_stride, commit_draws, nullptr), "CloverMatrix8::mvm_batch_at");
-        else      /* the launcher may forward groups to the single calls where those were measured faster */
-            clover_hip::check(clm8_mvm_batch(dev_values(), dev_scales(), rows, cols, count, px.data(), psx.data(), pr.data(), psr.data(), rng, nullptr),
-                              "CloverMatrix8::mvm_batch");
-        for (uint64_t j = 0; j < count; j++) r[j]->commit();
-    }
-
-    void mvm_transposed_batch_at_impl(const CloverVector8 *const *x, CloverVector8 *const *r, uint64_t count, uint64_t draw_base,
-                                      uint64_t draw_stride, uint64_t commit_draws, bool positioned)
-    {
-        for (uint64_t j = 0; j < count; j++)
-            if (x[j]->size() != getRows() || r[j]->size_pad() != getCols()) {
-                std::cout << "MVM can not be performed. Exiting ..." << std::endl;
-                exit(1);
-            }
-        const DevArrays px = dev_inputs(x, count), pr = dev_outputs(r, count, false);
-        uint64_t *rng = clover_hip::rng_or_null(random);
-        if (positioned)
-            clover_hip::check(clm8_mvm_transposed_batch_at(dev_values(), dev_scales(), rows, cols, count, px.q.data(), px.s.data(), pr.q.data(),
-                                                           pr.s.data(), rng, draw_base, draw_stride, commit_draws, nullptr),
-                              "CloverMatrix8::mvm_transposed_batch_at");
-        else      /* the launcher may forward groups to the single calls where those were measured faster */
-            clover_hip::check(clm8_mvm_transposed_batch(dev_values(), dev_scales(), rows, cols, count, px.q.data(), px.s.data(), pr.q.data(),
-                                                        pr.s.data(), rng, nullptr),
-                              "CloverMatrix8::mvm_transposed_batch");
-        for (uint64_t j = 0; j < count; j++) r[j]->commit();
-    }
-
-public:
     /* :480-548: every row wrapped in a non-owning CloverVector8 view over the matrix's own memory and multiplied with dot() (the
      * reference's order), then 64 results at a time quantised by scalar code -- an implementation independent of the mvm kernel */
     void mvm_scalar(const CloverVector8 &productVector, CloverVector8 &resultVector)

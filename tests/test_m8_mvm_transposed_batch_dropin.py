@@ -27,17 +27,22 @@ def _flags(det, explicit):
             *(["-DCLOVER_HIP_EXPLICIT_SYNC"] if explicit else []), f"-I{ROOT / 'include'}"]
 
 
+# the client of the three transposed batch families is one source; the classes of this family:
+CLIENT = ROOT / "tests" / "cpp" / "mvm_transposed_batch_dropin.cpp"
+CLASSES = ["-DDROPIN_MATRIX=CloverMatrix8", "-DDROPIN_VECTOR=CloverVector8"]
+
+
 def _build(tmp_path, det, explicit):
     lib = build_hip_library()
     exe = tmp_path / f"m8_mvm_transposed_batch_dropin_{int(det)}{int(explicit)}"
-    subprocess.run([*_flags(det, explicit), str(ROOT / "tests" / "cpp" / "m8_mvm_transposed_batch_dropin.cpp"), "-o", str(exe), f"-L{lib.parent}",
+    subprocess.run([*_flags(det, explicit), *CLASSES, str(CLIENT), "-o", str(exe), f"-L{lib.parent}",
                     "-lclover_hip", f"-Wl,-rpath,{lib.parent}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"], check=True)
     return exe
 
 
 def _undefined(tmp_path, source, det, explicit):
     obj = tmp_path / (source.stem + f"_{int(det)}{int(explicit)}.o")
-    subprocess.run([*_flags(det, explicit), "-c", str(source), "-o", str(obj)], check=True)
+    subprocess.run([*_flags(det, explicit), *CLASSES, "-c", str(source), "-o", str(obj)], check=True)
     out = subprocess.run(["nm", "-u", str(obj)], check=True, capture_output=True, text=True).stdout
     return {line.split()[-1] for line in out.splitlines() if line.strip()}
 
@@ -45,7 +50,7 @@ def _undefined(tmp_path, source, det, explicit):
 @pytest.mark.parametrize("det,explicit", BUILDS, ids=IDS)
 def test_the_client_compiles_in_every_build_and_references_the_calls_of_its_rounding(tmp_path, det, explicit):
     assert _build(tmp_path, det, explicit).exists()
-    und = _undefined(tmp_path, ROOT / "tests" / "cpp" / "m8_mvm_transposed_batch_dropin.cpp", det, explicit)
+    und = _undefined(tmp_path, CLIENT, det, explicit)
     assert "clm8_mvm_transposed_batch" in und
     if det:
         assert {"clm8_iht_batch_one_matrix", "clm8_mvm_transposed_scale_and_add_batch"} <= und
