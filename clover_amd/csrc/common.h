@@ -133,6 +133,10 @@ __device__ __forceinline__ int dot32(const u32x4 &a, const u32x4 &b)
 // scales (absolute maxima of the data); a block with an infinite element is outside the reference's contract already (its quantiser
 // feeds 7/inf = 0 and inf * 0 = NaN to cvttps, CloverVector4.h:668-685) and DESIGN.md 4 lists non-finite inputs as out of contract,
 // so the callers do not guard (a guard would cost the streaming kernels one VALU instruction per block word).
+// The fused forms pass div7(m * a) with m the scale the mvm just produced: a finite m times a finite a overflows to inf only for
+// m >= FLT_MAX / |a| (1.36e38 at a = 2.5).  The reference's scaleAndAdd then computes sv * a = inf and inf / 7.0f = inf itself, and its
+// elements q * inf + u are +/-inf, or NaN where q = 0 (CloverVector4.h:1228): out of contract there as well, so no guard here either.
+// The band grid of tests/edge_band_data.py goes up to block scales of a few 1e35 times a = 2.5 and asserts that m * a stays finite.
 __device__ __forceinline__ float div7(float x)
 {
     const float c = 1.0f / 7.0f;
