@@ -8,24 +8,7 @@
 // operands exactly, one fp32 fma"; hipcc keeps the widening apart from the fma (it folds it into v_fma_mix_f32 only with fp32
 // denormals flushed) and pairs the fmas into v_pk_fma_f32, each half still one fused, singly rounded fma.  The packed f16 dot
 // instructions round differently and are not used.
-#include "dot_common.h"
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ uint16_t f16_bits(float f)
-{
-    const _Float16 h = (_Float16)f;
-    uint16_t b;
-    __builtin_memcpy(&b, &h, 2);
-    return b;
-}
-
-template <bool NT, typename T> __device__ __forceinline__ T ld_stream(const T *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
-template <bool NT, typename T> __device__ __forceinline__ void st_stream(T v, T *p)
-{
-    if (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+#include "half16_device.h"      // the conversions, the 32 chains and their tree, the fused epilogue: shared with half16_batch.hip
 
 // ================================================================================================
 // streaming vector kernels: lane = 8 consecutive elements (16 bytes of f16), F16_VU groups in flight per lane
@@ -107,44 +90,6 @@ __global__ __launch_bounds__(256) void k_f16_clear(u32x4 *__restrict__ h, uint64
 }
 
 // ================================================================================================
-// the 32 chains and their tree
-// ================================================================================================
-// A quad of lanes owns one row (or the one dot): lane p = tid & 3 keeps accumulator p of the reference's four __m256 -- chains
-// 8p .. 8p + 7 -- in acc[0..7].  A 16-byte load is 8 consecutive elements, i.e. one step of those 8 chains; the quad reads the 64
-// contiguous bytes of a 32-element step.
-__device__ __forceinline__ void f16_chain_step(const h16x8 a, const h16x8 x, float acc[8])
-{
-#pragma unroll
-    for (int l = 0; l < 8; l++) acc[l] = __builtin_fmaf((float)x[l], (float)a[l], acc[l]);
-}
-__device__ __forceinline__ void f16_chain_step(const h16x8 a, const f32x4 x0, const f32x4 x1, float acc[8])
-{
-    acc[0] = __builtin_fmaf(x0.x, (float)a[0], acc[0]);
-    acc[1] = __builtin_fmaf(x0.y, (float)a[1], acc[1]);
-    acc[2] = __builtin_fmaf(x0.z, (float)a[2], acc[2]);
-    acc[3] = __builtin_fmaf(x0.w, (float)a[3], acc[3]);
-    acc[4] = __builtin_fmaf(x1.x, (float)a[4], acc[4]);
-    acc[5] = __builtin_fmaf(x1.y, (float)a[5], acc[5]);
-    acc[6] = __builtin_fmaf(x1.z, (float)a[6], acc[6]);
-    acc[7] = __builtin_fmaf(x1.w, (float)a[7], acc[7]);
-}
-
-// (acc0 + acc1) + (acc2 + acc3) lane-wise, then _mm256_haddf32_ps (CloverBase.h:149-157): t[i] = s[i + 4] + s[i],
-// (t0 + t2) + (t1 + t3).  acc0 + acc1 sits in lanes p, p ^ 1 of the quad, the sum of the two pairs in lanes p, p ^ 2: every lane of
-// the quad ends with the value.
-__device__ __forceinline__ float f16_chain_tree(const float acc[8])
-{
-    float s[8];
-#pragma unroll
-    for (int l = 0; l < 8; l++) {
-        const float pair = acc[l] + __shfl_xor(acc[l], 1);
-        s[l] = pair + __shfl_xor(pair, 2);
-    }
-    const float t0 = s[4] + s[0], t1 = s[5] + s[1], t2 = s[6] + s[2], t3 = s[7] + s[3];
-    return (t0 + t2) + (t1 + t3);
-}
-
-// ================================================================================================
 // mvm  (CloverMatrix16.h:230-308 f16 vectors, :321-381 fp32 vectors; mvm_parallel :133-228 has the same order per row)
 // ================================================================================================
 // Workgroup = 16 * WAVES rows, four lanes per row.  x is staged in LDS once per workgroup, 16 KiB at a time (8192 f16 or 4096 fp32
@@ -170,37 +115,7 @@ __device__ __forceinline__ void f16_mvm_steps(const h16x8 *__restrict__ Ap, cons
     }
 }
 
-// FUSE... = F16Fuse (clm_f16_mvm_scale_and_add, k_f16_mvm_saa below): the CloverVector16::scaleAndAdd that follows this mvm in the IHT / GD loops
-// (CloverVector16.h:309-386), done by the lane that stores the row: v = f16(d); r2[row] = f16(fma(f32(v), a, f32(u[row]))) -- the ROUNDED
-// v widened again, as two separate calls compute.  A row depends on no other row: no workgroup-wide step.  u[row] is requested before the
-// streaming loop.  r (the f16 A x, t of the ABI) may be NULL under FUSE: it is then not stored.
-// The flag is a trailing parameter pack, empty or one F16Fuse, and the kernel itself is the shared template: with the body in an inlined
-// device function the fp32-vector instantiations came out two instructions longer (another base for the unrolled loads); this way every
-// <WAVES, NT, XF32> instantiation keeps its signature and, instruction for instruction, the code it had.
-struct F16Fuse {
-    const uint16_t *u;
-    float a;
-    uint16_t *r2;            // may alias u (the in-place form): a lane reads its element of u before it writes it
-};
-__device__ __forceinline__ uint16_t f16_fuse_load_u(uint64_t) { return 0; }
-__device__ __forceinline__ uint16_t f16_fuse_load_u(uint64_t row, const F16Fuse &f) { return f.u[row]; }
-__device__ __forceinline__ void f16_fuse_store(void *, uint64_t, float, uint16_t) {}
-__device__ __forceinline__ void f16_fuse_store(void *t, uint64_t row, float d, uint16_t ub, const F16Fuse &f)
-{
-    _Float16 v = (_Float16)d, uh;                                        // _mm256_cvtps_ph(.., 0) of the row block (:302-306)
-    uint16_t vb;
-    __builtin_memcpy(&vb, &v, 2);
-    __builtin_memcpy(&uh, &ub, 2);
-    if (t) reinterpret_cast<uint16_t *>(t)[row] = vb;
-    // widening, fma and conversion stay the three instructions of k_f16_scale_and_add -- v_cvt_f32_f16, v_fma_f32, v_cvt_f16_f32 (left
-    // alone, hipcc folds them into v_fma_mixlo_f16 here)
-    float vf = (float)v;
-    asm volatile("" : "+v"(vf));
-    float s = __builtin_fmaf(vf, f.a, (float)uh);
-    asm volatile("" : "+v"(s));
-    f.r2[row] = f16_bits(s);
-}
-
+// F16Fuse, the fused epilogue of clm_f16_mvm_scale_and_add (k_f16_mvm_saa below): half16_device.h
 // fuse.r2 may be fuse.u: the lane that writes r2[row] has read u[row] before the loop.  r (t of the ABI) is apart from x, u and r2.
 template <int WAVES, bool NT, bool XF32, typename... FUSE>
 __global__ __launch_bounds__(64 * WAVES) void k_f16_mvm(const uint16_t *__restrict__ A, uint64_t rows, uint64_t cols, const void *__restrict__ x,
@@ -373,8 +288,6 @@ __global__ __launch_bounds__(256) void k_f16_transpose(const uint16_t *__restric
 // ================================================================================================
 // C ABI
 // ================================================================================================
-#define F16_ALIGNED(p) (((uintptr_t)(p) & 15u) == 0)
-
 static int f16_check_vec(const char *fn, uint64_t n_pad)
 {
     CLV_REQUIRE(n_pad % 128 == 0, "%s: n_pad=%llu is not a multiple of 128", fn, (unsigned long long)n_pad);
@@ -383,9 +296,6 @@ static int f16_check_vec(const char *fn, uint64_t n_pad)
 }
 
 static inline unsigned f16_vec_grid(uint64_t ngroups) { return (unsigned)((ngroups + F16_VEC_GROUPS_PER_WG - 1) / F16_VEC_GROUPS_PER_WG); }
-
-// streaming loads / stores once the operands cannot stay in the 256 MiB Infinity Cache (the clm4_mvm rule)
-#define F16_STREAMING(bytes) ((bytes) > (256ull << 20))
 
 static int f16_quantize(const char *fn, const float *x, uint64_t n, uint16_t *h, void *stream)
 {
@@ -549,6 +459,15 @@ extern "C" int clm_f16_mvm_scale_and_add(const uint16_t *A, uint64_t rows, uint6
 }
 #undef F16_SAA
 
+int clv_internal_f16_clear(uint16_t *x, uint64_t n_pad, hipStream_t st)
+{
+    if (!n_pad) return CLV_OK;
+    const uint64_t ng = n_pad / 8, want = (ng + 255) / 256;
+    hipLaunchKernelGGL(k_f16_clear, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, st, (u32x4 *)x, ng);
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+
 // Q_IHT / Q_GD (test/performance/01_measure.h:923-946, 999-1021) over a CloverMatrix16 with CloverVector16 vectors
 // (test/performance/02_bit16.cpp:112-117).  One call enqueues all iterations: 3 launches per iteration (2 for GD), nothing copied back.
 extern "C" int clm_f16_iht(const uint16_t *Phi, const uint16_t *PhiT, uint64_t m, uint64_t n, uint16_t *x, uint64_t x_len, const uint16_t *y,
@@ -559,12 +478,7 @@ extern "C" int clm_f16_iht(const uint16_t *Phi, const uint16_t *PhiT, uint64_t m
                 (unsigned long long)x_len);
     CLV_REQUIRE(threshold >= 0 && threshold <= 2, "clm_f16_iht: unknown threshold %d", threshold);
     CLV_REQUIRE(F16_ALIGNED(Phi) && F16_ALIGNED(PhiT) && F16_ALIGNED(x) && F16_ALIGNED(t2), "clm_f16_iht: the matrices, x and t2 must be 16-byte aligned");
-    if (n) {                                                                                             // x.clear()
-        const uint64_t ng = n / 8, want = (ng + 255) / 256;
-        hipLaunchKernelGGL(k_f16_clear, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, as_stream(stream), (u32x4 *)x, ng);
-        CLV_LAUNCH_CHECK();
-    }
-    int rc = CLV_OK;
+    int rc = clv_internal_f16_clear(x, n, as_stream(stream));                                            // x.clear()
     for (uint64_t it = 0; !rc && it < iterations; it++) {
         rc = clm_f16_mvm_scale_and_add(Phi, m, n, x, y, -1.0f, t1, t2, stream);                          // t1 = Phi x; t2 = y - t1
         if (!rc) rc = clm_f16_mvm_scale_and_add(PhiT, n, m, t2, x, mu, t3, x, stream);                   // t3 = Phi' t2; x += mu t3

@@ -2,7 +2,8 @@
 // and overlap check and the batched IHT / GD loop.  Included by mvm_batch4.hip (CloverMatrix4 x CloverVector4), mvm_batch8.hip
 // (CloverMatrix4 x CloverVector8), matrix8_batch.hip (CloverMatrix8 x CloverVector8), mvm_t4_batch.hip (CloverMatrix4' x CloverVector4
 // straight from the matrix's own bytes), mvm_t8_batch.hip (CloverMatrix4' x CloverVector8, likewise) and matrix8_t_batch.hip (CloverMatrix8' x
-// CloverVector8, likewise) and by nothing else.  Each of them defines its
+// CloverVector8, likewise); half16_batch.hip (CloverMatrix16 x CloverVector16, no scales and no draws: a driver of its own) includes it for
+// mvm_batch_forced() alone.  Each of the six defines its
 // kernel and a traits struct F with exactly what differs between the families:
 //   Args<NV>, Fuse<NV>                        the kernel's by-value argument structs (their pointer types decide the casts)
 //   matrix_bytes(rows, cols), vector_bytes(n) sizes for the overlap check; the matrix streams (NT) above the 256 MiB Infinity Cache

@@ -7,6 +7,7 @@
 // 32: ThreshHost<BITS> (what differs on the host), thresh_ladder, the checks and the templates the extern "C" entries name their width to.
 #include "common.h"
 #include "clover_hip_fp32.h"
+#include "clover_hip_batch_f16.h"
 #include "thresh_device.h"
 
 #include <type_traits>
@@ -619,8 +620,9 @@ __device__ __forceinline__ uint32_t f16_dense_key(uint32_t key)
     return (ed << 10) | ((key >> 13) & 0x3FFu);
 }
 
+// the body of k_f16_thresh_small and of k_f16_thresh_small_batch (one workgroup = one vector in both)
 template <int W>
-__global__ __launch_bounds__(TS_THREADS) void k_f16_thresh_small(uint32_t *__restrict__ q, uint32_t n, uint32_t k)
+__device__ __forceinline__ void f16_thresh_small_body(uint32_t *__restrict__ q, uint32_t n, uint32_t k)
 {
     typedef ThreshElems<16> E;
     __shared__ __attribute__((aligned(16))) uint32_t hist[2 * TSF_COPIES * TSF_CS];
@@ -708,6 +710,20 @@ __global__ __launch_bounds__(TS_THREADS) void k_f16_thresh_small(uint32_t *__res
             q[i] = outw;
         }
     }
+}
+
+template <int W>
+__global__ __launch_bounds__(TS_THREADS) void k_f16_thresh_small(uint32_t *__restrict__ q, uint32_t n, uint32_t k)
+{
+    f16_thresh_small_body<W>(q, n, k);
+}
+
+// clv_f16_threshold_batch: workgroup j runs the body above on vector j (ThreshBatchArgs: the pointers by value, groups of TS_BATCH_GROUP;
+// its scale slots are unused)
+template <int W>
+__global__ __launch_bounds__(TS_THREADS) void k_f16_thresh_small_batch(ThreshBatchArgs args, uint32_t n, uint32_t k)
+{
+    f16_thresh_small_body<W>(args.q[blockIdx.x], n, k);
 }
 
 // ---- single-workgroup path for CloverVector32 (n_pad <= TS_THREADS * TS_MAXW = 16384): k_f16_thresh_small with one element per word.  The
@@ -1944,8 +1960,8 @@ static int threshold_reference(uint32_t *q, const float *s, uint64_t n, uint64_t
 //   EPW, MAXW                elements per word; the largest compiled words per thread (one workgroup serves n_pad <= TS_THREADS * MAXW * EPW)
 //   SCALES, ALIGNED_X        whether a scale array exists (a kernel argument, a pointer to check); whether x must be 16-byte aligned
 //   SMALL_SWITCH             the environment switch, read per call, whose 0 keeps the large-vector path at every n (NULL: none)
-//   small<W>, small_batch<W> the one-workgroup kernel and, where one exists (4 / 8), its batch form
-//   q_bytes(n_pad)           bytes of a vector's q, for the batch call's overlap check (4 / 8)
+//   small<W>, small_batch<W> the one-workgroup kernel and, where one exists (4 / 8 / 16), its batch form
+//   q_bytes(n_pad)           bytes of a vector's q, for the batch call's overlap check (4 / 8 / 16)
 //   large, workspace_bytes   the large-vector path and the size of the workspace it carves
 // =================================================================================================
 template <int BITS>
@@ -1988,6 +2004,8 @@ struct ThreshHost<16> : ThreshHostLarge<16> {
     static constexpr bool SCALES = false, ALIGNED_X = false;
     static constexpr const char *SMALL_SWITCH = "CLV_F16_THRESHOLD_SMALL";
     template <int W> static constexpr auto small = k_f16_thresh_small<W>;
+    template <int W> static constexpr auto small_batch = k_f16_thresh_small_batch<W>;
+    static uint64_t q_bytes(uint64_t n_pad) { return n_pad * 2; }
 };
 
 template <>
@@ -2087,30 +2105,33 @@ static int threshold_heap(const char *fn, void *q, const float *s, uint64_t n, u
 
 // threshold on nvec vectors of one size.  q / s: HOST arrays of nvec device pointers.  FAST up to the one-workgroup limit: one launch per
 // TS_BATCH_GROUP vectors, workgroup j = the one-workgroup kernel's body on vector j; otherwise the sequence of single calls (`single`: the
-// width's _mode entry).  Bit-identical to that sequence.
-template <int BITS>
-static int threshold_batch(const char *fn, int (*single)(int8_t *, const float *, uint64_t, uint64_t, uint64_t, int, void *, void *),
-                           int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *stream)
+// width's _mode entry, as a callable that takes a vector's q and s).  Bit-identical to that sequence.  A width without scales (16)
+// passes s == NULL and has nothing of them checked; with its SMALL_SWITCH at 0 its single calls keep the large-vector path, so the batch
+// forwards to them.
+template <int BITS, class Q, class Single>
+static int threshold_batch(const char *fn, Single single, Q *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k,
+                           int mode, void *stream)
 {
     typedef ThreshHost<BITS> H;
     int rc = thresh_check_mode(fn, mode);
     if (!rc) rc = thresh_check_sizes(fn, n, n_pad);
     if (rc) return rc;
     if (!nvec) return CLV_OK;
-    CLV_REQUIRE(q && s, "%s: null pointer array", fn);
-    for (uint64_t j = 0; j < nvec; j++) CLV_REQUIRE(q[j] && s[j], "%s: null pointer in vector %llu", fn, (unsigned long long)j);
+    CLV_REQUIRE(q && (s || !H::SCALES), "%s: null pointer array", fn);
+    for (uint64_t j = 0; j < nvec; j++) CLV_REQUIRE(q[j] && (!H::SCALES || s[j]), "%s: null pointer in vector %llu", fn, (unsigned long long)j);
     std::vector<ClvRange> rg;
     rg.reserve(2 * nvec);
     for (uint64_t j = 0; j < nvec; j++) {
         rg.push_back(clv_range(q[j], H::q_bytes(n_pad), true, j, "q"));
-        rg.push_back(clv_range(s[j], n_pad / 64 * sizeof(float), false, j, "s"));
+        if (H::SCALES) rg.push_back(clv_range(s[j], n_pad / 64 * sizeof(float), false, j, "s"));
     }
     rc = clv_internal_check_ranges(fn, rg);
     if (rc) return rc;
     if (k >= n || n == 0) return CLV_OK;                       // everything survives
-    if (nvec == 1 || mode != CLV_THRESHOLD_FAST || n_pad > (uint64_t)TS_THREADS * H::MAXW * H::EPW) {
+    if (nvec == 1 || mode != CLV_THRESHOLD_FAST || n_pad > (uint64_t)TS_THREADS * H::MAXW * H::EPW ||
+        (H::SMALL_SWITCH && !clv_env_int(H::SMALL_SWITCH, 1))) {
         for (uint64_t j = 0; j < nvec; j++) {
-            rc = single(q[j], s[j], n, n_pad, k, mode, nullptr, stream);
+            rc = single(q[j], H::SCALES ? s[j] : nullptr, n, n_pad, k, mode, stream);
             if (rc) return rc;
         }
         return CLV_OK;
@@ -2122,7 +2143,7 @@ static int threshold_batch(const char *fn, int (*single)(int8_t *, const float *
         ThreshBatchArgs args;
         for (uint64_t j = 0; j < TS_BATCH_GROUP; j++) {
             args.q[j] = j < g ? (uint32_t *)q[j0 + j] : nullptr;
-            args.s[j] = j < g ? s[j0 + j] : nullptr;
+            args.s[j] = j < g && H::SCALES ? s[j0 + j] : nullptr;
         }
         thresh_ladder<H::MAXW>(wpt, [&](auto w) {
             hipLaunchKernelGGL(H::template small_batch<decltype(w)::value>, dim3((unsigned)g), dim3(TS_THREADS), 0, st, args, (uint32_t)n, (uint32_t)k);
@@ -2155,7 +2176,8 @@ extern "C" int clv4_threshold_heap(int8_t *q, const float *s, uint64_t n, uint64
 extern "C" int clv4_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode,
                                     void *stream)
 {
-    return threshold_batch<4>("clv4_threshold_batch", clv4_threshold_mode, q, s, nvec, n, n_pad, k, mode, stream);
+    return threshold_batch<4>("clv4_threshold_batch", [](int8_t *qj, const float *sj, uint64_t n_, uint64_t n_pad_, uint64_t k_, int mode_, void *stream_) {
+        return clv4_threshold_mode(qj, sj, n_, n_pad_, k_, mode_, nullptr, stream_); }, q, s, nvec, n, n_pad, k, mode, stream);
 }
 
 // CloverVector8::threshold(K) (CloverVector8.h:1680-1740): same algorithm and tie rule on |q * scale / 127|
@@ -2175,7 +2197,8 @@ extern "C" int clv8_threshold_heap(int8_t *q, const float *s, uint64_t n, uint64
 extern "C" int clv8_threshold_batch(int8_t *const *q, const float *const *s, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode,
                                     void *stream)
 {
-    return threshold_batch<8>("clv8_threshold_batch", clv8_threshold_mode, q, s, nvec, n, n_pad, k, mode, stream);
+    return threshold_batch<8>("clv8_threshold_batch", [](int8_t *qj, const float *sj, uint64_t n_, uint64_t n_pad_, uint64_t k_, int mode_, void *stream_) {
+        return clv8_threshold_mode(qj, sj, n_, n_pad_, k_, mode_, nullptr, stream_); }, q, s, nvec, n, n_pad, k, mode, stream);
 }
 
 // CloverVector16::threshold(K) / threshold_min_heap (CloverVector16.h:612-768): the same selection on |f32(h)|, two elements per word and no
@@ -2188,6 +2211,12 @@ extern "C" int clv_f16_threshold_mode(uint16_t *h, uint64_t n, uint64_t n_pad, u
 extern "C" int clv_f16_threshold_heap(uint16_t *h, uint64_t n, uint64_t n_pad, uint64_t k, void *heap_dev, void *workspace, void *stream)
 {
     return threshold_heap<16>("clv_f16_threshold_heap", h, nullptr, n, n_pad, k, heap_dev, workspace, stream);
+}
+// the same on nvec vectors (include/clover_hip_batch_f16.h): FAST up to one workgroup's 32768 elements in one launch per TS_BATCH_GROUP vectors
+extern "C" int clv_f16_threshold_batch(uint16_t *const *h, uint64_t nvec, uint64_t n, uint64_t n_pad, uint64_t k, int mode, void *stream)
+{
+    return threshold_batch<16>("clv_f16_threshold_batch", [](uint16_t *hj, const float *, uint64_t n_, uint64_t n_pad_, uint64_t k_, int mode_, void *stream_) {
+        return clv_f16_threshold_mode(hj, n_, n_pad_, k_, mode_, nullptr, stream_); }, h, (const float *const *)nullptr, nvec, n, n_pad, k, mode, stream);
 }
 
 // CloverVector32::threshold(K) (CloverVector32.h:549-600): the same selection on |x|, one element per word and no scales.  FAST:

@@ -221,6 +221,16 @@ SIGNATURES_BATCH_T_V8 = {
 }
 
 
+# name -> (restype, argtypes); everything include/clover_hip_batch_f16.h declares (the batched half-precision mvm, CloverMatrix16 x
+# CloverVector16: plain, fused, the threshold of several vectors and the IHT / GD loop for several signals): no scales, no generator
+SIGNATURES_BATCH_F16 = {
+    "clm_f16_mvm_batch": (C.c_int, [_vp, _u64, _u64, _u64, _vp, _vp, _vp]),
+    "clm_f16_mvm_scale_and_add_batch": (C.c_int, [_vp, _u64, _u64, _u64, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "clv_f16_threshold_batch": (C.c_int, [_vp, _u64, _u64, _u64, _u64, C.c_int, _vp]),
+    "clm_f16_iht_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
+}
+
+
 class CloverHipError(RuntimeError):
     pass
 
@@ -234,7 +244,8 @@ def load_library(path: str | Path | None = None, allow_probe: bool = False) -> C
             f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = C.CDLL(str(p))
-    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items(), *SIGNATURES_BATCH_T8.items(), *SIGNATURES_BATCH_T_V8.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items(), *SIGNATURES_BATCH_T8.items(), *SIGNATURES_BATCH_T_V8.items(),
+                              *SIGNATURES_BATCH_F16.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -839,6 +850,48 @@ class CloverHip:
         self.check(self.lib.clm_f16_iht(b[0].ptr, b[1].ptr, m, n, v["x"].ptr, n if x_len is None else x_len, b[2].ptr, v["t1"].ptr, v["t2"].ptr,
                                         v["t3"].ptr, iterations, K, mu, threshold, None))
         return {name: v[name].download(np.uint16, ln) for name, ln in lens.items()}
+
+    # several CloverVector16 with one CloverMatrix16 (clover_hip_batch_f16.h; host arrays of device pointers; lists in, lists out)
+    def mf16_mvm_batch(self, hA, rows, cols, hxs):
+        """hxs: list of x bit patterns; returns the list of r of clm_f16_mvm_batch.  hA may be a DevBuf (a matrix uploaded once)"""
+        dA = hA if isinstance(hA, DevBuf) else self.to_device(hA)
+        dx = [self.to_device(h) for h in hxs]
+        dr = [self.alloc(max(2 * rows, 2)) for _ in hxs]
+        pa = self.ptr_array
+        self.check(self.lib.clm_f16_mvm_batch(dA.ptr, rows, cols, len(hxs), pa(dx), pa(dr), None))
+        return [r.download(np.uint16, rows) for r in dr]
+
+    def mf16_mvm_scale_and_add_batch(self, hA, rows, cols, hxs, hus, a: float, in_place: bool = False, want_t: bool = True):
+        """hxs, hus: lists of bit patterns; returns the list of (t, r) of clm_f16_mvm_scale_and_add_batch; t is None when want_t is False"""
+        dA = hA if isinstance(hA, DevBuf) else self.to_device(hA)
+        dx, du = [self.to_device(h) for h in hxs], [self.to_device(h) for h in hus]
+        dt = [self.alloc(max(2 * rows, 2)) for _ in hxs] if want_t else None
+        dr = du if in_place else [self.alloc(max(2 * rows, 2)) for _ in hxs]
+        pa = self.ptr_array
+        self.check(self.lib.clm_f16_mvm_scale_and_add_batch(dA.ptr, rows, cols, len(hxs), pa(dx), pa(du), a, pa(dt), pa(dr), None))
+        return [((dt[j].download(np.uint16, rows) if want_t else None), dr[j].download(np.uint16, rows)) for j in range(len(hxs))]
+
+    def f16_threshold_batch(self, hs, n: int, k: int, mode: int = THRESHOLD_FAST):
+        """hs: list of vectors of one padded size; returns the list of thresholded vectors of clv_f16_threshold_batch"""
+        dh = [self.to_device(h) for h in hs]
+        self.check(self.lib.clv_f16_threshold_batch(self.ptr_array(dh), len(hs), n, hs[0].size if hs else 0, k, mode, None))
+        return [d.download(np.uint16, h.size) for d, h in zip(dh, hs)]
+
+    def mf16_iht_batch(self, hPhi, hPhiT, m, n, hys, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+                       prefill: int = 0x55):
+        """clm_f16_iht_batch on buffers prefilled with `prefill` bytes; hys: list of y bit patterns; returns per signal
+        {"x": bits, "t1": ..., "t2": ..., "t3": ...}.  hPhi / hPhiT may be DevBufs"""
+        dPhi, dPhiT = [h if isinstance(h, DevBuf) else self.to_device(h) for h in (hPhi, hPhiT)]
+        dy = [self.to_device(h) for h in hys]
+        lens = {"x": n, "t1": m, "t2": m, "t3": n}
+        v = {name: [self.alloc(max(2 * ln, 2)) for _ in hys] for name, ln in lens.items()}
+        for bufs in v.values():
+            for d in bufs:
+                self.check(self.lib.clv_memset(d.ptr, prefill, d.nbytes, None))
+        pa = self.ptr_array
+        self.check(self.lib.clm_f16_iht_batch(dPhi.ptr, dPhiT.ptr, m, n, len(hys), pa(v["x"]), n if x_len is None else x_len, pa(dy), pa(v["t1"]),
+                                              pa(v["t2"]), pa(v["t3"]), iterations, K, mu, threshold, None))
+        return [{name: v[name][j].download(np.uint16, ln) for name, ln in lens.items()} for j in range(len(hys))]
 
     def mf16_transpose(self, h, rows, cols) -> np.ndarray:
         dh, dt = self.to_device(h), self.alloc(max(2 * rows * cols, 2))

@@ -458,6 +458,23 @@ inline void Q_GD<CloverMatrix16, CloverVector16>(CloverMatrix16 &Phi, CloverMatr
     Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, 0, mu, false);
 }
 
+/* the same for `count` signals with ONE half-precision Phi (CloverMatrix16::iht_loop_batch -> clm_f16_iht_batch, clover_hip_batch_f16.h): per
+ * iteration two fused launches and one threshold for a group of signals; bit-identical to calling Q_IHT / Q_GD above signal after signal.
+ * Unconditional, as those: the 16-bit classes have no stochastic rounding; the threshold follows the exactness switch (FAST under
+ * -DCLOVER_FAST, the reference's survivors by default). */
+inline void Q_IHT_batch(CloverMatrix16 &Phi, CloverMatrix16 &PhiT, CloverVector16 *const *x, CloverVector16 *const *y, CloverVector16 *const *t1,
+                        CloverVector16 *const *t2, CloverVector16 *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
+                        const float mu)
+{
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, K, mu, true);
+}
+
+inline void Q_GD_batch(CloverMatrix16 &Phi, CloverMatrix16 &PhiT, CloverVector16 *const *x, CloverVector16 *const *y, CloverVector16 *const *t1,
+                       CloverVector16 *const *t2, CloverVector16 *const *t3, const uint64_t count, const uint64_t iterations, const float mu)
+{
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+}
+
 #ifdef CLOVER_FP32_ON_DEVICE
 /* CloverMatrix32 with CloverVector32 vectors under -DCLOVER_FP32_ON_DEVICE: the fp32 baseline of every table of the reference, on the
  * device.  The whole loop in one call (CloverMatrix32::iht_loop -> clm_f32_iht): three launches per iteration, two for Q_GD, the bits of

@@ -14,6 +14,10 @@
  *
  *   mvm_scaleAndAdd                      -> clm_f16_mvm_scale_and_add  (not in the reference: mvm + the scaleAndAdd behind it, one launch)
  *   iht_loop                             -> clm_f16_iht        (the whole Q_IHT / Q_GD loop of 01_measure.h:923-946, 999-1021 in one call)
+ *   mvm_batch / mvm_scaleAndAdd_batch / iht_loop_batch
+ *                                        -> clm_f16_mvm_batch, clm_f16_mvm_scale_and_add_batch, clm_f16_iht_batch (clover_hip_batch_f16.h;
+ *                                           not in the reference: the same for several vectors in ONE pass over the matrix per group of
+ *                                           CLM4_MVM_BATCH_MAX, bit-identical to the single methods vector after vector)
  *
  * Q_IHT<CloverMatrix16, CloverVector16> and Q_GD<...> are specialised in CloverIHT.h (which includes this header) and call iht_loop: every
  * step is a kernel on the device mirrors, nothing is copied back between steps.
@@ -23,10 +27,12 @@
 
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "CloverMatrix32.h"
 #include "CloverVector16.h"
 #include "CloverVector32.h"
+#include "clover_hip_batch_f16.h"  /* the batched half-precision calls: a header of their own beside clover_hip.h */
 
 class CloverMatrix16 {
 protected:
@@ -51,6 +57,36 @@ protected:
         if (productVector.size_pad() != getCols() || resultVector.size_pad() != getRows()) {
             std::cout << "MVM can not be performed. Exiting ..." << std::endl;
             exit(1);
+        }
+    }
+    /* The batch methods carry a caller's vectors into the batched C calls as the batch methods of CloverMatrix4 / 8 do (clover_batch.h),
+     * without the scale arrays those have: inputs are mapped read-only first, then the outputs write-only (read-write for the in-place
+     * form).  The pointers of inputs are stored without their const and handed on as const again. */
+    typedef std::vector<uint16_t *> DevArray;
+    static DevArray dev_inputs(const CloverVector16 *const *v, uint64_t count)
+    {
+        DevArray a;
+        for (uint64_t j = 0; j < count; j++) a.push_back(const_cast<uint16_t *>(v[j]->dev_values_ro()));
+        return a;
+    }
+    static DevArray dev_outputs(CloverVector16 *const *v, uint64_t count, bool read_too)
+    {
+        DevArray a;
+        for (uint64_t j = 0; j < count; j++) a.push_back(read_too ? v[j]->dev_values_rw() : v[j]->dev_values_wo());
+        return a;
+    }
+    static void batch_exit(const char *message)
+    {
+        std::cout << message << std::endl;
+        exit(1);
+    }
+    /* the size rules of mvm_scaleAndAdd, vector by vector; r == NULL: the in-place form */
+    void check_fused_batch(const CloverVector16 *const *x, const CloverVector16 *const *u, CloverVector16 *const *t, CloverVector16 *const *r,
+                           uint64_t count) const
+    {
+        for (uint64_t j = 0; j < count; j++) {
+            if (x[j]->size_pad() != getCols() || t[j]->size_pad() != getRows()) batch_exit("MVM can not be performed. Exiting ...");
+            if (u[j]->size_pad() != getRows() || (r && r[j]->size_pad() != getRows())) batch_exit("Vectors do not have the same size. Exiting ...");
         }
     }
     void check_transpose(const CloverMatrix16 &other) const
@@ -159,6 +195,56 @@ public:
                           "CloverMatrix16::iht_loop");
         x.commit();
         if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
+    }
+    /* Not in the reference: this * x[j] for `count` vectors in ONE pass over the matrix per group of CLM4_MVM_BATCH_MAX (clm_f16_mvm_batch);
+     * r[j] equals what mvm(*x[j], *r[j]) gives, bit for bit.  The x[j] may repeat; the r[j] are distinct and none of them is an x. */
+    void mvm_batch(const CloverVector16 *const *x, CloverVector16 *const *r, uint64_t count) const
+    {
+        for (uint64_t j = 0; j < count; j++)
+            if (x[j]->size_pad() != getCols() || r[j]->size_pad() != getRows()) batch_exit("MVM can not be performed. Exiting ...");
+        const DevArray px = dev_inputs(x, count), pr = dev_outputs(r, count, false);
+        clover_hip::check(clm_f16_mvm_batch(dev_values(), rows, cols, count, px.data(), pr.data(), nullptr), "CloverMatrix16::mvm_batch");
+        for (uint64_t j = 0; j < count; j++) r[j]->commit();
+    }
+    /* mvm_scaleAndAdd for `count` vectors: t[j] = this * x[j], r[j] = f16(u[j] + a * t[j]), the matrix read once per group
+     * (clm_f16_mvm_scale_and_add_batch); the bits of the loop of mvm_scaleAndAdd. */
+    void mvm_scaleAndAdd_batch(const CloverVector16 *const *x, const CloverVector16 *const *u, float a, CloverVector16 *const *t,
+                               CloverVector16 *const *r, uint64_t count) const
+    {
+        check_fused_batch(x, u, t, r, count);
+        const DevArray px = dev_inputs(x, count), pu = dev_inputs(u, count), pt = dev_outputs(t, count, false), pr = dev_outputs(r, count, false);
+        clover_hip::check(clm_f16_mvm_scale_and_add_batch(dev_values(), rows, cols, count, px.data(), pu.data(), a, pt.data(), pr.data(), nullptr),
+                          "CloverMatrix16::mvm_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
+    }
+    /* in place: u[j] = f16(u[j] + a * (this * x[j])); u[j] is mapped read-write and is both the call's u and its r */
+    void mvm_scaleAndAdd_batch(const CloverVector16 *const *x, CloverVector16 *const *u, float a, CloverVector16 *const *t, uint64_t count) const
+    {
+        check_fused_batch(x, u, t, nullptr, count);
+        const DevArray px = dev_inputs(x, count), pu = dev_outputs(u, count, true), pt = dev_outputs(t, count, false);
+        clover_hip::check(clm_f16_mvm_scale_and_add_batch(dev_values(), rows, cols, count, px.data(), pu.data(), a, pt.data(), pu.data(), nullptr),
+                          "CloverMatrix16::mvm_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
+    }
+    /* iht_loop for `count` signals with this matrix as Phi (clm_f16_iht_batch): per iteration every step runs once for a group of signals;
+     * x[j], t1[j], t2[j], t3[j] end as iht_loop(PhiT, *x[j], *y[j], ...) leaves them, bit for bit.  All x[j] have one size(). */
+    void iht_loop_batch(const CloverMatrix16 &PhiT, CloverVector16 *const *x, const CloverVector16 *const *y, CloverVector16 *const *t1,
+                        CloverVector16 *const *t2, CloverVector16 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu,
+                        bool with_threshold) const
+    {
+        for (uint64_t j = 0; j < count; j++)
+            if (PhiT.getRows() != getCols() || PhiT.getCols() != getRows() || x[j]->size_pad() != getCols() || y[j]->size_pad() != getRows() ||
+                t1[j]->size_pad() != getRows() || t2[j]->size_pad() != getRows() || t3[j]->size_pad() != getCols() || x[j]->size() != x[0]->size())
+                batch_exit("MVM can not be performed. Exiting ...");
+        const DevArray py = dev_inputs(y, count), px = dev_outputs(x, count, false), p1 = dev_outputs(t1, count, false),
+                       p2 = dev_outputs(t2, count, false), p3 = dev_outputs(t3, count, false);
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm_f16_iht_batch(dev_values(), PhiT.dev_values(), rows, cols, count, px.data(), count ? x[0]->size() : 0, py.data(),
+                                            p1.data(), p2.data(), p3.data(), iterations, K, mu, thr, nullptr), "CloverMatrix16::iht_loop_batch");
+        for (uint64_t j = 0; j < count; j++) {
+            x[j]->commit();
+            if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }
+        }
     }
     /* :98-131: one running fp32 sum of separately rounded products per row, rounded to f16 */
     void mvm_scalar(const CloverVector16 &productVector, CloverVector16 &resultVector) const

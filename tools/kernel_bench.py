@@ -1181,7 +1181,12 @@ for N8 in (8192, 16384):
     del P, sP, PT, sPT, vx, svx, vt3, svt3, vy, svy, vt1, svt1, vt2, svt2
 # ---- CloverVector16 / CloverMatrix16: raw binary16, 2 bytes per element, no scales
 # the rows of the fused calls and the one-call loop (the second f16 block below); the first block is skipped when only those are asked for
-F16_FUSED_ROWS = ("f16_mvm_scale_and_add", "f16_threshold_fast_n8192", "f16_q_iht_iteration", "f16_iht_loop", "f16_gd_loop")
+# group sizes of the f16 batch rows: 2, 4 and 8 (every instantiation full); KB_F16_BATCH_GROUPS=3,5,6,7 times the partly filled ones
+F16_GROUPS = tuple(int(g) for g in os.environ.get("KB_F16_BATCH_GROUPS", "2,4,8").split(","))
+F16_BATCH_ROWS = tuple(f"f16_mvm_batch{g}_{nb}^2" for nb in (32768, 65536) for g in F16_GROUPS) + \
+    tuple(f"f16_mvm_saa_batch{g}_8192x4096" for g in F16_GROUPS) + ("f16_iht_batch8_N8192",)
+F16_FUSED_ROWS = ("f16_mvm_scale_and_add", "f16_threshold_fast_n8192", "f16_q_iht_iteration", "f16_iht_loop", "f16_gd_loop", "f16_mvm_batch",
+                  "f16_mvm_saa_batch", "f16_iht_batch")
 SLAB = 1 << 28
 
 
@@ -1193,6 +1198,87 @@ def f16_fill(dst, count, seed):
         hip.check(lib.clv_fill_random_ints_f32(src.ptr, c, 10, seed, o, None))
         hip.check(lib.clv_f16_quantize(src.ptr, c, dst.ptr + 2 * o, None))
     hip.sync()
+
+
+# ---- several CloverVector16 with one CloverMatrix16 (half16_batch.hip): every row pairs the batch call, on the batched kernel
+# (CLV_MVM_BATCH=1), with the same vectors issued as single calls -- the rounds of the two ALTERNATED in one process, so that a drift of
+# the clocks lands on both.  f16_mvm_batch{2,4,8}_{32768,65536}^2: the plain mvm (streaming); f16_mvm_saa_batch{2,4,8}_8192x4096: the fused
+# x += mu Phi' t2 step of the IHT shape (cache-resident); f16_iht_batch8_N8192: clm_f16_iht_batch against 8 x clm_f16_iht, ms per iteration
+# for 8 signals.  KB_ONLY=f16_mvm_batch,f16_mvm_saa_batch,f16_iht_batch selects them and the run ends after them.
+def rec_pair_alternated(name, nbytes_single, g, single, batch, reps=10, per=1, rounds=5):
+    if not selected(name):
+        return
+
+    def forced_batch():
+        os.environ["CLV_MVM_BATCH"] = "1"
+        try:
+            return rounds_of(batch, reps=reps, rounds=1, warm=0)[0] / per
+        finally:
+            os.environ.pop("CLV_MVM_BATCH", None)
+    os.environ.pop("CLV_MVM_BATCH", None)
+    rounds_of(single, reps=1, rounds=1, warm=1)
+    forced_batch()
+    one, many = [], []
+    for _ in range(rounds):
+        one.append(rounds_of(single, reps=reps, rounds=1, warm=0)[0] / per)
+        many.append(forced_batch())
+    one, many = sorted(one), sorted(many)
+    o, m, spread = one[len(one) // 2], many[len(many) // 2], one[-1] - one[0]
+    res[name] = {"vectors": g, "batch_ms": round(m, 5), "single_calls_ms": round(o, 5), "single_calls_rounds_ms": [round(t, 5) for t in one],
+                 "batch_rounds_ms": [round(t, 5) for t in many], "single_calls_spread_ms": round(spread, 5), "speedup": round(o / m, 3),
+                 "batch_faster_by_more_than_the_spread": bool(o - m > spread),
+                 "GB/s_per_vector_batch": round(g * nbytes_single / m / 1e6, 1), "GB/s_single_calls": round(g * nbytes_single / o / 1e6, 1)}
+
+
+if any(selected(r) for r in F16_BATCH_ROWS):
+    for nb in (32768, 65536):
+        if not any(selected(f"f16_mvm_batch{g}_{nb}^2") for g in F16_GROUPS):
+            continue
+        hA = hip.alloc(2 * nb * nb)
+        f16_fill(hA, nb * nb, 63)
+        bx, br = [hip.alloc(2 * nb) for _ in range(8)], [hip.alloc(2 * nb) for _ in range(8)]
+        for j, b in enumerate(bx):
+            f16_fill(b, nb, 300 + j)
+        for g in F16_GROUPS:
+            def singles(g=g):
+                for j in range(g):
+                    hip.check(lib.clm_f16_mvm(hA.ptr, nb, nb, bx[j].ptr, br[j].ptr, None))
+            rec_pair_alternated(f"f16_mvm_batch{g}_{nb}^2", 2 * nb * nb + 4 * nb, g, singles,
+                                lambda g=g, a=(ptrs(bx[:g]), ptrs(br[:g])): hip.check(lib.clm_f16_mvm_batch(hA.ptr, nb, nb, g, a[0], a[1], None)),
+                                reps=10 if nb == 32768 else 4)
+        del hA, bx, br
+    im, inn, ig, iters = 4096, 8192, 8, 10
+    if any(selected(r) for r in F16_BATCH_ROWS[2 * len(F16_GROUPS):]):
+        P, PT = hip.alloc(2 * im * inn), hip.alloc(2 * im * inn)
+        f16_fill(P, im * inn, 68)
+        hip.check(lib.clm_f16_transpose(P.ptr, im, inn, PT.ptr, None))
+        V = {k: [hip.alloc(2 * ln) for _ in range(ig)] for k, ln in dict(y=im, x=inn, t1=im, t2=im, t3=inn, r=inn).items()}
+        for k in ("y", "x", "t2"):
+            for j, b in enumerate(V[k]):
+                f16_fill(b, b.nbytes // 2, 500 + 10 * j + len(k))
+        for sg in F16_GROUPS:
+            def saa_singles(sg=sg):
+                for j in range(sg):
+                    hip.check(lib.clm_f16_mvm_scale_and_add(PT.ptr, inn, im, V["t2"][j].ptr, V["x"][j].ptr, 2.0 ** -24, V["t3"][j].ptr, V["r"][j].ptr, None))
+            rec_pair_alternated(f"f16_mvm_saa_batch{sg}_8192x4096", 2 * im * inn + 2 * im + 6 * inn, sg, saa_singles,
+                                lambda sg=sg, a=tuple(ptrs(V[k][:sg]) for k in ("t2", "x", "t3", "r")): hip.check(
+                                    lib.clm_f16_mvm_scale_and_add_batch(PT.ptr, inn, im, sg, a[0], a[1], 2.0 ** -24, a[2], a[3], None)), reps=20)
+
+        def iht_singles():
+            for j in range(ig):
+                hip.check(lib.clm_f16_iht(P.ptr, PT.ptr, im, inn, V["x"][j].ptr, inn, V["y"][j].ptr, V["t1"][j].ptr, V["t2"][j].ptr, V["t3"][j].ptr,
+                                          iters, inn // 4, 2.0 ** -24, 1, None))
+        A = {k: ptrs(v) for k, v in V.items()}
+        rec_pair_alternated("f16_iht_batch8_N8192", 2 * 2 * im * inn, ig, iht_singles,
+                            lambda: hip.check(lib.clm_f16_iht_batch(P.ptr, PT.ptr, im, inn, ig, A["x"], inn, A["y"], A["t1"], A["t2"], A["t3"], iters,
+                                                                    inn // 4, 2.0 ** -24, 1, None)), reps=2, per=iters)
+        if "f16_iht_batch8_N8192" in res:
+            res["f16_iht_batch8_N8192"]["note"] = (f"ms per iteration for all 8 signals, calls of {iters} iterations, K = n / 4, FAST threshold; the single "
+                                                   "calls are 8 x clm_f16_iht (three launches per iteration and signal)")
+        del P, PT, V, A
+    if ONLY and all(any(o in r for r in F16_BATCH_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
 
 
 if not ONLY or any("f16" in o and not o.startswith(F16_FUSED_ROWS) for o in ONLY.split(",")):
