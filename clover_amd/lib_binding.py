@@ -231,6 +231,16 @@ SIGNATURES_BATCH_F16 = {
 }
 
 
+# name -> (restype, argtypes); everything include/clover_hip_f16_t.h declares (the transposed half-precision mvm, A' x straight from a
+# CloverMatrix16's own bytes: f16 and fp32 vectors, the fused form, the IHT / GD loop that holds one matrix)
+SIGNATURES_F16_T = {
+    "clm_f16_mvm_transposed": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm_f16_mvm_f32_transposed": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm_f16_mvm_transposed_scale_and_add": (C.c_int, [_vp, _u64, _u64, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "clm_f16_iht_one_matrix": (C.c_int, [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
+}
+
+
 class CloverHipError(RuntimeError):
     pass
 
@@ -245,7 +255,7 @@ def load_library(path: str | Path | None = None, allow_probe: bool = False) -> C
             "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = C.CDLL(str(p))
     for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items(), *SIGNATURES_BATCH_T8.items(), *SIGNATURES_BATCH_T_V8.items(),
-                              *SIGNATURES_BATCH_F16.items()):
+                              *SIGNATURES_BATCH_F16.items(), *SIGNATURES_F16_T.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -849,6 +859,41 @@ class CloverHip:
             self.check(self.lib.clv_memset(v[name].ptr, prefill, v[name].nbytes, None))
         self.check(self.lib.clm_f16_iht(b[0].ptr, b[1].ptr, m, n, v["x"].ptr, n if x_len is None else x_len, b[2].ptr, v["t1"].ptr, v["t2"].ptr,
                                         v["t3"].ptr, iterations, K, mu, threshold, None))
+        return {name: v[name].download(np.uint16, ln) for name, ln in lens.items()}
+
+    # A' x straight from A (clover_hip_f16_t.h): x has `rows` elements, the results `cols`.  hA may be a DevBuf (a matrix uploaded once)
+    def mf16_mvm_transposed(self, hA, rows, cols, hx) -> np.ndarray:
+        dA = hA if isinstance(hA, DevBuf) else self.to_device(hA)
+        dx, dr = self.to_device(hx), self.alloc(max(2 * cols, 2))
+        self.check(self.lib.clm_f16_mvm_transposed(dA.ptr, rows, cols, dx.ptr, dr.ptr, None))
+        return dr.download(np.uint16, cols)
+
+    def mf16_mvm_f32_transposed(self, hA, rows, cols, x) -> np.ndarray:
+        dA = hA if isinstance(hA, DevBuf) else self.to_device(hA)
+        dx, dr = self.to_device(np.ascontiguousarray(x, dtype=np.float32)), self.alloc(max(4 * cols, 4))
+        self.check(self.lib.clm_f16_mvm_f32_transposed(dA.ptr, rows, cols, dx.ptr, dr.ptr, None))
+        return dr.download(np.float32, cols)
+
+    def mf16_mvm_transposed_scale_and_add(self, hA, rows, cols, hx, hu, a: float, in_place: bool = False, want_t: bool = True):
+        """(t, r) of clm_f16_mvm_transposed_scale_and_add; t is None when want_t is False"""
+        dA = hA if isinstance(hA, DevBuf) else self.to_device(hA)
+        dx, du = self.to_device(hx), self.to_device(hu)
+        dt = self.alloc(max(2 * cols, 2)) if want_t else None
+        dr = du if in_place else self.alloc(max(2 * cols, 2))
+        self.check(self.lib.clm_f16_mvm_transposed_scale_and_add(dA.ptr, rows, cols, dx.ptr, du.ptr, a, dt.ptr if dt else None, dr.ptr, None))
+        return (dt.download(np.uint16, cols) if want_t else None), dr.download(np.uint16, cols)
+
+    def mf16_iht_one_matrix(self, hPhi, m, n, hy, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None, prefill: int = 0x55):
+        """clm_f16_iht_one_matrix on buffers prefilled with `prefill` bytes: {"x": bits, "t1": ..., "t2": ..., "t3": ...}"""
+        dPhi = hPhi if isinstance(hPhi, DevBuf) else self.to_device(hPhi)
+        dy = self.to_device(hy)
+        lens = {"x": n, "t1": m, "t2": m, "t3": n}
+        v = {}
+        for name, ln in lens.items():
+            v[name] = self.alloc(2 * ln)
+            self.check(self.lib.clv_memset(v[name].ptr, prefill, v[name].nbytes, None))
+        self.check(self.lib.clm_f16_iht_one_matrix(dPhi.ptr, m, n, v["x"].ptr, n if x_len is None else x_len, dy.ptr, v["t1"].ptr, v["t2"].ptr,
+                                                   v["t3"].ptr, iterations, K, mu, threshold, None))
         return {name: v[name].download(np.uint16, ln) for name, ln in lens.items()}
 
     # several CloverVector16 with one CloverMatrix16 (clover_hip_batch_f16.h; host arrays of device pointers; lists in, lists out)

@@ -458,6 +458,21 @@ inline void Q_GD<CloverMatrix16, CloverVector16>(CloverMatrix16 &Phi, CloverMatr
     Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, 0, mu, false);
 }
 
+/* Q_IHT / Q_GD on this pair holding ONE matrix: Phi' t2 comes straight from Phi's own bytes (CloverMatrix16::iht_loop_one_matrix ->
+ * clm_f16_iht_one_matrix, clover_hip_f16_t.h), the bits of Q_IHT / Q_GD above with PhiT = transpose(Phi) and the same launches per
+ * iteration.  Opt-in by name: Q_IHT / Q_GD themselves keep two matrices. */
+inline void Q_IHT_one_matrix(CloverMatrix16 &Phi, CloverVector16 &x, CloverVector16 &y, CloverVector16 &t1, CloverVector16 &t2, CloverVector16 &t3,
+                             const uint64_t iterations, const uint64_t K, const float mu)
+{
+    Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, K, mu, true);
+}
+
+inline void Q_GD_one_matrix(CloverMatrix16 &Phi, CloverVector16 &x, CloverVector16 &y, CloverVector16 &t1, CloverVector16 &t2, CloverVector16 &t3,
+                            const uint64_t iterations, const float mu)
+{
+    Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, 0, mu, false);
+}
+
 /* the same for `count` signals with ONE half-precision Phi (CloverMatrix16::iht_loop_batch -> clm_f16_iht_batch, clover_hip_batch_f16.h): per
  * iteration two fused launches and one threshold for a group of signals; bit-identical to calling Q_IHT / Q_GD above signal after signal.
  * Unconditional, as those: the 16-bit classes have no stochastic rounding; the threshold follows the exactness switch (FAST under

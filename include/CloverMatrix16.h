@@ -14,6 +14,10 @@
  *
  *   mvm_scaleAndAdd                      -> clm_f16_mvm_scale_and_add  (not in the reference: mvm + the scaleAndAdd behind it, one launch)
  *   iht_loop                             -> clm_f16_iht        (the whole Q_IHT / Q_GD loop of 01_measure.h:923-946, 999-1021 in one call)
+ *   mvm_transposed / mvm_transposed_scaleAndAdd / iht_loop_one_matrix
+ *                                        -> clm_f16_mvm_transposed, clm_f16_mvm_f32_transposed, clm_f16_mvm_transposed_scale_and_add,
+ *                                           clm_f16_iht_one_matrix (clover_hip_f16_t.h; not in the reference: this' * x straight from this
+ *                                           matrix's own bytes, no stored transpose, bit-identical to transpose() + the methods above)
  *   mvm_batch / mvm_scaleAndAdd_batch / iht_loop_batch
  *                                        -> clm_f16_mvm_batch, clm_f16_mvm_scale_and_add_batch, clm_f16_iht_batch (clover_hip_batch_f16.h;
  *                                           not in the reference: the same for several vectors in ONE pass over the matrix per group of
@@ -33,6 +37,7 @@
 #include "CloverVector16.h"
 #include "CloverVector32.h"
 #include "clover_hip_batch_f16.h"  /* the batched half-precision calls: a header of their own beside clover_hip.h */
+#include "clover_hip_f16_t.h"      /* the transposed half-precision calls: likewise */
 
 class CloverMatrix16 {
 protected:
@@ -55,6 +60,15 @@ protected:
     void check_mvm(const V &productVector, const R &resultVector) const
     {
         if (productVector.size_pad() != getCols() || resultVector.size_pad() != getRows()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+    }
+    /* the sizes of this' * x: x has as many elements as this has rows, the result as many as it has columns */
+    template <class V, class R>
+    void check_mvm_transposed(const V &productVector, const R &resultVector) const
+    {
+        if (productVector.size_pad() != getRows() || resultVector.size_pad() != getCols()) {
             std::cout << "MVM can not be performed. Exiting ..." << std::endl;
             exit(1);
         }
@@ -193,6 +207,62 @@ public:
         clover_hip::check(clm_f16_iht(dev_values(), PhiT.dev_values(), rows, cols, x.dev_values_wo(), x.size(), y.dev_values_ro(),
                                       t1.dev_values_wo(), t2.dev_values_wo(), t3.dev_values_wo(), iterations, K, mu, thr, nullptr),
                           "CloverMatrix16::iht_loop");
+        x.commit();
+        if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
+    }
+    /* Not in the reference: resultVector = this' * productVector from this matrix's own bytes (clm_f16_mvm_transposed), bit for bit what
+     * transpose(T); T.mvm(productVector, resultVector) gives, without the second matrix. */
+    void mvm_transposed(const CloverVector16 &productVector, CloverVector16 &resultVector) const
+    {
+        check_mvm_transposed(productVector, resultVector);
+        clover_hip::check(clm_f16_mvm_transposed(dev_values(), rows, cols, productVector.dev_values_ro(), resultVector.dev_values_wo(), nullptr),
+                          "CloverMatrix16::mvm_transposed");
+        resultVector.commit();
+    }
+    /* fp32 vector in, fp32 vector out (clm_f16_mvm_f32_transposed): the bits of transpose(T); T.mvm(productVector, resultVector) */
+    void mvm_transposed(const CloverVector32 &productVector, CloverVector32 &resultVector) const
+    {
+        check_mvm_transposed(productVector, resultVector);
+        clover_hip::check(clm_f16_mvm_f32_transposed(dev_values(), rows, cols, productVector.device_ro(), resultVector.device_wo(), nullptr),
+                          "CloverMatrix16::mvm_transposed");
+        resultVector.commit();
+    }
+    /* t = this' * x immediately followed by r = f16(u + a * t) (clm_f16_mvm_transposed_scale_and_add): one launch, the bits of
+     * transpose(T); T.mvm_scaleAndAdd(x, u, a, t, r) */
+    void mvm_transposed_scaleAndAdd(const CloverVector16 &x, const CloverVector16 &u, float a, CloverVector16 &t, CloverVector16 &r) const
+    {
+        check_mvm_transposed(x, t);
+        if (u.size_pad() != getCols() || r.size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        clover_hip::check(clm_f16_mvm_transposed_scale_and_add(dev_values(), rows, cols, x.dev_values_ro(), u.dev_values_ro(), a, t.dev_values_wo(),
+                                                               r.dev_values_wo(), nullptr), "CloverMatrix16::mvm_transposed_scaleAndAdd");
+        t.commit();
+        r.commit();
+    }
+    /* in place: u = f16(u + a * (this' * x)) */
+    void mvm_transposed_scaleAndAdd(const CloverVector16 &x, CloverVector16 &u, float a, CloverVector16 &t) const
+    {
+        check_mvm_transposed(x, t);
+        if (u.size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        uint16_t *du = u.dev_values_rw();
+        clover_hip::check(clm_f16_mvm_transposed_scale_and_add(dev_values(), rows, cols, x.dev_values_ro(), du, a, t.dev_values_wo(), du, nullptr),
+                          "CloverMatrix16::mvm_transposed_scaleAndAdd");
+        t.commit();
+        u.commit();
+    }
+    /* iht_loop with no PhiT (clm_f16_iht_one_matrix): the bits of iht_loop with PhiT = transpose of this, the same three launches per
+     * iteration (two without threshold), half the resident matrix bytes; DESIGN.md 3 has what that costs per iteration. */
+    void iht_loop_one_matrix(CloverVector16 &x, const CloverVector16 &y, CloverVector16 &t1, CloverVector16 &t2, CloverVector16 &t3,
+                             uint64_t iterations, uint64_t K, float mu, bool with_threshold) const
+    {
+        if (x.size_pad() != getCols() || y.size_pad() != getRows() || t1.size_pad() != getRows() || t2.size_pad() != getRows() ||
+            t3.size_pad() != getCols()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm_f16_iht_one_matrix(dev_values(), rows, cols, x.dev_values_wo(), x.size(), y.dev_values_ro(), t1.dev_values_wo(),
+                                                 t2.dev_values_wo(), t3.dev_values_wo(), iterations, K, mu, thr, nullptr),
+                          "CloverMatrix16::iht_loop_one_matrix");
         x.commit();
         if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
     }

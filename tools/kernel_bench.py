@@ -989,6 +989,84 @@ if any(selected(r) for r in M8T_ROWS):
         sys.exit(0)
 
 
+SLAB = 1 << 28
+
+
+def f16_fill(dst, count, seed):
+    """count f16 values = quantized random fp32 integers in [-10, 10], through a 1 GiB fp32 slab"""
+    src = hip.alloc(4 * min(SLAB, count))
+    for o in range(0, count, SLAB):
+        c = min(SLAB, count - o)
+        hip.check(lib.clv_fill_random_ints_f32(src.ptr, c, 10, seed, o, None))
+        hip.check(lib.clv_f16_quantize(src.ptr, c, dst.ptr + 2 * o, None))
+    hip.sync()
+
+
+# ---- A' x for a CloverMatrix16 straight from A (half16_t.hip): the three rows per size of the blocks above with clm_f16_mvm_transposed,
+# clm_f16_transpose + clm_f16_mvm and clm_f16_mvm on a held A', rounds alternated in one session; f16_iht_one_matrix_N8192:
+# clm_f16_iht_one_matrix against clm_f16_iht (the loop of f16_iht_loop_N8192: 4096 x 8192, FAST threshold, launch per step either way).
+# KB_ONLY=f16_mvm_transposed,f16_transpose_then_mvm,f16_mvm_held_transpose,f16_iht_one_matrix selects them and the run ends after them.
+F16T_ROWS = tuple(f"{k}_{nb}" for nb in MVT_SIZES for k in ("f16_mvm_transposed", "f16_transpose_then_mvm", "f16_mvm_held_transpose")) + \
+    ("f16_iht_one_matrix_N8192",)
+
+if any(selected(r) for r in F16T_ROWS):
+    for nb in MVT_SIZES:
+        if not any(selected(r) for r in F16T_ROWS if r.endswith(f"_{nb}")):
+            continue
+        hA, hAt = hip.alloc(2 * nb * nb), hip.alloc(2 * nb * nb)
+        f16_fill(hA, nb * nb, 64)
+        hx, hr = hip.alloc(2 * nb), hip.alloc(2 * nb)
+        f16_fill(hx, nb, 311)
+        hip.check(lib.clm_f16_transpose(hA.ptr, nb, nb, hAt.ptr, None))
+
+        def direct_f16():
+            hip.check(lib.clm_f16_mvm_transposed(hA.ptr, nb, nb, hx.ptr, hr.ptr, None))
+
+        def pair_f16():
+            hip.check(lib.clm_f16_transpose(hA.ptr, nb, nb, hAt.ptr, None))
+            hip.check(lib.clm_f16_mvm(hAt.ptr, nb, nb, hx.ptr, hr.ptr, None))
+
+        def held_f16():
+            hip.check(lib.clm_f16_mvm(hAt.ptr, nb, nb, hx.ptr, hr.ptr, None))
+        d, p, h = alternated((direct_f16, pair_f16, held_f16), reps=20 if nb == 8192 else 10 if nb == 32768 else 4)
+        mat_b = 2 * nb * nb
+        one_b = mat_b + 4 * nb
+        md, mp, mh = d[len(d) // 2], p[len(p) // 2], h[len(h) // 2]
+        for name, t, m, nbytes in ((f"f16_mvm_transposed_{nb}", d, md, one_b), (f"f16_transpose_then_mvm_{nb}", p, mp, 2 * mat_b + one_b),
+                                   (f"f16_mvm_held_transpose_{nb}", h, mh, one_b)):
+            res[name] = {"ms": round(m, 5), "rounds_ms": [round(v, 5) for v in t], "spread_ms": round(t[-1] - t[0], 5),
+                         "GB/s": round(nbytes / m / 1e6, 1), "frac_of_8TBs": round(nbytes / m / 1e6 / 8000.0, 4)}
+        res[f"f16_mvm_transposed_{nb}"].update({
+            "speedup_over_transpose_then_mvm": round(mp / md, 3), "faster_than_the_pair_by_more_than_its_spread": bool(mp - md > p[-1] - p[0]),
+            "ratio_to_mvm_on_a_held_transpose": round(md / mh, 3), "within_the_spread_of_the_held_transpose_call": bool(abs(md - mh) <= h[-1] - h[0])})
+        del hA, hAt, hx, hr
+    if selected("f16_iht_one_matrix_N8192"):
+        im, inn, iters = 4096, 8192, 20
+        P, PT = hip.alloc(2 * im * inn), hip.alloc(2 * im * inn)
+        f16_fill(P, im * inn, 65)
+        hip.check(lib.clm_f16_transpose(P.ptr, im, inn, PT.ptr, None))
+        vy, vx, vt1, vt2, vt3 = (hip.alloc(2 * n) for n in (im, inn, im, im, inn))
+        f16_fill(vy, im, 501)
+        tail = (vx.ptr, inn, vy.ptr, vt1.ptr, vt2.ptr, vt3.ptr, iters, im // 4, 2.0 ** -24, 1, None)
+
+        def two_f16():
+            hip.check(lib.clm_f16_iht(P.ptr, PT.ptr, im, inn, *tail))
+
+        def one_f16():
+            hip.check(lib.clm_f16_iht_one_matrix(P.ptr, im, inn, *tail))
+        t2, t1 = ([v / iters for v in t] for t in alternated((two_f16, one_f16), reps=2))
+        m2, m1 = t2[len(t2) // 2], t1[len(t1) // 2]
+        res["f16_iht_one_matrix_N8192"] = {
+            "one_matrix_ms_per_iteration": round(m1, 5), "clm_f16_iht_ms_per_iteration": round(m2, 5),
+            "one_matrix_rounds_ms": [round(v, 5) for v in t1], "clm_f16_iht_rounds_ms": [round(v, 5) for v in t2],
+            "ratio_to_clm_f16_iht": round(m1 / m2, 3), "within_the_spread_of_clm_f16_iht": bool(abs(m1 - m2) <= t2[-1] - t2[0]),
+            "note": f"calls of {iters} iterations, 4096 x 8192, K = m / 4, FAST threshold; both loops are launch per step"}
+        del P, PT
+    if ONLY and all(any(o in r for r in F16T_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
+
+
 # ---- vector ops at n = 2^30 (4 GiB fp32 source, 512 MiB + 64 MiB quantized) and n = 2^24
 for logn in (24, 30):
     n = 1 << logn
@@ -1187,19 +1265,6 @@ F16_BATCH_ROWS = tuple(f"f16_mvm_batch{g}_{nb}^2" for nb in (32768, 65536) for g
     tuple(f"f16_mvm_saa_batch{g}_8192x4096" for g in F16_GROUPS) + ("f16_iht_batch8_N8192",)
 F16_FUSED_ROWS = ("f16_mvm_scale_and_add", "f16_threshold_fast_n8192", "f16_q_iht_iteration", "f16_iht_loop", "f16_gd_loop", "f16_mvm_batch",
                   "f16_mvm_saa_batch", "f16_iht_batch")
-SLAB = 1 << 28
-
-
-def f16_fill(dst, count, seed):
-    """count f16 values = quantized random fp32 integers in [-10, 10], through a 1 GiB fp32 slab"""
-    src = hip.alloc(4 * min(SLAB, count))
-    for o in range(0, count, SLAB):
-        c = min(SLAB, count - o)
-        hip.check(lib.clv_fill_random_ints_f32(src.ptr, c, 10, seed, o, None))
-        hip.check(lib.clv_f16_quantize(src.ptr, c, dst.ptr + 2 * o, None))
-    hip.sync()
-
-
 # ---- several CloverVector16 with one CloverMatrix16 (half16_batch.hip): every row pairs the batch call, on the batched kernel
 # (CLV_MVM_BATCH=1), with the same vectors issued as single calls -- the rounds of the two ALTERNATED in one process, so that a drift of
 # the clocks lands on both.  f16_mvm_batch{2,4,8}_{32768,65536}^2: the plain mvm (streaming); f16_mvm_saa_batch{2,4,8}_8192x4096: the fused
