@@ -8,7 +8,7 @@
 //
 // The host side is a small driver of its own (the driver of the other families, mvm_batch_host.h, carries scale pointers and draw positions
 // throughout); it shares with them mvm_batch_forced(), the overlap check, the launch counter and CLM4_MVM_BATCH_MAX.
-#include "half16_device.h"
+#include "half16_batch.h"
 #include "mvm_batch_host.h"
 
 #include "clover_hip_batch_f16.h"
@@ -127,18 +127,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4)))
         }
 }
 
-// ---- host driver -------------------------------------------------------------------------------------------------------------
-// the vectors of a call (host arrays of device pointers).  u == NULL: the plain mvm, r[j] = f16(A x[j]).  Else the fused form: t[j] =
-// f16(A x[j]) (t == NULL: not stored), r[j] = f16(fma(f32(t[j]), a, f32(u[j])))
-struct F16BatchVectors {
-    const uint16_t *const *x;
-    const uint16_t *const *u;
-    float a;
-    uint16_t *const *t;
-    uint16_t *const *r;
-    F16BatchVectors from(uint64_t j0) const { return {x + j0, u ? u + j0 : nullptr, a, t ? t + j0 : nullptr, r + j0}; }
-};
-
+// ---- host driver (F16BatchVectors, the vectors of a call: half16_batch.h) ------------------------------------------------------
 template <int NV, int WAVES>
 static void f16_batch_launch_form(const uint16_t *A, uint64_t rows, uint64_t cols, int nv, const F16BatchArgs<NV> &arg, const F16BatchFuse<NV> &fuse,
                                   bool fused, hipStream_t st)
@@ -176,8 +165,8 @@ static int f16_batch_launch(const uint16_t *A, uint64_t rows, uint64_t cols, uin
     return CLV_OK;
 }
 
-// a group of g <= CLM4_MVM_BATCH_MAX vectors on the smallest instantiation that holds it
-static int f16_batch_launch_group(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t g, const F16BatchVectors &v, hipStream_t st)
+// a group of g <= CLM4_MVM_BATCH_MAX vectors on the smallest instantiation that holds it (half16_t_batch.hip runs step 1 of its loop on it)
+int f16_batch_launch_group(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t g, const F16BatchVectors &v, hipStream_t st)
 {
     return g <= 2 ? f16_batch_launch<2>(A, rows, cols, g, v, st) : g <= 4 ? f16_batch_launch<4>(A, rows, cols, g, v, st) : f16_batch_launch<8>(A, rows, cols, g, v, st);
 }

@@ -241,6 +241,16 @@ SIGNATURES_F16_T = {
 }
 
 
+# name -> (restype, argtypes); everything include/clover_hip_batch_f16_t.h declares (the batched transposed half-precision mvm, A' x[j]
+# for several CloverVector16 in one pass over a CloverMatrix16's own bytes: plain, fused, the IHT / GD loop for several signals that holds
+# one matrix)
+SIGNATURES_BATCH_F16_T = {
+    "clm_f16_mvm_transposed_batch": (C.c_int, [_vp, _u64, _u64, _u64, _vp, _vp, _vp]),
+    "clm_f16_mvm_transposed_scale_and_add_batch": (C.c_int, [_vp, _u64, _u64, _u64, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "clm_f16_iht_batch_one_matrix": (C.c_int, [_vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
+}
+
+
 class CloverHipError(RuntimeError):
     pass
 
@@ -255,7 +265,7 @@ def load_library(path: str | Path | None = None, allow_probe: bool = False) -> C
             "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = C.CDLL(str(p))
     for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items(), *SIGNATURES_BATCH_T8.items(), *SIGNATURES_BATCH_T_V8.items(),
-                              *SIGNATURES_BATCH_F16.items(), *SIGNATURES_F16_T.items()):
+                              *SIGNATURES_BATCH_F16.items(), *SIGNATURES_F16_T.items(), *SIGNATURES_BATCH_F16_T.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -936,6 +946,49 @@ class CloverHip:
         pa = self.ptr_array
         self.check(self.lib.clm_f16_iht_batch(dPhi.ptr, dPhiT.ptr, m, n, len(hys), pa(v["x"]), n if x_len is None else x_len, pa(dy), pa(v["t1"]),
                                               pa(v["t2"]), pa(v["t3"]), iterations, K, mu, threshold, None))
+        return [{name: v[name][j].download(np.uint16, ln) for name, ln in lens.items()} for j in range(len(hys))]
+
+    # A' x[j] for several CloverVector16 straight from A (clover_hip_batch_f16_t.h): every x has `rows` elements, the results `cols`
+    def mf16_mvm_transposed_batch(self, hA, rows, cols, hxs, prefill: int = 0xEE):
+        """hxs: list of x bit patterns; returns the list of r of clm_f16_mvm_transposed_batch.  hA may be a DevBuf (a matrix uploaded once)"""
+        dA = hA if isinstance(hA, DevBuf) else self.to_device(hA)
+        dx = [self.to_device(h) for h in hxs]
+        dr = [self.alloc(max(2 * cols, 2)) for _ in hxs]
+        for d in dr:
+            self.check(self.lib.clv_memset(d.ptr, prefill, d.nbytes, None))
+        pa = self.ptr_array
+        self.check(self.lib.clm_f16_mvm_transposed_batch(dA.ptr, rows, cols, len(hxs), pa(dx), pa(dr), None))
+        return [r.download(np.uint16, cols) for r in dr]
+
+    def mf16_mvm_transposed_scale_and_add_batch(self, hA, rows, cols, hxs, hus, a: float, in_place: bool = False, want_t: bool = True,
+                                                prefill: int = 0xEE):
+        """hxs, hus: lists of bit patterns; returns the list of (t, r) of clm_f16_mvm_transposed_scale_and_add_batch.  t is always
+        allocated and prefilled; with want_t False the call is given no t array and the (untouched) buffer is returned all the same"""
+        dA = hA if isinstance(hA, DevBuf) else self.to_device(hA)
+        dx, du = [self.to_device(h) for h in hxs], [self.to_device(h) for h in hus]
+        dt = [self.alloc(max(2 * cols, 2)) for _ in hxs]
+        dr = du if in_place else [self.alloc(max(2 * cols, 2)) for _ in hxs]
+        for d in dt + ([] if in_place else dr):
+            self.check(self.lib.clv_memset(d.ptr, prefill, d.nbytes, None))
+        pa = self.ptr_array
+        self.check(self.lib.clm_f16_mvm_transposed_scale_and_add_batch(dA.ptr, rows, cols, len(hxs), pa(dx), pa(du), a, pa(dt) if want_t else None,
+                                                                       pa(dr), None))
+        return [(dt[j].download(np.uint16, cols), dr[j].download(np.uint16, cols)) for j in range(len(hxs))]
+
+    def mf16_iht_batch_one_matrix(self, hPhi, m, n, hys, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+                                  prefill: int = 0x55):
+        """clm_f16_iht_batch_one_matrix on buffers prefilled with `prefill` bytes; hys: list of y bit patterns; returns per signal
+        {"x": bits, "t1": ..., "t2": ..., "t3": ...}.  hPhi may be a DevBuf"""
+        dPhi = hPhi if isinstance(hPhi, DevBuf) else self.to_device(hPhi)
+        dy = [self.to_device(h) for h in hys]
+        lens = {"x": n, "t1": m, "t2": m, "t3": n}
+        v = {name: [self.alloc(max(2 * ln, 2)) for _ in hys] for name, ln in lens.items()}
+        for bufs in v.values():
+            for d in bufs:
+                self.check(self.lib.clv_memset(d.ptr, prefill, d.nbytes, None))
+        pa = self.ptr_array
+        self.check(self.lib.clm_f16_iht_batch_one_matrix(dPhi.ptr, m, n, len(hys), pa(v["x"]), n if x_len is None else x_len, pa(dy), pa(v["t1"]),
+                                                         pa(v["t2"]), pa(v["t3"]), iterations, K, mu, threshold, None))
         return [{name: v[name][j].download(np.uint16, ln) for name, ln in lens.items()} for j in range(len(hys))]
 
     def mf16_transpose(self, h, rows, cols) -> np.ndarray:

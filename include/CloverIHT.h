@@ -490,6 +490,23 @@ inline void Q_GD_batch(CloverMatrix16 &Phi, CloverMatrix16 &PhiT, CloverVector16
     Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
 }
 
+/* `count` signals holding ONE half-precision matrix: both of the above at once (CloverMatrix16::iht_loop_batch_one_matrix ->
+ * clm_f16_iht_batch_one_matrix, clover_hip_batch_f16_t.h).  Bit-identical to Q_IHT_one_matrix / Q_GD_one_matrix signal after signal, and
+ * through those to Q_IHT_batch / Q_GD_batch with PhiT = transpose(Phi).  Opt-in by name. */
+inline void Q_IHT_batch_one_matrix(CloverMatrix16 &Phi, CloverVector16 *const *x, CloverVector16 *const *y, CloverVector16 *const *t1,
+                                   CloverVector16 *const *t2, CloverVector16 *const *t3, const uint64_t count, const uint64_t iterations,
+                                   const uint64_t K, const float mu)
+{
+    Phi.iht_loop_batch_one_matrix(x, y, t1, t2, t3, count, iterations, K, mu, true);
+}
+
+inline void Q_GD_batch_one_matrix(CloverMatrix16 &Phi, CloverVector16 *const *x, CloverVector16 *const *y, CloverVector16 *const *t1,
+                                  CloverVector16 *const *t2, CloverVector16 *const *t3, const uint64_t count, const uint64_t iterations,
+                                  const float mu)
+{
+    Phi.iht_loop_batch_one_matrix(x, y, t1, t2, t3, count, iterations, 0, mu, false);
+}
+
 #ifdef CLOVER_FP32_ON_DEVICE
 /* CloverMatrix32 with CloverVector32 vectors under -DCLOVER_FP32_ON_DEVICE: the fp32 baseline of every table of the reference, on the
  * device.  The whole loop in one call (CloverMatrix32::iht_loop -> clm_f32_iht): three launches per iteration, two for Q_GD, the bits of

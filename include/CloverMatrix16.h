@@ -22,6 +22,11 @@
  *                                        -> clm_f16_mvm_batch, clm_f16_mvm_scale_and_add_batch, clm_f16_iht_batch (clover_hip_batch_f16.h;
  *                                           not in the reference: the same for several vectors in ONE pass over the matrix per group of
  *                                           CLM4_MVM_BATCH_MAX, bit-identical to the single methods vector after vector)
+ *   mvm_transposed_batch / mvm_transposed_scaleAndAdd_batch / iht_loop_batch_one_matrix
+ *                                        -> clm_f16_mvm_transposed_batch, clm_f16_mvm_transposed_scale_and_add_batch,
+ *                                           clm_f16_iht_batch_one_matrix (clover_hip_batch_f16_t.h; not in the reference: this' * x[j] for
+ *                                           several vectors in ONE pass over this matrix's own bytes, bit-identical to the single
+ *                                           transposed methods vector after vector)
  *
  * Q_IHT<CloverMatrix16, CloverVector16> and Q_GD<...> are specialised in CloverIHT.h (which includes this header) and call iht_loop: every
  * step is a kernel on the device mirrors, nothing is copied back between steps.
@@ -38,6 +43,7 @@
 #include "CloverVector32.h"
 #include "clover_hip_batch_f16.h"  /* the batched half-precision calls: a header of their own beside clover_hip.h */
 #include "clover_hip_f16_t.h"      /* the transposed half-precision calls: likewise */
+#include "clover_hip_batch_f16_t.h" /* the batched transposed half-precision calls: likewise */
 
 class CloverMatrix16 {
 protected:
@@ -311,6 +317,67 @@ public:
         const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
         clover_hip::check(clm_f16_iht_batch(dev_values(), PhiT.dev_values(), rows, cols, count, px.data(), count ? x[0]->size() : 0, py.data(),
                                             p1.data(), p2.data(), p3.data(), iterations, K, mu, thr, nullptr), "CloverMatrix16::iht_loop_batch");
+        for (uint64_t j = 0; j < count; j++) {
+            x[j]->commit();
+            if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }
+        }
+    }
+    /* the size rules of mvm_transposed_scaleAndAdd, vector by vector; r == NULL: the in-place form */
+    void check_fused_transposed_batch(const CloverVector16 *const *x, const CloverVector16 *const *u, CloverVector16 *const *t,
+                                      CloverVector16 *const *r, uint64_t count) const
+    {
+        for (uint64_t j = 0; j < count; j++) {
+            check_mvm_transposed(*x[j], *t[j]);
+            if (u[j]->size_pad() != getCols() || (r && r[j]->size_pad() != getCols())) batch_exit("Vectors do not have the same size. Exiting ...");
+        }
+    }
+    /* Not in the reference: this' * x[j] for `count` vectors in ONE pass over this matrix's own bytes per group of CLM4_MVM_BATCH_MAX
+     * (clm_f16_mvm_transposed_batch); r[j] equals what mvm_transposed(*x[j], *r[j]) gives, bit for bit.  The x[j] may repeat; the r[j]
+     * are distinct and none of them is an x. */
+    void mvm_transposed_batch(const CloverVector16 *const *x, CloverVector16 *const *r, uint64_t count) const
+    {
+        for (uint64_t j = 0; j < count; j++) check_mvm_transposed(*x[j], *r[j]);
+        const DevArray px = dev_inputs(x, count), pr = dev_outputs(r, count, false);
+        clover_hip::check(clm_f16_mvm_transposed_batch(dev_values(), rows, cols, count, px.data(), pr.data(), nullptr),
+                          "CloverMatrix16::mvm_transposed_batch");
+        for (uint64_t j = 0; j < count; j++) r[j]->commit();
+    }
+    /* mvm_transposed_scaleAndAdd for `count` vectors: t[j] = this' * x[j], r[j] = f16(u[j] + a * t[j]), the matrix read once per group
+     * (clm_f16_mvm_transposed_scale_and_add_batch); the bits of the loop of mvm_transposed_scaleAndAdd. */
+    void mvm_transposed_scaleAndAdd_batch(const CloverVector16 *const *x, const CloverVector16 *const *u, float a, CloverVector16 *const *t,
+                                          CloverVector16 *const *r, uint64_t count) const
+    {
+        check_fused_transposed_batch(x, u, t, r, count);
+        const DevArray px = dev_inputs(x, count), pu = dev_inputs(u, count), pt = dev_outputs(t, count, false), pr = dev_outputs(r, count, false);
+        clover_hip::check(clm_f16_mvm_transposed_scale_and_add_batch(dev_values(), rows, cols, count, px.data(), pu.data(), a, pt.data(), pr.data(),
+                                                                     nullptr), "CloverMatrix16::mvm_transposed_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
+    }
+    /* in place: u[j] = f16(u[j] + a * (this' * x[j])); u[j] is mapped read-write and is both the call's u and its r */
+    void mvm_transposed_scaleAndAdd_batch(const CloverVector16 *const *x, CloverVector16 *const *u, float a, CloverVector16 *const *t,
+                                          uint64_t count) const
+    {
+        check_fused_transposed_batch(x, u, t, nullptr, count);
+        const DevArray px = dev_inputs(x, count), pu = dev_outputs(u, count, true), pt = dev_outputs(t, count, false);
+        clover_hip::check(clm_f16_mvm_transposed_scale_and_add_batch(dev_values(), rows, cols, count, px.data(), pu.data(), a, pt.data(), pu.data(),
+                                                                     nullptr), "CloverMatrix16::mvm_transposed_scaleAndAdd_batch");
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
+    }
+    /* iht_loop_batch with no PhiT (clm_f16_iht_batch_one_matrix): x[j], t1[j], t2[j], t3[j] end as iht_loop_one_matrix(*x[j], *y[j], ...)
+     * leaves them, bit for bit; half the resident matrix bytes.  All x[j] have one size(). */
+    void iht_loop_batch_one_matrix(CloverVector16 *const *x, const CloverVector16 *const *y, CloverVector16 *const *t1, CloverVector16 *const *t2,
+                                   CloverVector16 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu, bool with_threshold) const
+    {
+        for (uint64_t j = 0; j < count; j++)
+            if (x[j]->size_pad() != getCols() || y[j]->size_pad() != getRows() || t1[j]->size_pad() != getRows() || t2[j]->size_pad() != getRows() ||
+                t3[j]->size_pad() != getCols() || x[j]->size() != x[0]->size())
+                batch_exit("MVM can not be performed. Exiting ...");
+        const DevArray py = dev_inputs(y, count), px = dev_outputs(x, count, false), p1 = dev_outputs(t1, count, false),
+                       p2 = dev_outputs(t2, count, false), p3 = dev_outputs(t3, count, false);
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm_f16_iht_batch_one_matrix(dev_values(), rows, cols, count, px.data(), count ? x[0]->size() : 0, py.data(), p1.data(),
+                                                       p2.data(), p3.data(), iterations, K, mu, thr, nullptr),
+                          "CloverMatrix16::iht_loop_batch_one_matrix");
         for (uint64_t j = 0; j < count; j++) {
             x[j]->commit();
             if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }

@@ -1270,29 +1270,39 @@ F16_FUSED_ROWS = ("f16_mvm_scale_and_add", "f16_threshold_fast_n8192", "f16_q_ih
 # the clocks lands on both.  f16_mvm_batch{2,4,8}_{32768,65536}^2: the plain mvm (streaming); f16_mvm_saa_batch{2,4,8}_8192x4096: the fused
 # x += mu Phi' t2 step of the IHT shape (cache-resident); f16_iht_batch8_N8192: clm_f16_iht_batch against 8 x clm_f16_iht, ms per iteration
 # for 8 signals.  KB_ONLY=f16_mvm_batch,f16_mvm_saa_batch,f16_iht_batch selects them and the run ends after them.
-def rec_pair_alternated(name, nbytes_single, g, single, batch, reps=10, per=1, rounds=5):
+def rec_pair_alternated(name, nbytes_single, g, single, batch, reps=10, per=1, rounds=5, held=None):
+    """held: a second baseline (a batch call on a stored transpose), timed forced batched in every round beside the two sides"""
     if not selected(name):
         return
 
-    def forced_batch():
+    def forced_batch(fn=batch):
         os.environ["CLV_MVM_BATCH"] = "1"
         try:
-            return rounds_of(batch, reps=reps, rounds=1, warm=0)[0] / per
+            return rounds_of(fn, reps=reps, rounds=1, warm=0)[0] / per
         finally:
             os.environ.pop("CLV_MVM_BATCH", None)
     os.environ.pop("CLV_MVM_BATCH", None)
     rounds_of(single, reps=1, rounds=1, warm=1)
     forced_batch()
-    one, many = [], []
+    one, many, other = [], [], []
+    if held:
+        forced_batch(held)
     for _ in range(rounds):
         one.append(rounds_of(single, reps=reps, rounds=1, warm=0)[0] / per)
         many.append(forced_batch())
+        if held:
+            other.append(forced_batch(held))
     one, many = sorted(one), sorted(many)
     o, m, spread = one[len(one) // 2], many[len(many) // 2], one[-1] - one[0]
     res[name] = {"vectors": g, "batch_ms": round(m, 5), "single_calls_ms": round(o, 5), "single_calls_rounds_ms": [round(t, 5) for t in one],
                  "batch_rounds_ms": [round(t, 5) for t in many], "single_calls_spread_ms": round(spread, 5), "speedup": round(o / m, 3),
                  "batch_faster_by_more_than_the_spread": bool(o - m > spread),
                  "GB/s_per_vector_batch": round(g * nbytes_single / m / 1e6, 1), "GB/s_single_calls": round(g * nbytes_single / o / 1e6, 1)}
+    if held:
+        other = sorted(other)
+        h = other[len(other) // 2]
+        res[name].update({"held_transpose_batch_ms": round(h, 5), "held_transpose_batch_rounds_ms": [round(t, 5) for t in other],
+                          "held_transpose_batch_spread_ms": round(other[-1] - other[0], 5), "batch_over_held_transpose_batch": round(m / h, 3)})
 
 
 if any(selected(r) for r in F16_BATCH_ROWS):
@@ -1342,6 +1352,92 @@ if any(selected(r) for r in F16_BATCH_ROWS):
                                                    "calls are 8 x clm_f16_iht (three launches per iteration and signal)")
         del P, PT, V, A
     if ONLY and all(any(o in r for r in F16_BATCH_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
+
+
+# ---- A' x[j] for several CloverVector16 straight from one CloverMatrix16 (half16_t_batch.hip): every row pairs the batch call, on the
+# batched kernel (CLV_MVM_BATCH=1), with two baselines on the same vectors in the same process, rounds alternated: (a) the g single
+# transposed calls and (b) the row-major batch call on a held transpose.  f16_mvm_transposed_batch{g}_{32768,65536}: the plain product
+# (streaming); f16_mvm_transposed_saa_batch{g}_{8192x4096,65536^2}: the fused x += mu Phi' t2 step, on the IHT shape (Phi 4096 x 8192,
+# cache-resident) and streaming; f16_iht_batch_one_matrix_N8192: clm_f16_iht_batch_one_matrix against 8 x clm_f16_iht_one_matrix and
+# against clm_f16_iht_batch with a held transpose, ms per iteration for 8 signals.  g = 2, 4, 8, or KB_F16_BATCH_GROUPS.
+# KB_ONLY=f16_mvm_transposed_batch,f16_mvm_transposed_saa_batch,f16_iht_batch_one_matrix selects them and the run ends after them.
+F16TB_ROWS = tuple(f"f16_mvm_transposed_batch{g}_{nb}" for nb in (32768, 65536) for g in F16_GROUPS) + \
+    tuple(f"f16_mvm_transposed_saa_batch{g}_{sz}" for sz in ("8192x4096", "65536^2") for g in F16_GROUPS) + ("f16_iht_batch_one_matrix_N8192",)
+if any(selected(r) for r in F16TB_ROWS):
+    for nb in (32768, 65536):
+        plain = any(selected(f"f16_mvm_transposed_batch{g}_{nb}") for g in F16_GROUPS)
+        fused = nb == 65536 and any(selected(f"f16_mvm_transposed_saa_batch{g}_65536^2") for g in F16_GROUPS)
+        if not (plain or fused):
+            continue
+        hA, hAt = hip.alloc(2 * nb * nb), hip.alloc(2 * nb * nb)
+        f16_fill(hA, nb * nb, 63)
+        hip.check(lib.clm_f16_transpose(hA.ptr, nb, nb, hAt.ptr, None))
+        bx, bu, bt, br = ([hip.alloc(2 * nb) for _ in range(8)] for _ in range(4))
+        for j in range(8):
+            f16_fill(bx[j], nb, 300 + j)
+            f16_fill(bu[j], nb, 400 + j)
+        for g in F16_GROUPS:
+            a = tuple(ptrs(v[:g]) for v in (bx, bu, bt, br))
+
+            def singles(g=g):
+                for j in range(g):
+                    hip.check(lib.clm_f16_mvm_transposed(hA.ptr, nb, nb, bx[j].ptr, br[j].ptr, None))
+            if plain:
+                rec_pair_alternated(f"f16_mvm_transposed_batch{g}_{nb}", 2 * nb * nb + 4 * nb, g, singles,
+                                    lambda g=g, a=a: hip.check(lib.clm_f16_mvm_transposed_batch(hA.ptr, nb, nb, g, a[0], a[3], None)),
+                                    reps=10 if nb == 32768 else 4,
+                                    held=lambda g=g, a=a: hip.check(lib.clm_f16_mvm_batch(hAt.ptr, nb, nb, g, a[0], a[3], None)))
+
+            def saa_singles(g=g):
+                for j in range(g):
+                    hip.check(lib.clm_f16_mvm_transposed_scale_and_add(hA.ptr, nb, nb, bx[j].ptr, bu[j].ptr, 2.0 ** -24, bt[j].ptr, br[j].ptr, None))
+            if fused:
+                rec_pair_alternated(f"f16_mvm_transposed_saa_batch{g}_65536^2", 2 * nb * nb + 8 * nb, g, saa_singles,
+                                    lambda g=g, a=a: hip.check(lib.clm_f16_mvm_transposed_scale_and_add_batch(hA.ptr, nb, nb, g, a[0], a[1], 2.0 ** -24,
+                                                                                                              a[2], a[3], None)), reps=4,
+                                    held=lambda g=g, a=a: hip.check(lib.clm_f16_mvm_scale_and_add_batch(hAt.ptr, nb, nb, g, a[0], a[1], 2.0 ** -24,
+                                                                                                        a[2], a[3], None)))
+        del hA, hAt, bx, bu, bt, br
+    im, inn, ig, iters = 4096, 8192, 8, 10
+    if any(selected(r) for r in F16TB_ROWS if "8192" in r.split("_")[-1]):
+        P, PT = hip.alloc(2 * im * inn), hip.alloc(2 * im * inn)
+        f16_fill(P, im * inn, 68)
+        hip.check(lib.clm_f16_transpose(P.ptr, im, inn, PT.ptr, None))
+        V = {k: [hip.alloc(2 * ln) for _ in range(ig)] for k, ln in dict(y=im, x=inn, t1=im, t2=im, t3=inn, r=inn).items()}
+        for k in ("y", "x", "t2"):
+            for j, b in enumerate(V[k]):
+                f16_fill(b, b.nbytes // 2, 500 + 10 * j + len(k))
+        for sg in F16_GROUPS:
+            a = tuple(ptrs(V[k][:sg]) for k in ("t2", "x", "t3", "r"))
+
+            def step_singles(sg=sg):
+                for j in range(sg):
+                    hip.check(lib.clm_f16_mvm_transposed_scale_and_add(P.ptr, im, inn, V["t2"][j].ptr, V["x"][j].ptr, 2.0 ** -24, V["t3"][j].ptr,
+                                                                       V["r"][j].ptr, None))
+            rec_pair_alternated(f"f16_mvm_transposed_saa_batch{sg}_8192x4096", 2 * im * inn + 2 * im + 6 * inn, sg, step_singles,
+                                lambda sg=sg, a=a: hip.check(lib.clm_f16_mvm_transposed_scale_and_add_batch(P.ptr, im, inn, sg, a[0], a[1], 2.0 ** -24,
+                                                                                                            a[2], a[3], None)), reps=20,
+                                held=lambda sg=sg, a=a: hip.check(lib.clm_f16_mvm_scale_and_add_batch(PT.ptr, inn, im, sg, a[0], a[1], 2.0 ** -24,
+                                                                                                      a[2], a[3], None)))
+
+        def iht1_singles():
+            for j in range(ig):
+                hip.check(lib.clm_f16_iht_one_matrix(P.ptr, im, inn, V["x"][j].ptr, inn, V["y"][j].ptr, V["t1"][j].ptr, V["t2"][j].ptr, V["t3"][j].ptr,
+                                                     iters, inn // 4, 2.0 ** -24, 1, None))
+        A = {k: ptrs(v) for k, v in V.items()}
+        rec_pair_alternated("f16_iht_batch_one_matrix_N8192", 2 * 2 * im * inn, ig, iht1_singles,
+                            lambda: hip.check(lib.clm_f16_iht_batch_one_matrix(P.ptr, im, inn, ig, A["x"], inn, A["y"], A["t1"], A["t2"], A["t3"], iters,
+                                                                               inn // 4, 2.0 ** -24, 1, None)), reps=2, per=iters,
+                            held=lambda: hip.check(lib.clm_f16_iht_batch(P.ptr, PT.ptr, im, inn, ig, A["x"], inn, A["y"], A["t1"], A["t2"], A["t3"], iters,
+                                                                         inn // 4, 2.0 ** -24, 1, None)))
+        if "f16_iht_batch_one_matrix_N8192" in res:
+            res["f16_iht_batch_one_matrix_N8192"]["note"] = (f"ms per iteration for all 8 signals, calls of {iters} iterations, K = n / 4, FAST threshold; "
+                                                             "the single calls are 8 x clm_f16_iht_one_matrix (three launches per iteration and signal); "
+                                                             "held = clm_f16_iht_batch with a stored transpose")
+        del P, PT, V, A
+    if ONLY and all(any(o in r for r in F16TB_ROWS) for o in ONLY.split(",")):
         print(json.dumps(res, indent=1))
         sys.exit(0)
 
