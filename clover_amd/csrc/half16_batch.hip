@@ -6,12 +6,10 @@
 // bytes of a lane once, widens them once and runs, per vector, one 16-byte LDS read of x and the 8 fmas of f16_chain_step on the lane's 8
 // chains: per vector the instruction sequence of k_f16_mvm (half16.hip), so the results equal the single calls bit for bit.
 //
-// The host side is a small driver of its own (the driver of the other families, mvm_batch_host.h, carries scale pointers and draw positions
-// throughout); it shares with them mvm_batch_forced(), the overlap check, the launch counter and CLM4_MVM_BATCH_MAX.
-#include "half16_batch.h"
-#include "mvm_batch_host.h"
-
-#include "clover_hip_batch_f16.h"
+// The host side is half16_batch_host.h, shared with the transposed family (half16_t_batch.hip) and a driver of its own beside that of the
+// other families (mvm_batch_host.h carries scale pointers and draw positions throughout); it shares with them mvm_batch_forced(), the
+// overlap check, the launch counter and CLM4_MVM_BATCH_MAX.  The traits of this family, F16Batch, are declared there.
+#include "half16_batch_host.h"
 
 // Columns of x staged in LDS per pass: 512 per wave of the workgroup, i.e. every thread stages ONE 16-byte piece per vector and chunk in
 // either workgroup form.  The 64-row form holds 4 KiB of binary16 per vector, 32 KiB at NV = 8 -- by LDS alone five workgroups per CU, one
@@ -127,10 +125,10 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4)))
         }
 }
 
-// ---- host driver (F16BatchVectors, the vectors of a call: half16_batch.h) ------------------------------------------------------
+// ---- launches: declared in half16_batch_host.h, instantiated here for the driver's NV = 2, 4, 8 ----------------------------------------
 template <int NV, int WAVES>
-static void f16_batch_launch_form(const uint16_t *A, uint64_t rows, uint64_t cols, int nv, const F16BatchArgs<NV> &arg, const F16BatchFuse<NV> &fuse,
-                                  bool fused, hipStream_t st)
+static void f16_batch_launch_form(hipStream_t st, const uint16_t *A, uint64_t rows, uint64_t cols, int nv, const F16BatchArgs<NV> &arg,
+                                  const F16BatchFuse<NV> &fuse, bool fused)
 {
     const dim3 grid((unsigned)((rows + 16 * WAVES - 1) / (16 * WAVES))), block(64 * WAVES);
     // nontemporal loads by the rule of the single calls: once the matrix cannot live in the 256 MiB Infinity Cache
@@ -143,187 +141,43 @@ static void f16_batch_launch_form(const uint16_t *A, uint64_t rows, uint64_t col
     }
 }
 
-// one launch for the first g <= NV vectors of v; the workgroup form by the rule of the single calls (f16_mvm_wide)
+// the kernel's two argument structs from the slots; the workgroup form by the rule of the single calls (f16_mvm_wide)
 template <int NV>
-static int f16_batch_launch(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t g, const F16BatchVectors &v, hipStream_t st)
+void F16Batch::launch(hipStream_t st, const uint16_t *A, uint64_t rows, uint64_t cols, int nv, const F16BatchSlots<NV> &s)
 {
     F16BatchArgs<NV> arg;
     F16BatchFuse<NV> fuse;
-    const bool fused = v.u != nullptr;
-    for (uint64_t i = 0; i < NV; i++) {
-        const bool in = i < g;
-        arg.x[i] = in ? v.x[i] : nullptr;
-        arg.r[i] = !in ? nullptr : fused ? (v.t ? v.t[i] : nullptr) : v.r[i];
-        fuse.u[i] = in && fused ? v.u[i] : nullptr;
-        fuse.r2[i] = in && fused ? v.r[i] : nullptr;
+    for (int i = 0; i < NV; i++) {
+        arg.x[i] = s.x[i];
+        arg.r[i] = s.r[i];
+        fuse.u[i] = s.u[i];
+        fuse.r2[i] = s.r2[i];
     }
-    fuse.a = v.a;
-    if (f16_mvm_wide(rows)) f16_batch_launch_form<NV, 4>(A, rows, cols, (int)g, arg, fuse, fused, st);
-    else f16_batch_launch_form<NV, 1>(A, rows, cols, (int)g, arg, fuse, fused, st);
-    CLV_LAUNCH_CHECK();
-    clv_internal_mvm_batch_count();
-    return CLV_OK;
+    fuse.a = s.a;
+    if (f16_mvm_wide(rows)) f16_batch_launch_form<NV, 4>(st, A, rows, cols, nv, arg, fuse, s.fused);
+    else f16_batch_launch_form<NV, 1>(st, A, rows, cols, nv, arg, fuse, s.fused);
 }
+template void F16Batch::launch<2>(hipStream_t, const uint16_t *, uint64_t, uint64_t, int, const F16BatchSlots<2> &);
+template void F16Batch::launch<4>(hipStream_t, const uint16_t *, uint64_t, uint64_t, int, const F16BatchSlots<4> &);
+template void F16Batch::launch<8>(hipStream_t, const uint16_t *, uint64_t, uint64_t, int, const F16BatchSlots<8> &);
 
-// a group of g <= CLM4_MVM_BATCH_MAX vectors on the smallest instantiation that holds it (half16_t_batch.hip runs step 1 of its loop on it)
-int f16_batch_launch_group(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t g, const F16BatchVectors &v, hipStream_t st)
-{
-    return g <= 2 ? f16_batch_launch<2>(A, rows, cols, g, v, st) : g <= 4 ? f16_batch_launch<4>(A, rows, cols, g, v, st) : f16_batch_launch<8>(A, rows, cols, g, v, st);
-}
-
-// Whether a group of g vectors of a call of two or more runs as one batched launch or as g single launches.  CLV_MVM_BATCH = 1 / 0 forces
-// one or the other for every group -- forced to 1 a remainder group of ONE vector (nvec = 9, 17, ...) runs batched too, so that a forced
-// call is ceil(nvec / 8) batched launches and nothing else.  Unset = the rule measured on the MI355X ("Several vectors, one
-// CloverMatrix16 pass"; profiles/f16_mvm_batch_kernel_bench.json, profiles/f16_mvm_batch_groups_kernel_bench.json): batched exactly where
-// the batched launch beat the single calls by more than their spread --
-//   a streaming matrix (above the 256 MiB rule; 65536^2 and 32768^2): every group of two or more (2: 1.95 x ... 8: 4.1 - 5.1 x);
-//   a cache-resident one (the fused step at 8192 x 4096, 64 MiB): groups of three or more (3: 1.03 x, 4: 1.17, 8: 1.28); TWO vectors lost
-//   to the two single calls (0.95 x) and are forwarded.
-// Not measured: matrices between 64 MiB and 1 GiB, below 64 MiB, and streaming matrices of fewer than 32768 rows (the 16-row form).
-static bool f16_batch_selected(uint64_t g, uint64_t rows, uint64_t cols)
-{
-    const int force = mvm_batch_forced();
-    if (force >= 0) return force != 0;
-    return g >= (F16_STREAMING(rows * cols * 2) ? 2u : 3u);
-}
-
-// the checked arguments of clm_f16_mvm_batch (v.u == NULL) / clm_f16_mvm_scale_and_add_batch on the stream, group by group
-static int f16_batch_run(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t nvec, const F16BatchVectors &v, void *stream)
-{
-    for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
-        const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        int rc = CLV_OK;
-        if (!f16_batch_selected(g, rows, cols)) {
-            for (uint64_t j = j0; j < j0 + g && !rc; j++)
-                rc = v.u ? clm_f16_mvm_scale_and_add(A, rows, cols, v.x[j], v.u[j], v.a, v.t ? v.t[j] : nullptr, v.r[j], stream)
-                         : clm_f16_mvm(A, rows, cols, v.x[j], v.r[j], stream);
-        } else {
-            rc = f16_batch_launch_group(A, rows, cols, g, v.from(j0), as_stream(stream));
-        }
-        if (rc) return rc;
-    }
-    return CLV_OK;
-}
-
-// every check of the two mvm batch calls, before any device work: the single calls' size and alignment rules, then the arrays, the
-// entries, the aliases the single calls refuse by name and the overlap check.  u == NULL and t == NULL in the plain call.
-static int f16_batch_check_args(const char *fn, const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t nvec, const uint16_t *const *x,
-                                const uint16_t *const *u, uint16_t *const *t, uint16_t *const *r, bool fused)
-{
-    CLV_REQUIRE(A, "%s: null pointer", fn);
-    CLV_REQUIRE(F16_ALIGNED(A), "%s: the matrix and x must be 16-byte aligned", fn);
-    CLV_REQUIRE(cols % 128 == 0, "%s: cols=%llu must be a multiple of 128", fn, (unsigned long long)cols);
-    CLV_REQUIRE(rows / 16 < 0x7FFFFFFFull, "%s: matrix too large", fn);
-    if (!nvec) return CLV_OK;
-    CLV_REQUIRE(x && r && (!fused || u), "%s: null pointer array", fn);
-    for (uint64_t j = 0; j < nvec; j++)
-        CLV_REQUIRE(x[j] && r[j] && (!fused || u[j]) && (!t || t[j]), "%s: null pointer in vector %llu", fn, (unsigned long long)j);
-    for (uint64_t j = 0; j < nvec; j++) {
-        CLV_REQUIRE(F16_ALIGNED(x[j]), "%s: the matrix and x must be 16-byte aligned (x of vector %llu)", fn, (unsigned long long)j);
-        CLV_REQUIRE(((uintptr_t)r[j] & 1u) == 0 && (!fused || ((uintptr_t)u[j] & 1u) == 0) && (!t || ((uintptr_t)t[j] & 1u) == 0),
-                    "%s: u, t and r must be 2-byte aligned (vector %llu)", fn, (unsigned long long)j);
-        CLV_REQUIRE(r[j] != x[j] && (!t || t[j] != x[j]), "%s: the results of vector %llu must not alias the vector being multiplied", fn,
-                    (unsigned long long)j);
-        CLV_REQUIRE(!t || (t[j] != r[j] && t[j] != u[j]), "%s: t of vector %llu must not alias r or u", fn, (unsigned long long)j);
-    }
-    std::vector<ClvRange> rg;
-    rg.reserve(4 * nvec + 1);
-    const uint64_t xb = cols * 2, rb = rows * 2;
-    rg.push_back(clv_range(A, rows * cols * 2, false, ~0ull, "A"));
-    for (uint64_t j = 0; j < nvec; j++) {
-        rg.push_back(clv_range(x[j], xb, false, j, "x"));
-        rg.push_back(clv_range(r[j], rb, true, j, "r"));
-        // the in-place form r[j] == u[j]: the result IS the input, only the lane that owns a row touches it in either
-        if (fused && r[j] != u[j]) rg.push_back(clv_range(u[j], rb, false, j, "u"));
-        if (t) rg.push_back(clv_range(t[j], rb, true, j, "t"));
-    }
-    return clv_internal_check_ranges(fn, rg);
-}
-
-// ---- C ABI -------------------------------------------------------------------------------------------------------------------
+// ---- C ABI (include/clover_hip_batch_f16.h) ------------------------------------------------------------------------------------------
 extern "C" int clm_f16_mvm_batch(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t nvec, const uint16_t *const *x, uint16_t *const *r,
                                  void *stream)
 {
-    int rc = f16_batch_check_args("clm_f16_mvm_batch", A, rows, cols, nvec, x, nullptr, nullptr, r, false);
-    if (rc) return rc;
-    if (!nvec || !rows) return CLV_OK;
-    if (nvec == 1) return clm_f16_mvm(A, rows, cols, x[0], r[0], stream);
-    return f16_batch_run(A, rows, cols, nvec, {x, nullptr, 0.0f, nullptr, r}, stream);
+    return f16_batch_entry<F16Batch>("clm_f16_mvm_batch", A, rows, cols, nvec, x, r, stream);
 }
 
 extern "C" int clm_f16_mvm_scale_and_add_batch(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t nvec, const uint16_t *const *x,
                                                const uint16_t *const *u, float a, uint16_t *const *t, uint16_t *const *r, void *stream)
 {
-    int rc = f16_batch_check_args("clm_f16_mvm_scale_and_add_batch", A, rows, cols, nvec, x, u, t, r, true);
-    if (rc) return rc;
-    if (!nvec || !rows) return CLV_OK;
-    if (nvec == 1) return clm_f16_mvm_scale_and_add(A, rows, cols, x[0], u[0], a, t ? t[0] : nullptr, r[0], stream);
-    return f16_batch_run(A, rows, cols, nvec, {x, u, a, t, r}, stream);
+    return f16_batch_fused_entry<F16Batch>("clm_f16_mvm_scale_and_add_batch", A, rows, cols, nvec, x, u, a, t, r, stream);
 }
 
-// Q_IHT / Q_GD for nvec signals with one Phi: the loop of clm_f16_iht (half16.hip) with every step batched.  Per iteration and group two
-// fused launches and, with a threshold, one clv_f16_threshold_batch.  Bit-identical to clm_f16_iht per signal.
-#define F16_IHTB "clm_f16_iht_batch"
+// Q_IHT / Q_GD for nvec signals with Phi and a held PhiT (f16_batch_iht, half16_batch_host.h)
 extern "C" int clm_f16_iht_batch(const uint16_t *Phi, const uint16_t *PhiT, uint64_t m, uint64_t n, uint64_t nvec, uint16_t *const *x, uint64_t x_len,
                                  const uint16_t *const *y, uint16_t *const *t1, uint16_t *const *t2, uint16_t *const *t3, uint64_t iterations,
                                  uint64_t K, float mu, int threshold, void *stream)
 {
-    CLV_REQUIRE(Phi && PhiT, F16_IHTB ": null pointer");
-    CLV_REQUIRE(m % 128 == 0 && n % 128 == 0 && x_len <= n, F16_IHTB ": m=%llu n=%llu x_len=%llu", (unsigned long long)m, (unsigned long long)n,
-                (unsigned long long)x_len);
-    CLV_REQUIRE(threshold >= 0 && threshold <= 2, F16_IHTB ": unknown threshold %d", threshold);
-    CLV_REQUIRE(F16_ALIGNED(Phi) && F16_ALIGNED(PhiT), F16_IHTB ": the matrices, x and t2 must be 16-byte aligned");
-    CLV_REQUIRE(m / 16 < 0x7FFFFFFFull && n / 16 < 0x7FFFFFFFull, F16_IHTB ": matrix too large");
-    if (!nvec) return CLV_OK;
-    CLV_REQUIRE(x && y && t1 && t2 && t3, F16_IHTB ": null pointer array");
-    for (uint64_t j = 0; j < nvec; j++)
-        CLV_REQUIRE(x[j] && y[j] && t1[j] && t2[j] && t3[j], F16_IHTB ": null pointer in vector %llu", (unsigned long long)j);
-    for (uint64_t j = 0; j < nvec; j++) {
-        CLV_REQUIRE(F16_ALIGNED(x[j]) && F16_ALIGNED(t2[j]), F16_IHTB ": the matrices, x and t2 must be 16-byte aligned (vector %llu)",
-                    (unsigned long long)j);
-        CLV_REQUIRE((((uintptr_t)y[j] | (uintptr_t)t1[j] | (uintptr_t)t3[j]) & 1u) == 0, F16_IHTB ": y, t1 and t3 must be 2-byte aligned (vector %llu)",
-                    (unsigned long long)j);
-    }
-    {   // the range check of mvm_batch_iht without its scale arrays
-        std::vector<ClvRange> rg;
-        rg.reserve(5 * nvec + 2);
-        const uint64_t mb = m * 2, nb = n * 2;
-        rg.push_back(clv_range(Phi, m * n * 2, false, ~0ull, "Phi"));
-        rg.push_back(clv_range(PhiT, m * n * 2, false, ~0ull, "PhiT"));
-        for (uint64_t j = 0; j < nvec; j++) {
-            rg.push_back(clv_range(y[j], mb, false, j, "y"));
-            rg.push_back(clv_range(x[j], nb, true, j, "x"));
-            rg.push_back(clv_range(t1[j], mb, true, j, "t1"));
-            rg.push_back(clv_range(t2[j], mb, true, j, "t2"));
-            rg.push_back(clv_range(t3[j], nb, true, j, "t3"));
-        }
-        int rc = clv_internal_check_ranges(F16_IHTB, rg);
-        if (rc) return rc;
-    }
-    const int mode = threshold == 2 ? CLV_THRESHOLD_REFERENCE : CLV_THRESHOLD_FAST;
-    hipStream_t st = as_stream(stream);
-    for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
-        const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        if (nvec == 1 || !(m && n && f16_batch_selected(g, m, n))) {      // one signal, an empty matrix, or forwarded: the single call, signal after signal
-            for (uint64_t j = j0; j < j0 + g; j++) {
-                int rc = clm_f16_iht(Phi, PhiT, m, n, x[j], x_len, y[j], t1[j], t2[j], t3[j], iterations, K, mu, threshold, stream);
-                if (rc) return rc;
-            }
-            continue;
-        }
-        for (uint64_t j = j0; j < j0 + g; j++) {
-            int rc = clv_internal_f16_clear(x[j], n, st);                                   // x.clear()
-            if (rc) return rc;
-        }
-        const F16BatchVectors step1 = {x + j0, y + j0, -1.0f, t1 + j0, t2 + j0};            // t1 = Phi x; t2 = y - t1
-        const F16BatchVectors step2 = {t2 + j0, x + j0, mu, t3 + j0, x + j0};               // t3 = Phi' t2; x += mu t3
-        for (uint64_t it = 0; it < iterations; it++) {
-            int rc = f16_batch_launch_group(Phi, m, n, g, step1, st);
-            if (!rc) rc = f16_batch_launch_group(PhiT, n, m, g, step2, st);
-            if (!rc && threshold) rc = clv_f16_threshold_batch(x + j0, g, x_len, n, K, mode, stream);      // keep the K largest
-            if (rc) return rc;
-        }
-    }
-    return CLV_OK;
+    return f16_batch_iht<F16Batch>("clm_f16_iht_batch", Phi, PhiT, m, n, nvec, x, x_len, y, t1, t2, t3, iterations, K, mu, threshold, stream);
 }
-#undef F16_IHTB

@@ -14,11 +14,9 @@
 //               the conversion and the fused epilogue written as in k_f16_mvm_t.  u[v][col] is fetched before the walk, so r[v] may be u[v].
 // Slots v >= nv are absent: never staged, never accumulated, never stored, their pointers never dereferenced.
 //
-// The host side is a small driver of its own in the style of half16_batch.hip.
-#include "half16_batch.h"
-#include "mvm_batch_host.h"
+// The host side is half16_batch_host.h, shared with the row-major family (half16_batch.hip).
+#include "half16_batch_host.h"
 
-#include "clover_hip_batch_f16.h"
 #include "clover_hip_batch_f16_t.h"
 #include "clover_hip_f16_t.h"
 
@@ -228,200 +226,88 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         }
 }
 
-// ---- host driver -------------------------------------------------------------------------------------------------------------
-// one launch for the first g <= NV vectors of v (F16BatchVectors, half16_batch.h: here x[j] has `rows` elements, the others `cols`)
+// ---- what differs from the row-major family (half16_batch_host.h) --------------------------------------------------------------------
+struct F16TBatch {
+    // the size and alignment rules of clm_f16_mvm_transposed (half16_t.hip)
+    static int check_matrix(const char *fn, const uint16_t *A, uint64_t rows, uint64_t cols)
+    {
+        CLV_REQUIRE(A, "%s: null pointer", fn);
+        CLV_REQUIRE(rows % 128 == 0 && cols % 128 == 0, "%s: rows=%llu cols=%llu must be multiples of 128", fn, (unsigned long long)rows,
+                    (unsigned long long)cols);
+        CLV_REQUIRE(F16_ALIGNED(A), "%s: the matrix and x must be 16-byte aligned", fn);
+        CLV_REQUIRE(!cols || rows <= 0xFFFFFFFFFFFFull / cols, "%s: matrix too large", fn);
+        CLV_REQUIRE(rows / 32 <= 0x7FFFFFFFull && cols / 64 <= 0x7FFFFFFFull, "%s: matrix too large", fn);
+        return CLV_OK;
+    }
+    // A is rows x cols: x has `rows` elements, r = A' x (and u, t) `cols`
+    static uint64_t x_len(uint64_t rows, uint64_t) { return rows; }
+    static uint64_t r_len(uint64_t, uint64_t cols) { return cols; }
+    // a matrix without rows has nothing to multiply, one without columns nothing to write
+    static bool nothing_to_do(uint64_t nvec, uint64_t rows, uint64_t cols) { return !nvec || !rows || !cols; }
+    // Whether a group of g vectors of a call of two or more runs as one batched launch or as g single transposed launches.  CLV_MVM_BATCH =
+    // 1 / 0 forces one or the other for every group -- forced to 1 a remainder group of ONE vector (nvec = 9, 17, ...) runs batched too, so
+    // that a forced call is ceil(nvec / 8) batched launches and nothing else.  Unset = the rule measured on the MI355X ("A'x for
+    // several CloverVector16, one CloverMatrix16"; profiles/f16_mvm_transposed_batch_kernel_bench.json for 2, 4 and 8 vectors,
+    // profiles/f16_mvm_transposed_batch_groups_kernel_bench.json for 3, 5, 6 and 7): batched exactly where the batched launch beat the g single
+    // transposed calls by more than the spread of their rounds -- which is every group of two or more in both size classes:
+    //   a streaming matrix (above the 256 MiB rule; 32768^2 and 65536^2, plain, and fused at 65536^2): 2: 2.0 x ... 8: 5.2 - 5.3 x;
+    //   a cache-resident one (the fused step on Phi 4096 x 8192, 64 MiB): 2: 1.11 x (0.0281 against 0.0310 ms, spread 0.0004), 3: 1.12,
+    //   4: 1.31, 5: 1.55, 8: 1.93; the loop at N = 8192 for 8 signals 1.49 x.
+    // Not measured: the plain call in the cache-resident class (it takes the fused step's numbers), matrices between 64 MiB and 1 GiB and
+    // below 64 MiB, the loop for groups other than 8.
+    static bool batched_by_rule(uint64_t g, uint64_t, uint64_t) { return g >= 2; }
+    static constexpr auto mvm = clm_f16_mvm_transposed;
+    static constexpr auto scale_and_add = clm_f16_mvm_transposed_scale_and_add;
+    static constexpr auto iht_one_matrix = clm_f16_iht_one_matrix;
+    template <int NV>
+    static void launch(hipStream_t st, const uint16_t *A, uint64_t rows, uint64_t cols, int nv, const F16BatchSlots<NV> &s);
+};
+
+// the kernel's argument struct from the slots; instantiated for the driver's NV = 2, 4, 8
 template <int NV>
-static int f16tb_launch(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t g, const F16BatchVectors &v, hipStream_t st)
+void F16TBatch::launch(hipStream_t st, const uint16_t *A, uint64_t rows, uint64_t cols, int nv, const F16BatchSlots<NV> &s)
 {
     F16TBatchArgs<NV> arg;
-    const bool fused = v.u != nullptr;
-    for (uint64_t i = 0; i < NV; i++) {
-        const bool in = i < g;
-        arg.x[i] = in ? v.x[i] : nullptr;
-        arg.r[i] = !in ? nullptr : fused ? (v.t ? v.t[i] : nullptr) : v.r[i];
-        arg.u[i] = in && fused ? v.u[i] : nullptr;
-        arg.r2[i] = in && fused ? v.r[i] : nullptr;
+    for (int i = 0; i < NV; i++) {
+        arg.x[i] = s.x[i];
+        arg.r[i] = s.r[i];
+        arg.u[i] = s.u[i];
+        arg.r2[i] = s.r2[i];
     }
-    arg.a = v.a;
+    arg.a = s.a;
     const dim3 grid((unsigned)((cols + F16TB_COLS(NV) - 1) / F16TB_COLS(NV))), block(256);
-    const int nv = (int)g;
     // nontemporal loads by the rule of the single calls: once the matrix cannot live in the 256 MiB Infinity Cache
     const bool nt = F16_STREAMING(rows * cols * 2);
-    switch (2 * nt + fused) {
+    switch (2 * nt + s.fused) {
     case 3: hipLaunchKernelGGL((k_f16_mvm_t_batch<NV, true, true>), grid, block, 0, st, A, rows, cols, nv, arg); break;
     case 2: hipLaunchKernelGGL((k_f16_mvm_t_batch<NV, true, false>), grid, block, 0, st, A, rows, cols, nv, arg); break;
     case 1: hipLaunchKernelGGL((k_f16_mvm_t_batch<NV, false, true>), grid, block, 0, st, A, rows, cols, nv, arg); break;
     default: hipLaunchKernelGGL((k_f16_mvm_t_batch<NV, false, false>), grid, block, 0, st, A, rows, cols, nv, arg); break;
     }
-    CLV_LAUNCH_CHECK();
-    clv_internal_mvm_batch_count();
-    return CLV_OK;
 }
+template void F16TBatch::launch<2>(hipStream_t, const uint16_t *, uint64_t, uint64_t, int, const F16BatchSlots<2> &);
+template void F16TBatch::launch<4>(hipStream_t, const uint16_t *, uint64_t, uint64_t, int, const F16BatchSlots<4> &);
+template void F16TBatch::launch<8>(hipStream_t, const uint16_t *, uint64_t, uint64_t, int, const F16BatchSlots<8> &);
 
-// a group of g <= CLM4_MVM_BATCH_MAX vectors on the smallest instantiation that holds it
-static int f16tb_launch_group(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t g, const F16BatchVectors &v, hipStream_t st)
-{
-    return g <= 2 ? f16tb_launch<2>(A, rows, cols, g, v, st) : g <= 4 ? f16tb_launch<4>(A, rows, cols, g, v, st) : f16tb_launch<8>(A, rows, cols, g, v, st);
-}
-
-// Whether a group of g vectors of a call of two or more runs as one batched launch or as g single transposed launches.  CLV_MVM_BATCH =
-// 1 / 0 forces one or the other for every group -- forced to 1 a remainder group of ONE vector (nvec = 9, 17, ...) runs batched too, so
-// that a forced call is ceil(nvec / 8) batched launches and nothing else.  Unset = the rule measured on the MI355X ("A'x for
-// several CloverVector16, one CloverMatrix16"; profiles/f16_mvm_transposed_batch_kernel_bench.json for 2, 4 and 8 vectors,
-// profiles/f16_mvm_transposed_batch_groups_kernel_bench.json for 3, 5, 6 and 7): batched exactly where the batched launch beat the g single
-// transposed calls by more than the spread of their rounds -- which is every group of two or more in both size classes:
-//   a streaming matrix (above the 256 MiB rule; 32768^2 and 65536^2, plain, and fused at 65536^2): 2: 2.0 x ... 8: 5.2 - 5.3 x;
-//   a cache-resident one (the fused step on Phi 4096 x 8192, 64 MiB): 2: 1.11 x (0.0281 against 0.0310 ms, spread 0.0004), 3: 1.12,
-//   4: 1.31, 5: 1.55, 8: 1.93; the loop at N = 8192 for 8 signals 1.49 x.
-// Not measured: the plain call in the cache-resident class (it takes the fused step's numbers), matrices between 64 MiB and 1 GiB and
-// below 64 MiB, the loop for groups other than 8.
-static bool f16tb_selected(uint64_t g, uint64_t, uint64_t)
-{
-    const int force = mvm_batch_forced();
-    if (force >= 0) return force != 0;
-    return g >= 2;
-}
-
-// the checked arguments of clm_f16_mvm_transposed_batch (v.u == NULL) / clm_f16_mvm_transposed_scale_and_add_batch on the stream, group by group
-static int f16tb_run(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t nvec, const F16BatchVectors &v, void *stream)
-{
-    for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
-        const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        int rc = CLV_OK;
-        if (!f16tb_selected(g, rows, cols)) {
-            for (uint64_t j = j0; j < j0 + g && !rc; j++)
-                rc = v.u ? clm_f16_mvm_transposed_scale_and_add(A, rows, cols, v.x[j], v.u[j], v.a, v.t ? v.t[j] : nullptr, v.r[j], stream)
-                         : clm_f16_mvm_transposed(A, rows, cols, v.x[j], v.r[j], stream);
-        } else {
-            rc = f16tb_launch_group(A, rows, cols, g, v.from(j0), as_stream(stream));
-        }
-        if (rc) return rc;
-    }
-    return CLV_OK;
-}
-
-// every check of the two product calls, before any device work: the single transposed call's size and alignment rules, then the arrays,
-// the entries, the aliases the single calls refuse by name and the overlap check -- x sized by the ROWS, r / u / t by the COLUMNS.
-// u == NULL and t == NULL in the plain call.
-static int f16tb_check_args(const char *fn, const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t nvec, const uint16_t *const *x,
-                            const uint16_t *const *u, uint16_t *const *t, uint16_t *const *r, bool fused)
-{
-    CLV_REQUIRE(A, "%s: null pointer", fn);
-    CLV_REQUIRE(rows % 128 == 0 && cols % 128 == 0, "%s: rows=%llu cols=%llu must be multiples of 128", fn, (unsigned long long)rows,
-                (unsigned long long)cols);
-    CLV_REQUIRE(F16_ALIGNED(A), "%s: the matrix and x must be 16-byte aligned", fn);
-    CLV_REQUIRE(!cols || rows <= 0xFFFFFFFFFFFFull / cols, "%s: matrix too large", fn);
-    CLV_REQUIRE(rows / 32 <= 0x7FFFFFFFull && cols / 64 <= 0x7FFFFFFFull, "%s: matrix too large", fn);
-    if (!nvec) return CLV_OK;
-    CLV_REQUIRE(x && r && (!fused || u), "%s: null pointer array", fn);
-    for (uint64_t j = 0; j < nvec; j++)
-        CLV_REQUIRE(x[j] && r[j] && (!fused || u[j]) && (!t || t[j]), "%s: null pointer in vector %llu", fn, (unsigned long long)j);
-    for (uint64_t j = 0; j < nvec; j++) {
-        CLV_REQUIRE(F16_ALIGNED(x[j]), "%s: the matrix and x must be 16-byte aligned (x of vector %llu)", fn, (unsigned long long)j);
-        CLV_REQUIRE(((uintptr_t)r[j] & 1u) == 0 && (!fused || ((uintptr_t)u[j] & 1u) == 0) && (!t || ((uintptr_t)t[j] & 1u) == 0),
-                    "%s: u, t and r must be 2-byte aligned (vector %llu)", fn, (unsigned long long)j);
-        CLV_REQUIRE(r[j] != x[j] && (!t || t[j] != x[j]), "%s: the results of vector %llu must not alias the vector being multiplied", fn,
-                    (unsigned long long)j);
-        CLV_REQUIRE(!t || (t[j] != r[j] && t[j] != u[j]), "%s: t of vector %llu must not alias r or u", fn, (unsigned long long)j);
-    }
-    std::vector<ClvRange> rg;
-    rg.reserve(4 * nvec + 1);
-    const uint64_t xb = rows * 2, rb = cols * 2;
-    rg.push_back(clv_range(A, rows * cols * 2, false, ~0ull, "A"));
-    for (uint64_t j = 0; j < nvec; j++) {
-        rg.push_back(clv_range(x[j], xb, false, j, "x"));
-        rg.push_back(clv_range(r[j], rb, true, j, "r"));
-        // the in-place form r[j] == u[j]: the result IS the input, only the lane that owns a column touches it in either
-        if (fused && r[j] != u[j]) rg.push_back(clv_range(u[j], rb, false, j, "u"));
-        if (t) rg.push_back(clv_range(t[j], rb, true, j, "t"));
-    }
-    return clv_internal_check_ranges(fn, rg);
-}
-
-// ---- C ABI -------------------------------------------------------------------------------------------------------------------
+// ---- C ABI (include/clover_hip_batch_f16_t.h) ----------------------------------------------------------------------------------------
 extern "C" int clm_f16_mvm_transposed_batch(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t nvec, const uint16_t *const *x,
                                             uint16_t *const *r, void *stream)
 {
-    int rc = f16tb_check_args("clm_f16_mvm_transposed_batch", A, rows, cols, nvec, x, nullptr, nullptr, r, false);
-    if (rc) return rc;
-    if (!nvec || !rows || !cols) return CLV_OK;
-    if (nvec == 1) return clm_f16_mvm_transposed(A, rows, cols, x[0], r[0], stream);
-    return f16tb_run(A, rows, cols, nvec, {x, nullptr, 0.0f, nullptr, r}, stream);
+    return f16_batch_entry<F16TBatch>("clm_f16_mvm_transposed_batch", A, rows, cols, nvec, x, r, stream);
 }
 
 extern "C" int clm_f16_mvm_transposed_scale_and_add_batch(const uint16_t *A, uint64_t rows, uint64_t cols, uint64_t nvec, const uint16_t *const *x,
                                                           const uint16_t *const *u, float a, uint16_t *const *t, uint16_t *const *r, void *stream)
 {
-    int rc = f16tb_check_args("clm_f16_mvm_transposed_scale_and_add_batch", A, rows, cols, nvec, x, u, t, r, true);
-    if (rc) return rc;
-    if (!nvec || !rows || !cols) return CLV_OK;
-    if (nvec == 1) return clm_f16_mvm_transposed_scale_and_add(A, rows, cols, x[0], u[0], a, t ? t[0] : nullptr, r[0], stream);
-    return f16tb_run(A, rows, cols, nvec, {x, u, a, t, r}, stream);
+    return f16_batch_fused_entry<F16TBatch>("clm_f16_mvm_transposed_scale_and_add_batch", A, rows, cols, nvec, x, u, a, t, r, stream);
 }
 
-// Q_IHT / Q_GD for nvec signals with ONE matrix: the loop of clm_f16_iht_batch (half16_batch.hip) with Phi' t2 straight from Phi's own
-// bytes.  The checks run once; per group there is one decision, and a selected group costs per iteration two fused launches and, with a
-// threshold, one clv_f16_threshold_batch.  Bit-identical to clm_f16_iht_one_matrix per signal.
-#define F16_IHTB1 "clm_f16_iht_batch_one_matrix"
+// Q_IHT / Q_GD for nvec signals with ONE matrix: step 1 on the row-major family, Phi' t2 straight from Phi's own bytes on this one
+// (f16_batch_iht, half16_batch_host.h)
 extern "C" int clm_f16_iht_batch_one_matrix(const uint16_t *Phi, uint64_t m, uint64_t n, uint64_t nvec, uint16_t *const *x, uint64_t x_len,
                                             const uint16_t *const *y, uint16_t *const *t1, uint16_t *const *t2, uint16_t *const *t3,
                                             uint64_t iterations, uint64_t K, float mu, int threshold, void *stream)
 {
-    CLV_REQUIRE(Phi, F16_IHTB1 ": null pointer");
-    CLV_REQUIRE(m % 128 == 0 && n % 128 == 0 && x_len <= n, F16_IHTB1 ": m=%llu n=%llu x_len=%llu", (unsigned long long)m, (unsigned long long)n,
-                (unsigned long long)x_len);
-    CLV_REQUIRE(threshold >= 0 && threshold <= 2, F16_IHTB1 ": unknown threshold %d", threshold);
-    CLV_REQUIRE(F16_ALIGNED(Phi), F16_IHTB1 ": the matrix, x and t2 must be 16-byte aligned");
-    CLV_REQUIRE(m / 16 < 0x7FFFFFFFull && n / 16 < 0x7FFFFFFFull && (!n || m <= 0xFFFFFFFFFFFFull / n), F16_IHTB1 ": matrix too large");
-    if (!nvec) return CLV_OK;
-    CLV_REQUIRE(x && y && t1 && t2 && t3, F16_IHTB1 ": null pointer array");
-    for (uint64_t j = 0; j < nvec; j++)
-        CLV_REQUIRE(x[j] && y[j] && t1[j] && t2[j] && t3[j], F16_IHTB1 ": null pointer in vector %llu", (unsigned long long)j);
-    for (uint64_t j = 0; j < nvec; j++) {
-        CLV_REQUIRE(F16_ALIGNED(x[j]) && F16_ALIGNED(t2[j]), F16_IHTB1 ": the matrix, x and t2 must be 16-byte aligned (vector %llu)",
-                    (unsigned long long)j);
-        CLV_REQUIRE((((uintptr_t)y[j] | (uintptr_t)t1[j] | (uintptr_t)t3[j]) & 1u) == 0, F16_IHTB1 ": y, t1 and t3 must be 2-byte aligned (vector %llu)",
-                    (unsigned long long)j);
-    }
-    {   // the range check of clm_f16_iht_batch without PhiT
-        std::vector<ClvRange> rg;
-        rg.reserve(5 * nvec + 1);
-        const uint64_t mb = m * 2, nb = n * 2;
-        rg.push_back(clv_range(Phi, m * n * 2, false, ~0ull, "Phi"));
-        for (uint64_t j = 0; j < nvec; j++) {
-            rg.push_back(clv_range(y[j], mb, false, j, "y"));
-            rg.push_back(clv_range(x[j], nb, true, j, "x"));
-            rg.push_back(clv_range(t1[j], mb, true, j, "t1"));
-            rg.push_back(clv_range(t2[j], mb, true, j, "t2"));
-            rg.push_back(clv_range(t3[j], nb, true, j, "t3"));
-        }
-        int rc = clv_internal_check_ranges(F16_IHTB1, rg);
-        if (rc) return rc;
-    }
-    const int mode = threshold == 2 ? CLV_THRESHOLD_REFERENCE : CLV_THRESHOLD_FAST;
-    hipStream_t st = as_stream(stream);
-    for (uint64_t j0 = 0; j0 < nvec; j0 += CLM4_MVM_BATCH_MAX) {
-        const uint64_t g = nvec - j0 < CLM4_MVM_BATCH_MAX ? nvec - j0 : CLM4_MVM_BATCH_MAX;
-        if (nvec == 1 || !(m && n && f16tb_selected(g, m, n))) {      // one signal, an empty matrix, or forwarded: the single call, signal after signal
-            for (uint64_t j = j0; j < j0 + g; j++) {
-                int rc = clm_f16_iht_one_matrix(Phi, m, n, x[j], x_len, y[j], t1[j], t2[j], t3[j], iterations, K, mu, threshold, stream);
-                if (rc) return rc;
-            }
-            continue;
-        }
-        for (uint64_t j = j0; j < j0 + g; j++) {
-            int rc = clv_internal_f16_clear(x[j], n, st);                                   // x.clear()
-            if (rc) return rc;
-        }
-        const F16BatchVectors step1 = {x + j0, y + j0, -1.0f, t1 + j0, t2 + j0};            // t1 = Phi x; t2 = y - t1
-        const F16BatchVectors step2 = {t2 + j0, x + j0, mu, t3 + j0, x + j0};               // t3 = Phi' t2; x += mu t3, in place
-        for (uint64_t it = 0; it < iterations; it++) {
-            int rc = f16_batch_launch_group(Phi, m, n, g, step1, st);
-            if (!rc) rc = f16tb_launch_group(Phi, m, n, g, step2, st);
-            if (!rc && threshold) rc = clv_f16_threshold_batch(x + j0, g, x_len, n, K, mode, stream);      // keep the K largest
-            if (rc) return rc;
-        }
-    }
-    return CLV_OK;
+    return f16_batch_iht<F16Batch, F16TBatch>("clm_f16_iht_batch_one_matrix", Phi, nullptr, m, n, nvec, x, x_len, y, t1, t2, t3, iterations, K, mu,
+                                              threshold, stream);
 }
-#undef F16_IHTB1

@@ -213,17 +213,7 @@ void M8TBatch::launch(dim3 grid, hipStream_t st, const uint8_t *A, const float *
 {
     hipLaunchKernelGGL((k_m8_mvm_t_batch<NV, M8TB_U(NV), NT, FUSE, ST>), grid, dim3(256), 0, st, A, sA, rows, cols, nv, arg, fuse, rs);
 }
-#define M8TB_INST(NV, NT, FUSE, ST)                                                                                                     \
-    template void M8TBatch::launch<NV, NT, FUSE, ST>(dim3, hipStream_t, const uint8_t *, const float *, uint64_t, uint64_t, int,         \
-                                                     const M8BatchArgs<NV> &, const M8BatchFuse<NV> &, const MvmBatchRng &);
-#define M8TB_INST_NV(NV)                                                                                                       \
-    M8TB_INST(NV, false, false, false) M8TB_INST(NV, false, false, true) M8TB_INST(NV, false, true, false) M8TB_INST(NV, false, true, true) \
-    M8TB_INST(NV, true, false, false) M8TB_INST(NV, true, false, true) M8TB_INST(NV, true, true, false) M8TB_INST(NV, true, true, true)
-M8TB_INST_NV(2)
-M8TB_INST_NV(4)
-M8TB_INST_NV(8)
-#undef M8TB_INST_NV
-#undef M8TB_INST
+MVM_BATCH_INSTANTIATE_LAUNCHES(M8TBatch)
 
 // ---- C ABI (include/clover_hip_batch_t8.h) ---------------------------------------------------------------------------------------
 extern "C" int clm8_mvm_transposed_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,

@@ -2,7 +2,7 @@
 // and overlap check and the batched IHT / GD loop.  Included by mvm_batch4.hip (CloverMatrix4 x CloverVector4), mvm_batch8.hip
 // (CloverMatrix4 x CloverVector8), matrix8_batch.hip (CloverMatrix8 x CloverVector8), mvm_t4_batch.hip (CloverMatrix4' x CloverVector4
 // straight from the matrix's own bytes), mvm_t8_batch.hip (CloverMatrix4' x CloverVector8, likewise) and matrix8_t_batch.hip (CloverMatrix8' x
-// CloverVector8, likewise); half16_batch.hip (CloverMatrix16 x CloverVector16, no scales and no draws: a driver of its own) includes it for
+// CloverVector8, likewise); half16_batch_host.h (the driver of the two half-precision families, no scales and no draws) includes it for
 // mvm_batch_forced() alone.  Each of the six defines its
 // kernel and a traits struct F with exactly what differs between the families:
 //   Args<NV>, Fuse<NV>                        the kernel's by-value argument structs (their pointer types decide the casts)
@@ -14,7 +14,8 @@
 //   iht_prefers_single(...)                   whether a group of the IHT loop is better off as single calls (measured per family)
 //   launch<NV, NT, FUSE, ST>(...)             the hipLaunchKernelGGL of the family's kernel, with its U and LDS bytes
 //   x_len, r_len, grid, batched_by_rule       which dimension sizes x and which r, the grid of a launch and the measured dispatch rule:
-//                                             MvmBatchByRows (below) for the three families that walk the matrix by rows
+//                                             MvmBatchByRows (below) for the three families that walk the matrix by rows; the transposed
+//                                             three take x_len and r_len from MvmBatchByCols and keep a grid and a rule of their own
 //   nothing_to_do(nvec, rows, cols)           the empty-call rule of the three mvm batch entry points: checked arguments, no device work
 // The extern "C" mvm batch entry points of a family forward to mvm_batch_entry, mvm_batch_at_entry and mvm_batch_fused_entry (below) with
 // their own names, which the messages quote.
@@ -43,6 +44,28 @@ struct MvmBatchByRows {
     static bool batched_by_rule(uint64_t g, uint64_t, uint64_t, bool, bool) { return g >= 2; }
     static bool nothing_to_do(uint64_t nvec, uint64_t rows, uint64_t) { return !nvec || !rows; }
 };
+
+// what the three transposed families share: A is rows x cols, x has `rows` elements and r = A' x has `cols`; a matrix without rows has
+// nothing to multiply, one without columns nothing to write; r[j] == x[j] is left to the range check
+struct MvmBatchByCols {
+    static uint64_t x_len(uint64_t rows, uint64_t) { return rows; }
+    static uint64_t r_len(uint64_t, uint64_t cols) { return cols; }
+    static bool nothing_to_do(uint64_t nvec, uint64_t rows, uint64_t cols) { return !nvec || !rows || !cols; }
+    static bool result_may_not_alias_x(bool) { return false; }
+};
+
+// the explicit instantiations of F::launch behind a transposed family's definition of it, for the driver's NV = 2, 4, 8 (the traits are
+// declared in a header of their own, the launches defined beside the kernel)
+#define MVM_BATCH_INSTANTIATE_LAUNCH(F, NV, NT, FUSE, ST)                                                                     \
+    template void F::launch<NV, NT, FUSE, ST>(dim3, hipStream_t, const uint8_t *, const float *, uint64_t, uint64_t, int, \
+                                              const F::Args<NV> &, const F::Fuse<NV> &, const MvmBatchRng &);
+#define MVM_BATCH_INSTANTIATE_LAUNCHES_NV(F, NV)                                                                                      \
+    MVM_BATCH_INSTANTIATE_LAUNCH(F, NV, false, false, false) MVM_BATCH_INSTANTIATE_LAUNCH(F, NV, false, false, true)              \
+    MVM_BATCH_INSTANTIATE_LAUNCH(F, NV, false, true, false) MVM_BATCH_INSTANTIATE_LAUNCH(F, NV, false, true, true)                \
+    MVM_BATCH_INSTANTIATE_LAUNCH(F, NV, true, false, false) MVM_BATCH_INSTANTIATE_LAUNCH(F, NV, true, false, true)                \
+    MVM_BATCH_INSTANTIATE_LAUNCH(F, NV, true, true, false) MVM_BATCH_INSTANTIATE_LAUNCH(F, NV, true, true, true)
+#define MVM_BATCH_INSTANTIATE_LAUNCHES(F) \
+    MVM_BATCH_INSTANTIATE_LAUNCHES_NV(F, 2) MVM_BATCH_INSTANTIATE_LAUNCHES_NV(F, 4) MVM_BATCH_INSTANTIATE_LAUNCHES_NV(F, 8)
 
 // Whether a group of g vectors runs as one batched launch or as g single launches.  Forced to 1, with an rng a remainder group of ONE vector
 // (nvec = 9, 17, ...) runs batched too: a forced call then hands the state from batched launch to batched launch throughout, which is what

@@ -9,14 +9,12 @@
 
 #define MVTB_W 4           // output blocks (64 columns each) per workgroup: MVT_W of the single kernel (mvm_t4.hip), whose lane map this keeps
 
-struct MvmT4Batch {
+struct MvmT4Batch : MvmBatchByCols {
     template <int NV> using Args = MvmBatchArgs<NV>;
     template <int NV> using Fuse = MvmBatchFuse<NV>;
     static uint64_t matrix_bytes(uint64_t rows, uint64_t cols) { return rows * (cols / 2); }
     static uint64_t vector_bytes(uint64_t n) { return n / 2; }
     // A is rows x cols: x has `rows` elements, r = A' x has `cols`; a workgroup owns MVTB_W output blocks and walks all rows
-    static uint64_t x_len(uint64_t rows, uint64_t) { return rows; }
-    static uint64_t r_len(uint64_t, uint64_t cols) { return cols; }
     static dim3 grid(uint64_t, uint64_t cols) { return dim3((unsigned)((cols / 64 + MVTB_W - 1) / MVTB_W)); }
     // the size rules of clm4_mvm_transposed (mvm_t4.hip)
     static int check_matrix(const char *fn, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols)
@@ -27,9 +25,6 @@ struct MvmT4Batch {
         CLV_REQUIRE(cols / 64 <= 0x7FFFFFFFull, "%s: too many columns", fn);
         return CLV_OK;
     }
-    // a matrix without rows has nothing to multiply, one without columns nothing to write
-    static bool nothing_to_do(uint64_t nvec, uint64_t rows, uint64_t cols) { return !nvec || !rows || !cols; }
-    static bool result_may_not_alias_x(bool) { return false; }
     static constexpr auto mvm = clm4_mvm_transposed;
     static constexpr auto scale_and_add = clm4_mvm_transposed_scale_and_add;
     static constexpr auto iht_one_matrix = clm4_iht_one_matrix;

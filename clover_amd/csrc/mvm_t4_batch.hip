@@ -244,17 +244,7 @@ void MvmT4Batch::launch(dim3 grid, hipStream_t st, const uint8_t *A, const float
 {
     hipLaunchKernelGGL((k_m4_mvm_t_batch<NV, MVTB_U(NV), NT, FUSE, ST>), grid, dim3(256), 0, st, A, sA, rows, cols, nv, arg, fuse, rs);
 }
-#define MVTB_INST(NV, NT, FUSE, ST)                                                                                                       \
-    template void MvmT4Batch::launch<NV, NT, FUSE, ST>(dim3, hipStream_t, const uint8_t *, const float *, uint64_t, uint64_t, int,         \
-                                                       const MvmBatchArgs<NV> &, const MvmBatchFuse<NV> &, const MvmBatchRng &);
-#define MVTB_INST_NV(NV)                                                                                                       \
-    MVTB_INST(NV, false, false, false) MVTB_INST(NV, false, false, true) MVTB_INST(NV, false, true, false) MVTB_INST(NV, false, true, true) \
-    MVTB_INST(NV, true, false, false) MVTB_INST(NV, true, false, true) MVTB_INST(NV, true, true, false) MVTB_INST(NV, true, true, true)
-MVTB_INST_NV(2)
-MVTB_INST_NV(4)
-MVTB_INST_NV(8)
-#undef MVTB_INST_NV
-#undef MVTB_INST
+MVM_BATCH_INSTANTIATE_LAUNCHES(MvmT4Batch)
 
 // ---- C ABI (include/clover_hip_batch_t.h) ----------------------------------------------------------------------------------------
 extern "C" int clm4_mvm_transposed_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,

@@ -9,15 +9,13 @@
 
 #define MVT8B_W 2          // output blocks (64 columns each) per workgroup: MVT8_W of the single kernel (mvm_t8.hip)
 
-struct MvmT8Batch {
+struct MvmT8Batch : MvmBatchByCols {
     template <int NV> using Args = Mvm8BatchArgs<NV>;
     template <int NV> using Fuse = Mvm8BatchFuse<NV>;
     static uint64_t matrix_bytes(uint64_t rows, uint64_t cols) { return rows * (cols / 2); }
     static uint64_t vector_bytes(uint64_t n) { return n; }
     // A is rows x cols: x has `rows` elements, r = A' x has `cols`; a workgroup owns MVT8B_W output blocks (64 bytes of every row) and
     // walks all rows
-    static uint64_t x_len(uint64_t rows, uint64_t) { return rows; }
-    static uint64_t r_len(uint64_t, uint64_t cols) { return cols; }
     static dim3 grid(uint64_t, uint64_t cols) { return dim3((unsigned)(cols / (64 * MVT8B_W))); }
     // the size rules of clm4_mvm_v8_transposed (mvm_t8.hip)
     static int check_matrix(const char *fn, const int8_t *A, const float *sA, uint64_t rows, uint64_t cols)
@@ -29,9 +27,6 @@ struct MvmT8Batch {
         CLV_REQUIRE(rows / 64 <= 0x7FFFFFFFull, "%s: too many rows", fn);
         return CLV_OK;
     }
-    // a matrix without rows has nothing to multiply, one without columns nothing to write
-    static bool nothing_to_do(uint64_t nvec, uint64_t rows, uint64_t cols) { return !nvec || !rows || !cols; }
-    static bool result_may_not_alias_x(bool) { return false; }
     static constexpr auto mvm = clm4_mvm_v8_transposed;
     static constexpr auto scale_and_add = clm4_mvm_v8_transposed_scale_and_add;
     static constexpr auto iht_one_matrix = clm4_iht_v8_one_matrix;

@@ -253,17 +253,7 @@ void MvmT8Batch::launch(dim3 grid, hipStream_t st, const uint8_t *A, const float
 {
     hipLaunchKernelGGL((k_m4_mvm8_t_batch<NV, MVT8B_U(NV), NT, FUSE, ST>), grid, dim3(256), 0, st, A, sA, rows, cols, nv, arg, fuse, rs);
 }
-#define MVT8B_INST(NV, NT, FUSE, ST)                                                                                                     \
-    template void MvmT8Batch::launch<NV, NT, FUSE, ST>(dim3, hipStream_t, const uint8_t *, const float *, uint64_t, uint64_t, int,        \
-                                                       const Mvm8BatchArgs<NV> &, const Mvm8BatchFuse<NV> &, const MvmBatchRng &);
-#define MVT8B_INST_NV(NV)                                                                                                          \
-    MVT8B_INST(NV, false, false, false) MVT8B_INST(NV, false, false, true) MVT8B_INST(NV, false, true, false) MVT8B_INST(NV, false, true, true) \
-    MVT8B_INST(NV, true, false, false) MVT8B_INST(NV, true, false, true) MVT8B_INST(NV, true, true, false) MVT8B_INST(NV, true, true, true)
-MVT8B_INST_NV(2)
-MVT8B_INST_NV(4)
-MVT8B_INST_NV(8)
-#undef MVT8B_INST_NV
-#undef MVT8B_INST
+MVM_BATCH_INSTANTIATE_LAUNCHES(MvmT8Batch)
 
 // ---- C ABI (include/clover_hip_batch_t_v8.h) ---------------------------------------------------------------------------------------
 extern "C" int clm4_mvm_v8_transposed_batch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, uint64_t nvec, const int8_t *const *x,

@@ -76,9 +76,19 @@ def test_the_signatures_follow_the_single_calls():
 
 def test_the_kernel_is_a_source_of_the_library():
     assert "half16_batch.hip" in HIP_SOURCES
-    text = (repo_root() / "clover_amd" / "csrc" / "half16_batch.hip").read_text()
+    csrc = repo_root() / "clover_amd" / "csrc"
+    text = (csrc / "half16_batch.hip").read_text()
     # the chunk of x the GPU tests take their shapes from: 512 columns per wave of the workgroup
     assert re.search(r"#define\s+F16B_CHUNK\(WAVES\)\s+\(512u \* \(WAVES\)\)", text)
+    for shared in ("f16_fuse_store", "f16_bits", "ld_stream", "F16_STREAMING", "f16_chain_tree"):      # the device side: beside the kernel
+        assert shared in text, shared
+    assert not re.search(r"\basm\b", text), "no inline assembly"
+    # the host side: the driver it shares with the transposed family, no group loop of its own
+    host = (csrc / "half16_batch_host.h").read_text()
+    for shared in ("mvm_batch_forced", "clv_internal_mvm_batch_count"):
+        assert shared in host, shared
+    assert re.search(r'^#include "half16_batch_host\.h"', text, flags=re.M)
+    assert not re.search(r"\bfor\s*\([^{\n]*CLM4_MVM_BATCH_MAX", text), "half16_batch.hip has a group loop of its own"
     build = (repo_root() / "clover_amd" / "build.py").read_text()
     assert "clover_hip_batch_f16.h" in build, "the header is a dependency of the library"
 

@@ -29,7 +29,7 @@ from f16_transposed_helpers import rt  # noqa: F401  (fixture)
 pytestmark = pytest.mark.gpu
 
 ENVS = [None, "1", "0"]
-# The dispatch rule with CLV_MVM_BATCH unset (f16tb_selected, half16_t_batch.hip), from profiles/f16_mvm_transposed_batch_kernel_bench.json
+# The dispatch rule with CLV_MVM_BATCH unset (F16TBatch::batched_by_rule, half16_t_batch.hip), from profiles/f16_mvm_transposed_batch_kernel_bench.json
 # and profiles/f16_mvm_transposed_batch_groups_kernel_bench.json: every group of 2 ... 8 beat the single transposed calls by more than
 # their spread, over a streaming matrix (2.0 x at two vectors) and over a cache-resident one (1.11 x at two vectors).  The smallest
 # group that runs batched, by size class; None would mean that the class forwards every group to the single calls

@@ -84,12 +84,22 @@ def test_the_signatures_follow_the_single_transposed_calls():
 
 def test_the_kernel_is_a_source_of_the_library_and_the_header_a_dependency():
     assert "half16_t_batch.hip" in HIP_SOURCES
-    text = (repo_root() / "clover_amd" / "csrc" / "half16_t_batch.hip").read_text()
+    csrc = repo_root() / "clover_amd" / "csrc"
+    text = (csrc / "half16_t_batch.hip").read_text()
     for regex in (COLS_RE, U_RE, CHUNK_RE):              # the constants the GPU tests take their shapes from
         assert re.search(regex, text), regex
-    for shared in ("F16Fuse", "f16_fuse_store", "f16_bits", "ld_stream", "F16_STREAMING", "mvm_batch_forced", "clv_internal_mvm_batch_count"):
+    for shared in ("F16Fuse", "f16_fuse_store", "f16_bits", "ld_stream", "F16_STREAMING"):       # the device side: beside the kernel
         assert shared in text, shared
     assert not re.search(r"\basm\b", text), "no inline assembly"
+    # the host side: one driver for both half-precision families, no group loop in either source
+    host = (csrc / "half16_batch_host.h").read_text()
+    for shared in ("mvm_batch_forced", "clv_internal_mvm_batch_count"):
+        assert shared in host, shared
+    for name in ("half16_batch.hip", "half16_t_batch.hip"):
+        source = (csrc / name).read_text()
+        assert re.search(r'^#include "half16_batch_host\.h"', source, flags=re.M), name
+        assert not re.search(r"\bfor\s*\([^{\n]*CLM4_MVM_BATCH_MAX", source), f"{name} has a group loop of its own"
+    assert not (csrc / "half16_batch.h").exists()
     build = (repo_root() / "clover_amd" / "build.py").read_text()
     assert "clover_hip_batch_f16_t.h" in build, "the header is a dependency of the library"
 
