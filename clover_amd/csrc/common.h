@@ -81,6 +81,8 @@ int clv_internal_dot_chain(const void *X, uint64_t blocks_padded, float *out_dev
 int clv_internal_v8_clear(int8_t *x, float *sx, uint64_t n_pad, hipStream_t st);
 // CloverVector4::clear() as one launch (iht4.hip): nibbles 0, scales 1.0; first step of clm4_iht and clm4_iht_one_matrix
 int clv_internal_v4_clear(int8_t *x, float *sx, uint64_t n_pad, hipStream_t st);
+// CloverVector32::clear() as one launch (fp32.hip): n (a multiple of 4) zeros; first step of clm_f32_iht and the clm4_iht_f32 pair
+int clv_internal_f32_clear(float *x, uint64_t n, hipStream_t st);
 // zero-initialised hand-over slots per (device, stream), <= 64 KiB; every user leaves them zero again (runtime.hip)
 int clv_internal_sync_slots(void **ptr, uint64_t bytes, hipStream_t stream);
 

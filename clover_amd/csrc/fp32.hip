@@ -347,6 +347,15 @@ extern "C" int clv_f32_dot(const float *u, const float *v, uint64_t n_pad, int m
     return CLV_OK;
 }
 
+int clv_internal_f32_clear(float *x, uint64_t n, hipStream_t st)
+{
+    if (!n) return CLV_OK;
+    const uint64_t ng = n / 4, want = (ng + 255) / 256;
+    hipLaunchKernelGGL(k_f32_clear, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, st, (u32x4 *)x, ng);
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+
 // the checks and the launch of both mvm forms; t is the plain result (fuse == nullptr) or the optional copy of the row values
 static int f32_mvm(const char *fn, const float *A, uint64_t rows, uint64_t cols, const float *x, float *t, const F32Fuse *fuse, void *stream)
 {
@@ -400,12 +409,7 @@ extern "C" int clm_f32_iht(const float *Phi, const float *PhiT, uint64_t m, uint
                 (unsigned long long)x_len);
     CLV_REQUIRE(threshold >= 0 && threshold <= 2, "clm_f32_iht: unknown threshold %d", threshold);
     CLV_REQUIRE(F32_ALIGNED(Phi) && F32_ALIGNED(PhiT) && F32_ALIGNED(x) && F32_ALIGNED(t2), "clm_f32_iht: the matrices, x and t2 must be 16-byte aligned");
-    if (n) {                                                                                             // x.clear()
-        const uint64_t ng = n / 4, want = (ng + 255) / 256;
-        hipLaunchKernelGGL(k_f32_clear, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, as_stream(stream), (u32x4 *)x, ng);
-        CLV_LAUNCH_CHECK();
-    }
-    int rc = CLV_OK;
+    int rc = clv_internal_f32_clear(x, n, as_stream(stream));                                            // x.clear()
     for (uint64_t it = 0; !rc && it < iterations; it++) {
         rc = clm_f32_mvm_scale_and_add(Phi, m, n, x, y, -1.0f, t1, t2, stream);                          // t1 = Phi x; t2 = y - t1
         if (!rc) rc = clm_f32_mvm_scale_and_add(PhiT, n, m, t2, x, mu, t3, x, stream);                   // t3 = Phi' t2; x += mu t3

@@ -1,7 +1,7 @@
 // mvm_f32.hip -- the mixed-precision CloverMatrix4::mvm(const CloverVector32 &, CloverVector32 &).
 // One of the callers either side of the hot path.  With mvm these are the five steps of the reference's quantized IHT / GD
 // iterations (test/performance/01_measure.h:923-946, 999-1021), so x, t1..t3 can stay in HBM across iterations.
-#include "common.h"
+#include "mvm_f32_device.h"
 
 #include <type_traits>
 
@@ -27,10 +27,12 @@
 #define MVF_WAVES 1                 // minimum waves per SIMD the register allocation must leave room for (A/B builds: 3, 4)
 #endif
 
-template <bool NT>
+// FUSE... = nothing (clm4_mvm_f32) or one M4F32Fuse (mvm_f32_device.h): r is then t of the fused call and may be NULL
+template <bool NT, typename... FUSE>
 __global__ __launch_bounds__(256, MVF_WAVES) void k_m4_mvm_f32(const u32x4 *__restrict__ A, const float *__restrict__ sA, uint64_t cols,
-                                                    const float *__restrict__ x, float *__restrict__ r)
+                                                    const float *__restrict__ x, float *__restrict__ r, FUSE... fuse)
 {
+    constexpr bool FUSED = sizeof...(FUSE) != 0;
     extern __shared__ __attribute__((aligned(16))) float mvf_x[];        // MVF_CHUNK floats of x, then MVF_CHUNK/64 block factors
     float *s7 = mvf_x + MVF_CHUNK;
     const int tid = threadIdx.x, a = tid & 3, rho = tid >> 2;
@@ -40,6 +42,8 @@ __global__ __launch_bounds__(256, MVF_WAVES) void k_m4_mvm_f32(const u32x4 *__re
     float acc[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) acc[j] = 0.0f;
+    float fuse_u = 0.0f;
+    if (FUSED && a == 0) fuse_u = m4f32_fuse_load_u(row, fuse...);      // ahead of the streaming loop: the epilogue waits on nothing
     for (uint64_t c0 = 0; c0 < cols; c0 += MVF_CHUNK) {
         const uint32_t cw = (uint32_t)((cols - c0) < MVF_CHUNK ? (cols - c0) : MVF_CHUNK);
         if (c0) __syncthreads();
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(256, MVF_WAVES) void k_m4_mvm_f32(const u32x4 *__re
     }
     const float t0 = s3[4] + s3[0], t1 = s3[5] + s3[1], t2 = s3[6] + s3[2], t3 = s3[7] + s3[3];
     const float dot = (t0 + t2) + (t1 + t3);
-    if (a == 0) r[row] = dot;
+    if (a == 0) m4f32_store(r, row, dot, fuse_u, fuse...);
 }
 
 extern "C" int clm4_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *r, void *stream)
@@ -145,6 +149,22 @@ extern "C" int clm4_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uin
     } else {
         CLV_HIP(hipFuncSetAttribute((const void *)k_m4_mvm_f32<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_m4_mvm_f32<false>, grid, dim3(256), lds, as_stream(stream), (const u32x4 *)A, sA, cols, x, r);
+    }
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+
+int clv_internal_m4_mvm_f32_fused(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *t, const M4F32Fuse &fuse,
+                                  hipStream_t st)
+{
+    const size_t lds = (MVF_CHUNK + MVF_CHUNK / 64) * sizeof(float);
+    const dim3 grid((unsigned)(rows / 64));
+    if (m4f32_streaming(rows, cols)) {
+        CLV_HIP(hipFuncSetAttribute((const void *)k_m4_mvm_f32<true, M4F32Fuse>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_m4_mvm_f32<true, M4F32Fuse>), grid, dim3(256), lds, st, (const u32x4 *)A, sA, cols, x, t, fuse);
+    } else {
+        CLV_HIP(hipFuncSetAttribute((const void *)k_m4_mvm_f32<false, M4F32Fuse>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_m4_mvm_f32<false, M4F32Fuse>), grid, dim3(256), lds, st, (const u32x4 *)A, sA, cols, x, t, fuse);
     }
     CLV_LAUNCH_CHECK();
     return CLV_OK;

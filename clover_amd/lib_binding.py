@@ -250,6 +250,16 @@ SIGNATURES_BATCH_F16_T = {
     "clm_f16_iht_batch_one_matrix": (C.c_int, [_vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
 }
 
+# name -> (restype, argtypes); everything include/clover_hip_m4_f32.h declares (CloverMatrix4 on fp32 vectors: the fused mvm + scaleAndAdd,
+# A' x straight from A's own bytes with its fused form, the IHT / GD loop of <CloverMatrix4, CloverVector32> with two matrices or one)
+SIGNATURES_M4_F32 = {
+    "clm4_mvm_f32_scale_and_add": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "clm4_mvm_f32_transposed": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "clm4_mvm_f32_transposed_scale_and_add": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "clm4_iht_f32": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
+    "clm4_iht_f32_one_matrix": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
+}
+
 
 class CloverHipError(RuntimeError):
     pass
@@ -265,7 +275,7 @@ def load_library(path: str | Path | None = None, allow_probe: bool = False) -> C
             "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = C.CDLL(str(p))
     for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items(), *SIGNATURES_BATCH_T8.items(), *SIGNATURES_BATCH_T_V8.items(),
-                              *SIGNATURES_BATCH_F16.items(), *SIGNATURES_F16_T.items(), *SIGNATURES_BATCH_F16_T.items()):
+                              *SIGNATURES_BATCH_F16.items(), *SIGNATURES_F16_T.items(), *SIGNATURES_BATCH_F16_T.items(), *SIGNATURES_M4_F32.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -713,6 +723,50 @@ class CloverHip:
         d = self.alloc(max(rows * 4, 4))
         self.check(self.lib.clm4_mvm_f32(b[0].ptr, b[1].ptr, rows, cols, b[2].ptr, d.ptr, None))
         return d.download(np.float32, rows)
+
+    # CloverMatrix4 on fp32 vectors (include/clover_hip_m4_f32.h); the matrix pair and every vector a numpy array or a DevBuf
+    def _m4_dev(self, q, s):
+        return (q if isinstance(q, DevBuf) else self.to_device(q)), (s if isinstance(s, DevBuf) else self.to_device(s))
+
+    def _m4_f32_fused(self, fn, qA, sA, rows, cols, nout, x, u, a, in_place, want_t):
+        (dq, ds), dx, du = self._m4_dev(qA, sA), self._f32_dev(x), self._f32_dev(u)
+        dt = self.alloc(max(4 * nout, 4)) if want_t else None
+        dr = du if in_place else self.alloc(max(4 * nout, 4))
+        self.check(fn(dq.ptr, ds.ptr, rows, cols, dx.ptr, du.ptr, a, dt.ptr if dt else None, dr.ptr, None))
+        return (dt.download(np.float32, nout) if want_t else None), dr.download(np.float32, nout)
+
+    def m4_mvm_f32_scale_and_add(self, qA, sA, rows, cols, x, u, a: float, in_place: bool = False, want_t: bool = True):
+        """(t, r2) of clm4_mvm_f32_scale_and_add, `rows` values each; t is None when want_t is False"""
+        return self._m4_f32_fused(self.lib.clm4_mvm_f32_scale_and_add, qA, sA, rows, cols, rows, x, u, a, in_place, want_t)
+
+    def m4_mvm_f32_transposed(self, qA, sA, rows, cols, x) -> np.ndarray:
+        (dq, ds), dx, dr = self._m4_dev(qA, sA), self._f32_dev(x), self.alloc(max(4 * cols, 4))
+        self.check(self.lib.clm4_mvm_f32_transposed(dq.ptr, ds.ptr, rows, cols, dx.ptr, dr.ptr, None))
+        return dr.download(np.float32, cols)
+
+    def m4_mvm_f32_transposed_scale_and_add(self, qA, sA, rows, cols, x, u, a: float, in_place: bool = False, want_t: bool = True):
+        """(t, r2) of clm4_mvm_f32_transposed_scale_and_add, `cols` values each; t is None when want_t is False"""
+        return self._m4_f32_fused(self.lib.clm4_mvm_f32_transposed_scale_and_add, qA, sA, rows, cols, cols, x, u, a, in_place, want_t)
+
+    def m4_iht_f32(self, qPhi, sPhi, qPhiT, sPhiT, m, n, y, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+                   prefill: int = 0x55):
+        """clm4_iht_f32 (qPhiT None: clm4_iht_f32_one_matrix) on buffers prefilled with `prefill` bytes:
+        {"x": fp32[n], "t1": fp32[m], "t2": fp32[m], "t3": fp32[n]}"""
+        b = [*self._m4_dev(qPhi, sPhi), *(self._m4_dev(qPhiT, sPhiT) if qPhiT is not None else ())]
+        dy = self._f32_dev(y)
+        lens = {"x": n, "t1": m, "t2": m, "t3": n}
+        v = {}
+        for name, ln in lens.items():
+            v[name] = self.alloc(4 * ln)
+            self.check(self.lib.clv_memset(v[name].ptr, prefill, v[name].nbytes, None))
+        tail = (m, n, v["x"].ptr, n if x_len is None else x_len, dy.ptr, v["t1"].ptr, v["t2"].ptr, v["t3"].ptr, iterations, K, mu, threshold, None)
+        fn = self.lib.clm4_iht_f32_one_matrix if qPhiT is None else self.lib.clm4_iht_f32
+        self.check(fn(*[d.ptr for d in b], *tail))
+        return {name: v[name].download(np.float32, ln) for name, ln in lens.items()}
+
+    def m4_iht_f32_one_matrix(self, qPhi, sPhi, m, n, y, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+                              prefill: int = 0x55):
+        return self.m4_iht_f32(qPhi, sPhi, None, None, m, n, y, iterations, K, mu, threshold, x_len=x_len, prefill=prefill)
 
     # -- CloverMatrix8 ---------------------------------------------------------------------------
     def m8_quantize(self, A: np.ndarray, rng: DevBuf | None = None):

@@ -523,6 +523,34 @@ inline void Q_GD<CloverMatrix32, CloverVector32>(CloverMatrix32 &Phi, CloverMatr
 {
     Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, 0, mu, false);
 }
+
+/* CloverMatrix4 with CloverVector32 vectors (the reference's Q_IHT<CloverMatrix4, CloverVector32>: the matrix carries the bytes, the iterate
+ * keeps fp32) under the same switch, which puts CloverVector32's scaleAndAdd and threshold on the device: the whole loop in one call
+ * (CloverMatrix4::iht_loop -> clm4_iht_f32, clover_hip_m4_f32.h), one fused launch per product plus the threshold, the bits of the generic
+ * templates' five method calls.  Overloads, as for the other vector widths of CloverMatrix4; without the switch the generic templates
+ * run one device product and the host methods, as before. */
+inline void Q_IHT(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector32 &x, CloverVector32 &y, CloverVector32 &t1, CloverVector32 &t2,
+                  CloverVector32 &t3, const uint64_t iterations, const uint64_t K, const float mu)
+{
+    Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, K, mu, true);
+}
+inline void Q_GD(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector32 &x, CloverVector32 &y, CloverVector32 &t1, CloverVector32 &t2,
+                 CloverVector32 &t3, const uint64_t iterations, const float mu)
+{
+    Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, 0, mu, false);
+}
+/* the same holding ONE matrix: Phi' t2 comes straight from Phi's own bytes (CloverMatrix4::iht_loop_one_matrix -> clm4_iht_f32_one_matrix),
+ * the bits of the two above with PhiT = transpose(Phi).  Opt-in by name. */
+inline void Q_IHT_one_matrix(CloverMatrix4 &Phi, CloverVector32 &x, CloverVector32 &y, CloverVector32 &t1, CloverVector32 &t2, CloverVector32 &t3,
+                             const uint64_t iterations, const uint64_t K, const float mu)
+{
+    Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, K, mu, true);
+}
+inline void Q_GD_one_matrix(CloverMatrix4 &Phi, CloverVector32 &x, CloverVector32 &y, CloverVector32 &t1, CloverVector32 &t2, CloverVector32 &t3,
+                            const uint64_t iterations, const float mu)
+{
+    Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, 0, mu, false);
+}
 #endif
 
 #endif
