@@ -10,7 +10,7 @@ import shutil
 import subprocess
 from pathlib import Path
 
-HIP_SOURCES = ["runtime.hip", "vector4.hip", "matrix4.hip", "mvm_t4.hip", "mvm_t8.hip", "matrix8_t.hip", "mvm_batch4.hip", "mvm_t4_batch.hip", "mvm_batch8.hip", "mvm_t8_batch.hip", "matrix8_batch.hip", "matrix8_t_batch.hip", "rng4.hip", "gemm4.hip", "gemm6.hip", "gemm8.hip", "multi.hip", "scale_add4.hip", "transpose4.hip", "threshold4.hip", "iht4.hip", "iht_persist.hip", "mvm_f32.hip", "mvm_f32_t.hip", "mixed8.hip", "matrix8.hip", "half16.hip", "half16_batch.hip", "half16_t.hip", "half16_t_batch.hip", "fp32.hip"]
+HIP_SOURCES = ["runtime.hip", "vector4.hip", "matrix4.hip", "mvm_t4.hip", "mvm_t8.hip", "matrix8_t.hip", "mvm_batch4.hip", "mvm_t4_batch.hip", "mvm_batch8.hip", "mvm_t8_batch.hip", "matrix8_batch.hip", "matrix8_t_batch.hip", "rng4.hip", "gemm4.hip", "gemm6.hip", "gemm8.hip", "multi.hip", "scale_add4.hip", "transpose4.hip", "threshold4.hip", "iht4.hip", "iht_persist.hip", "mvm_f32.hip", "mvm_f32_t.hip", "mixed8.hip", "matrix8.hip", "matrix8_f32_t.hip", "half16.hip", "half16_batch.hip", "half16_t.hip", "half16_t_batch.hip", "fp32.hip"]
 # per-file additions.  gemm6.hip: hipcc's SLP pass pairs the fold's scalar fmas into v_pk_fma_f32, which is slower beside MFMAs
 # (MI355X_MICROARCH.md, "price of one filler beside MFMAs"); measured here: see DESIGN.md 6
 EXTRA_FLAGS = {}
@@ -47,7 +47,7 @@ def build_hip_library(force: bool = False, verbose: bool = False) -> Path:
     root = repo_root()
     src_dir = root / "clover_amd" / "csrc"
     srcs = [src_dir / s for s in HIP_SOURCES if (src_dir / s).exists()]
-    deps = srcs + list(src_dir.glob("*.h")) + list(src_dir.glob("*.inc")) + [root / "include" / "clover_hip.h", root / "include" / "clover_hip_fp32.h", root / "include" / "clover_hip_batch_t.h", root / "include" / "clover_hip_batch_t8.h", root / "include" / "clover_hip_batch_t_v8.h", root / "include" / "clover_hip_batch_f16.h", root / "include" / "clover_hip_f16_t.h", root / "include" / "clover_hip_batch_f16_t.h", root / "include" / "clover_hip_m4_f32.h"]
+    deps = srcs + list(src_dir.glob("*.h")) + list(src_dir.glob("*.inc")) + [root / "include" / "clover_hip.h", root / "include" / "clover_hip_fp32.h", root / "include" / "clover_hip_batch_t.h", root / "include" / "clover_hip_batch_t8.h", root / "include" / "clover_hip_batch_t_v8.h", root / "include" / "clover_hip_batch_f16.h", root / "include" / "clover_hip_f16_t.h", root / "include" / "clover_hip_batch_f16_t.h", root / "include" / "clover_hip_m4_f32.h", root / "include" / "clover_hip_m8_f32.h"]
     out = hip_library_path()
     out.parent.mkdir(parents=True, exist_ok=True)
     if force or _stale(out, deps):

@@ -5,6 +5,7 @@
 // reference's SIMD arithmetic order bit for bit; tests/matrix8_restate.c states the same orders on the CPU.
 #include "rng_device.h"
 #include "mvm8_device.h"
+#include "mvm_f32_device.h"
 
 #include <stdlib.h>
 
@@ -263,12 +264,16 @@ __global__ __launch_bounds__(256) void k_m8_mvm_saa(const uint8_t *__restrict__ 
 //     x[i] = sum[i + 4] + sum[i],  (x0 + x2) + (x1 + x3).
 // Mapping: 8 lanes per row, lane e (0..7) owns accumulator e >> 1, AVX lanes 4 (e & 1) .. 4 (e & 1) + 3, i.e. elements 4e..4e+3 and
 // 32+4e..32+4e+3 of every block -- dword e and dword 8 + e of the row's block.  Workgroup = 32 rows.
-template <bool NT>
+// FUSE... = nothing (clm8_mvm_f32) or one M4F32Fuse (mvm_f32_device.h): r is then t of the fused call and may be NULL
+template <bool NT, typename... FUSE>
 __global__ __launch_bounds__(256) void k_m8_mvm_f32(const uint32_t *__restrict__ A, const float *__restrict__ sA, uint64_t cols,
-                                                    const f32x4 *__restrict__ x, float *__restrict__ r)
+                                                    const f32x4 *__restrict__ x, float *__restrict__ r, FUSE... fuse)
 {
+    constexpr bool FUSED = sizeof...(FUSE) != 0;
     const int tid = threadIdx.x, e = tid & 7;
     const uint64_t row = (uint64_t)blockIdx.x * 32 + (tid >> 3);
+    float fuse_u = 0.0f;
+    if (FUSED && e == 0) fuse_u = m4f32_fuse_load_u(row, fuse...);      // ahead of the streaming loop: the epilogue waits on nothing
     const uint32_t nblk = (uint32_t)(cols / 64);
     const uint32_t *Ar = A + row * (cols / 4);
     const float *sAr = sA + (row >> 6) * nblk;
@@ -310,7 +315,7 @@ __global__ __launch_bounds__(256) void k_m8_mvm_f32(const uint32_t *__restrict__
     s2 = s2 + __shfl_xor(s2, 4);
     s3 = s3 + __shfl_xor(s3, 4);
     const float x0 = s0 + __shfl_xor(s0, 1), x1 = s1 + __shfl_xor(s1, 1), x2 = s2 + __shfl_xor(s2, 1), x3 = s3 + __shfl_xor(s3, 1);
-    if (e == 0) r[row] = (x0 + x2) + (x1 + x3);
+    if (e == 0) m4f32_store(r, row, (x0 + x2) + (x1 + x3), fuse_u, fuse...);
 }
 
 // ================================================================================================
@@ -530,6 +535,19 @@ extern "C" int clm8_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uin
         hipLaunchKernelGGL(k_m8_mvm_f32<true>, grid, block, 0, as_stream(stream), (const uint32_t *)A, sA, cols, (const f32x4 *)x, r);
     else
         hipLaunchKernelGGL(k_m8_mvm_f32<false>, grid, block, 0, as_stream(stream), (const uint32_t *)A, sA, cols, (const f32x4 *)x, r);
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+
+// clm8_mvm_f32_scale_and_add (matrix8_f32_t.hip checks the arguments): the launch of clm8_mvm_f32 with the epilogue pack
+int clv_internal_m8_mvm_f32_fused(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *t, const M4F32Fuse &fuse,
+                                  hipStream_t st)
+{
+    const dim3 grid((unsigned)(rows / 32)), block(256);
+    if (m8f32_streaming(rows, cols))
+        hipLaunchKernelGGL((k_m8_mvm_f32<true, M4F32Fuse>), grid, block, 0, st, (const uint32_t *)A, sA, cols, (const f32x4 *)x, t, fuse);
+    else
+        hipLaunchKernelGGL((k_m8_mvm_f32<false, M4F32Fuse>), grid, block, 0, st, (const uint32_t *)A, sA, cols, (const f32x4 *)x, t, fuse);
     CLV_LAUNCH_CHECK();
     return CLV_OK;
 }

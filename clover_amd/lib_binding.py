@@ -260,6 +260,9 @@ SIGNATURES_M4_F32 = {
     "clm4_iht_f32_one_matrix": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
 }
 
+# name -> (restype, argtypes); everything include/clover_hip_m8_f32.h declares: the same column for CloverMatrix8
+SIGNATURES_M8_F32 = {"clm8" + name[4:]: sig for name, sig in SIGNATURES_M4_F32.items()}
+
 
 class CloverHipError(RuntimeError):
     pass
@@ -275,7 +278,8 @@ def load_library(path: str | Path | None = None, allow_probe: bool = False) -> C
             "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = C.CDLL(str(p))
     for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items(), *SIGNATURES_BATCH_T8.items(), *SIGNATURES_BATCH_T_V8.items(),
-                              *SIGNATURES_BATCH_F16.items(), *SIGNATURES_F16_T.items(), *SIGNATURES_BATCH_F16_T.items(), *SIGNATURES_M4_F32.items()):
+                              *SIGNATURES_BATCH_F16.items(), *SIGNATURES_F16_T.items(), *SIGNATURES_BATCH_F16_T.items(), *SIGNATURES_M4_F32.items(),
+                              *SIGNATURES_M8_F32.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -752,6 +756,11 @@ class CloverHip:
                    prefill: int = 0x55):
         """clm4_iht_f32 (qPhiT None: clm4_iht_f32_one_matrix) on buffers prefilled with `prefill` bytes:
         {"x": fp32[n], "t1": fp32[m], "t2": fp32[m], "t3": fp32[n]}"""
+        return self._q_iht_f32(self.lib.clm4_iht_f32, self.lib.clm4_iht_f32_one_matrix, qPhi, sPhi, qPhiT, sPhiT, m, n, y, iterations, K, mu,
+                               threshold, x_len, prefill)
+
+    def _q_iht_f32(self, two, one, qPhi, sPhi, qPhiT, sPhiT, m, n, y, iterations, K, mu, threshold, x_len, prefill):
+        """the fp32-vector loop of a quantized matrix width: `two` with (qPhiT, sPhiT), `one` when qPhiT is None"""
         b = [*self._m4_dev(qPhi, sPhi), *(self._m4_dev(qPhiT, sPhiT) if qPhiT is not None else ())]
         dy = self._f32_dev(y)
         lens = {"x": n, "t1": m, "t2": m, "t3": n}
@@ -760,7 +769,7 @@ class CloverHip:
             v[name] = self.alloc(4 * ln)
             self.check(self.lib.clv_memset(v[name].ptr, prefill, v[name].nbytes, None))
         tail = (m, n, v["x"].ptr, n if x_len is None else x_len, dy.ptr, v["t1"].ptr, v["t2"].ptr, v["t3"].ptr, iterations, K, mu, threshold, None)
-        fn = self.lib.clm4_iht_f32_one_matrix if qPhiT is None else self.lib.clm4_iht_f32
+        fn = one if qPhiT is None else two
         self.check(fn(*[d.ptr for d in b], *tail))
         return {name: v[name].download(np.float32, ln) for name, ln in lens.items()}
 
@@ -845,6 +854,32 @@ class CloverHip:
         d = self.alloc(max(rows * 4, 4))
         self.check(self.lib.clm8_mvm_f32(b[0].ptr, b[1].ptr, rows, cols, b[2].ptr, d.ptr, None))
         return d.download(np.float32, rows)
+
+    # CloverMatrix8 on fp32 vectors (include/clover_hip_m8_f32.h), shaped like their m4_ neighbours: the matrix pair and every vector a numpy
+    # array or a DevBuf
+    def m8_mvm_f32_scale_and_add(self, qA, sA, rows, cols, x, u, a: float, in_place: bool = False, want_t: bool = True):
+        """(t, r2) of clm8_mvm_f32_scale_and_add, `rows` values each; t is None when want_t is False"""
+        return self._m4_f32_fused(self.lib.clm8_mvm_f32_scale_and_add, qA, sA, rows, cols, rows, x, u, a, in_place, want_t)
+
+    def m8_mvm_f32_transposed(self, qA, sA, rows, cols, x) -> np.ndarray:
+        (dq, ds), dx, dr = self._m4_dev(qA, sA), self._f32_dev(x), self.alloc(max(4 * cols, 4))
+        self.check(self.lib.clm8_mvm_f32_transposed(dq.ptr, ds.ptr, rows, cols, dx.ptr, dr.ptr, None))
+        return dr.download(np.float32, cols)
+
+    def m8_mvm_f32_transposed_scale_and_add(self, qA, sA, rows, cols, x, u, a: float, in_place: bool = False, want_t: bool = True):
+        """(t, r2) of clm8_mvm_f32_transposed_scale_and_add, `cols` values each; t is None when want_t is False"""
+        return self._m4_f32_fused(self.lib.clm8_mvm_f32_transposed_scale_and_add, qA, sA, rows, cols, cols, x, u, a, in_place, want_t)
+
+    def m8_iht_f32(self, qPhi, sPhi, qPhiT, sPhiT, m, n, y, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+                   prefill: int = 0x55):
+        """clm8_iht_f32 (qPhiT None: clm8_iht_f32_one_matrix) on buffers prefilled with `prefill` bytes:
+        {"x": fp32[n], "t1": fp32[m], "t2": fp32[m], "t3": fp32[n]}"""
+        return self._q_iht_f32(self.lib.clm8_iht_f32, self.lib.clm8_iht_f32_one_matrix, qPhi, sPhi, qPhiT, sPhiT, m, n, y, iterations, K, mu,
+                               threshold, x_len, prefill)
+
+    def m8_iht_f32_one_matrix(self, qPhi, sPhi, m, n, y, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+                              prefill: int = 0x55):
+        return self.m8_iht_f32(qPhi, sPhi, None, None, m, n, y, iterations, K, mu, threshold, x_len=x_len, prefill=prefill)
 
     def m8_transpose(self, q, s, rows, cols):
         dq, ds = self.to_device(q), self.to_device(s)

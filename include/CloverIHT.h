@@ -551,6 +551,30 @@ inline void Q_GD_one_matrix(CloverMatrix4 &Phi, CloverVector32 &x, CloverVector3
 {
     Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, 0, mu, false);
 }
+
+/* CloverMatrix8 with CloverVector32 vectors (the reference's Q_IHT<CloverMatrix8, CloverVector32>), the same column under the same switch:
+ * CloverMatrix8::iht_loop -> clm8_iht_f32, iht_loop_one_matrix -> clm8_iht_f32_one_matrix (clover_hip_m8_f32.h).  Overloads; without the
+ * switch the generic templates run one device product and the host methods, as before. */
+inline void Q_IHT(CloverMatrix8 &Phi, CloverMatrix8 &PhiT, CloverVector32 &x, CloverVector32 &y, CloverVector32 &t1, CloverVector32 &t2,
+                  CloverVector32 &t3, const uint64_t iterations, const uint64_t K, const float mu)
+{
+    Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, K, mu, true);
+}
+inline void Q_GD(CloverMatrix8 &Phi, CloverMatrix8 &PhiT, CloverVector32 &x, CloverVector32 &y, CloverVector32 &t1, CloverVector32 &t2,
+                 CloverVector32 &t3, const uint64_t iterations, const float mu)
+{
+    Phi.iht_loop(PhiT, x, y, t1, t2, t3, iterations, 0, mu, false);
+}
+inline void Q_IHT_one_matrix(CloverMatrix8 &Phi, CloverVector32 &x, CloverVector32 &y, CloverVector32 &t1, CloverVector32 &t2, CloverVector32 &t3,
+                             const uint64_t iterations, const uint64_t K, const float mu)
+{
+    Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, K, mu, true);
+}
+inline void Q_GD_one_matrix(CloverMatrix8 &Phi, CloverVector32 &x, CloverVector32 &y, CloverVector32 &t1, CloverVector32 &t2, CloverVector32 &t3,
+                            const uint64_t iterations, const float mu)
+{
+    Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, 0, mu, false);
+}
 #endif
 
 #endif

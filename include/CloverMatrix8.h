@@ -28,6 +28,11 @@
  *                                         clm8_iht_batch_one_matrix (clover_hip_batch_t8.h; not in the reference: this' * x[j] for several
  *                                         vectors from this matrix's own bytes, and the batched loop with no stored transpose)
  *   gemm                               -> clm8_gemm       (not in the reference, which has no GEMM; semantics in DESIGN.md 6)
+ *   mvm_transposed (CloverVector32)    -> clm8_mvm_f32_transposed (clover_hip_m8_f32.h; not in the reference: this' * x straight from this
+ *                                         matrix's own bytes); under -DCLOVER_FP32_ON_DEVICE also mvm_scaleAndAdd,
+ *                                         mvm_transposed_scaleAndAdd, iht_loop and iht_loop_one_matrix for CloverVector32 vectors
+ *                                         (clm8_mvm_f32_scale_and_add, clm8_mvm_f32_transposed_scale_and_add, clm8_iht_f32,
+ *                                         clm8_iht_f32_one_matrix)
  *
  * Q_IHT<CloverMatrix8, CloverVector8> and Q_GD<...> are specialised in CloverIHT.h (which includes this header): iht_loop when rounding is
  * deterministic, the mvm_scaleAndAdd pairs otherwise; every step is a kernel on the device mirrors, nothing is copied back between steps.
@@ -45,6 +50,7 @@
 #include "CloverVector32.h"
 #include "CloverVector8.h"
 #include "clover_batch.h"          /* what the batch methods share with CloverMatrix4's: the marshalling into the batched C calls */
+#include "clover_hip_m8_f32.h"     /* this matrix on fp32 vectors: the fused step, this' * x, the fp32-vector IHT / GD loop */
 
 class CloverMatrix4;
 
@@ -466,6 +472,100 @@ public:
         resultVector.commit();
     }
     void mvm_parallel(const CloverVector32 &productVector, CloverVector32 &resultVector) { mvm(productVector, resultVector); }
+    /* Not in the reference: resultVector = this' * productVector for fp32 vectors straight from this matrix's own bytes
+     * (clm8_mvm_f32_transposed, clover_hip_m8_f32.h), bit for bit what transpose(T); T.mvm(productVector, resultVector) gives. */
+    void mvm_transposed(const CloverVector32 &productVector, CloverVector32 &resultVector)
+    {
+        if (productVector.size() != getRows() || resultVector.size_pad() != getCols()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        clover_hip::check(clm8_mvm_f32_transposed(dev_values(), dev_scales(), rows, cols, productVector.device_ro(), resultVector.device_wo(), nullptr),
+                          "CloverMatrix8::mvm_transposed");
+        resultVector.commit();
+    }
+    void mvm_transposed_parallel(const CloverVector32 &productVector, CloverVector32 &resultVector) { mvm_transposed(productVector, resultVector); }
+#ifdef CLOVER_FP32_ON_DEVICE
+    /* Not in the reference, and only where CloverVector32's own arithmetic runs on the device: t = this * x immediately followed by
+     * r = u + a * t, the pair of steps the IHT / GD loops repeat, as for the other widths -- one launch (clm8_mvm_f32_scale_and_add), the
+     * bits of mvm(x, t); u.scaleAndAdd(t, a, r). */
+    void mvm_scaleAndAdd(const CloverVector32 &x, const CloverVector32 &u, float a, CloverVector32 &t, CloverVector32 &r)
+    {
+        if (x.size() != getCols() || t.size_pad() != getRows()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
+        if (u.size_pad() != getRows() || r.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        clover_hip::check(clm8_mvm_f32_scale_and_add(dev_values(), dev_scales(), rows, cols, x.device_ro(), u.device_ro(), a, t.device_wo(),
+                                                     r.device_wo(), nullptr), "CloverMatrix8::mvm_scaleAndAdd");
+        t.commit();
+        r.commit();
+    }
+    /* in place: u = u + a * (this * x) */
+    void mvm_scaleAndAdd(const CloverVector32 &x, CloverVector32 &u, float a, CloverVector32 &t)
+    {
+        if (x.size() != getCols() || t.size_pad() != getRows()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
+        if (u.size_pad() != getRows()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        float *du = u.device_rw();
+        clover_hip::check(clm8_mvm_f32_scale_and_add(dev_values(), dev_scales(), rows, cols, x.device_ro(), du, a, t.device_wo(), du, nullptr),
+                          "CloverMatrix8::mvm_scaleAndAdd");
+        t.commit();
+        u.commit();
+    }
+    /* the same on this' * x (clm8_mvm_f32_transposed_scale_and_add): the bits of mvm_transposed(x, t); u.scaleAndAdd(t, a, r) */
+    void mvm_transposed_scaleAndAdd(const CloverVector32 &x, const CloverVector32 &u, float a, CloverVector32 &t, CloverVector32 &r)
+    {
+        if (x.size() != getRows() || t.size_pad() != getCols()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
+        if (u.size_pad() != getCols() || r.size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        clover_hip::check(clm8_mvm_f32_transposed_scale_and_add(dev_values(), dev_scales(), rows, cols, x.device_ro(), u.device_ro(), a, t.device_wo(),
+                                                                r.device_wo(), nullptr), "CloverMatrix8::mvm_transposed_scaleAndAdd");
+        t.commit();
+        r.commit();
+    }
+    void mvm_transposed_scaleAndAdd(const CloverVector32 &x, CloverVector32 &u, float a, CloverVector32 &t)
+    {
+        if (x.size() != getRows() || t.size_pad() != getCols()) { std::cout << "MVM can not be performed. Exiting ..." << std::endl; exit(1); }
+        if (u.size_pad() != getCols()) { std::cout << "Vectors do not have the same size. Exiting ..." << std::endl; exit(1); }
+        float *du = u.device_rw();
+        clover_hip::check(clm8_mvm_f32_transposed_scale_and_add(dev_values(), dev_scales(), rows, cols, x.device_ro(), du, a, t.device_wo(), du, nullptr),
+                          "CloverMatrix8::mvm_transposed_scaleAndAdd");
+        t.commit();
+        u.commit();
+    }
+    /* The reference's Q_IHT / Q_GD loop (01_measure.h:923-946, 999-1021) on <CloverMatrix8, CloverVector32> with this matrix as Phi, in one
+     * call (clm8_iht_f32): x.clear(), then `iterations` times t1 = Phi x; t2 = y - t1; t3 = PhiT t2; x += mu t3; [threshold(K)] -- one
+     * fused launch per product plus the threshold, the bits of the five method calls.  The threshold is the one x.threshold_parallel(K)
+     * would take under the exactness switch (default: the reference's survivors). */
+    void iht_loop(CloverMatrix8 &PhiT, CloverVector32 &x, const CloverVector32 &y, CloverVector32 &t1, CloverVector32 &t2, CloverVector32 &t3,
+                  uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    {
+        if (PhiT.rows != cols || PhiT.cols != rows || x.size_pad() != getCols() || y.size_pad() != getRows() || t1.size_pad() != getRows() ||
+            t2.size_pad() != getRows() || t3.size_pad() != getCols()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm8_iht_f32(dev_values(), dev_scales(), PhiT.dev_values(), PhiT.dev_scales(), rows, cols, x.device_wo(), x.size(),
+                                       y.device_ro(), t1.device_wo(), t2.device_wo(), t3.device_wo(), iterations, K, mu, thr, nullptr),
+                          "CloverMatrix8::iht_loop");
+        x.commit();
+        if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
+    }
+    /* iht_loop without PhiT (clm8_iht_f32_one_matrix): t3 = Phi' t2 comes from this matrix; the bits of iht_loop with PhiT = transpose of
+     * this.  Half the resident matrix bytes; DESIGN.md 3 has what that costs per iteration. */
+    void iht_loop_one_matrix(CloverVector32 &x, const CloverVector32 &y, CloverVector32 &t1, CloverVector32 &t2, CloverVector32 &t3,
+                             uint64_t iterations, uint64_t K, float mu, bool with_threshold)
+    {
+        if (x.size_pad() != getCols() || y.size_pad() != getRows() || t1.size_pad() != getRows() || t2.size_pad() != getRows() ||
+            t3.size_pad() != getCols()) {
+            std::cout << "MVM can not be performed. Exiting ..." << std::endl;
+            exit(1);
+        }
+        const int thr = !with_threshold ? 0 : (clover_hip::threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        clover_hip::check(clm8_iht_f32_one_matrix(dev_values(), dev_scales(), rows, cols, x.device_wo(), x.size(), y.device_ro(), t1.device_wo(),
+                                                  t2.device_wo(), t3.device_wo(), iterations, K, mu, thr, nullptr),
+                          "CloverMatrix8::iht_loop_one_matrix");
+        x.commit();
+        if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
+    }
+#endif
     /* :550-556: double accumulation on the host */
     void mvm_scalar(const CloverVector32 &productVector, CloverVector32 &resultVector)
     {

@@ -1181,6 +1181,108 @@ if any(selected(r) for r in M4F32_ROWS):
         sys.exit(0)
 
 
+# ---- CloverMatrix8 on fp32 vectors (matrix8.hip, matrix8_f32_t.hip; clover_hip_m8_f32.h): the rows of the block above at one byte per
+# element.  m8_mvm_f32_transposed_<n>^2: clm8_mvm_f32_transposed beside (a) clm8_transpose + clm8_mvm_f32 and (b) clm8_mvm_f32 on a held A'
+# (65536^2 holds 8 GiB: the matrix and its transpose).  m8_mvm_f32_scale_and_add_<n>^2 / m8_mvm_f32_transposed_scale_and_add_<n>^2: the
+# fused call beside the two calls it replaces.  m8_f32_iht_loop_N8192 (Phi 4096 x 8192, FAST): clm8_iht_f32 and clm8_iht_f32_one_matrix
+# beside the five calls issued one by one, the baseline's threshold in the FAST mode too; ms per iteration.  8192^2 is cache-resident
+# (64 MiB): no share of the HBM peak is claimed for it.
+# KB_ONLY=m8_mvm_f32_,m8_f32_iht_loop selects them and the run ends after them.
+M8F32_ROWS = tuple(f"{k}_{nb}^2" for nb in MVT_SIZES for k in ("m8_mvm_f32_transposed", "m8_mvm_f32_transpose_then_mvm", "m8_mvm_f32_held_transpose",
+                                                                "m8_mvm_f32_scale_and_add", "m8_mvm_f32_transposed_scale_and_add")) + ("m8_f32_iht_loop_N8192",)
+
+if any(selected(r) for r in M8F32_ROWS):
+    for nb in MVT_SIZES:
+        if not any(selected(r) for r in M8F32_ROWS if r.endswith(f"_{nb}^2")):
+            continue
+        fA, fsA, fAt, fsAt = hip.alloc(nb * nb), hip.alloc(4 * (nb // 64) ** 2), hip.alloc(nb * nb), hip.alloc(4 * (nb // 64) ** 2)
+        hip.check(lib.clv_fill_random_nibbles(fA.ptr, fA.nbytes, 91, 0, None))           # random bytes: every value of an int8
+        hip.check(lib.clv_fill_random_scales(fsA.ptr, fsA.nbytes // 4, 92, 0, None))
+        fx, fu, ft, fr = (hip.alloc(4 * nb) for _ in range(4))
+        hip.check(lib.clv_fill_random_ints_f32(fx.ptr, nb, 10, 93, 0, None))
+        hip.check(lib.clv_fill_random_ints_f32(fu.ptr, nb, 10, 94, 0, None))
+        hip.check(lib.clm8_transpose(fA.ptr, fsA.ptr, nb, nb, fAt.ptr, fsAt.ptr, None))
+        reps = 20 if nb == 8192 else 10 if nb == 32768 else 4
+        hbm = nb > 8192
+        mat_b = nb * nb + 4 * (nb // 64) ** 2
+        one_b = mat_b + 8 * nb
+
+        def direct_m8():
+            hip.check(lib.clm8_mvm_f32_transposed(fA.ptr, fsA.ptr, nb, nb, fx.ptr, fr.ptr, None))
+
+        def pair_m8():
+            hip.check(lib.clm8_transpose(fA.ptr, fsA.ptr, nb, nb, fAt.ptr, fsAt.ptr, None))
+            hip.check(lib.clm8_mvm_f32(fAt.ptr, fsAt.ptr, nb, nb, fx.ptr, fr.ptr, None))
+
+        def held_m8():
+            hip.check(lib.clm8_mvm_f32(fAt.ptr, fsAt.ptr, nb, nb, fx.ptr, fr.ptr, None))
+        if any(selected(f"{k}_{nb}^2") for k in ("m8_mvm_f32_transposed", "m8_mvm_f32_transpose_then_mvm", "m8_mvm_f32_held_transpose")):
+            d, p, h = alternated((direct_m8, pair_m8, held_m8), reps=reps)
+            md, mp, mh = d[len(d) // 2], p[len(p) // 2], h[len(h) // 2]
+            res[f"m8_mvm_f32_transposed_{nb}^2"] = summary(d, one_b, hbm)
+            res[f"m8_mvm_f32_transpose_then_mvm_{nb}^2"] = summary(p, 3 * mat_b + 8 * nb, hbm)
+            res[f"m8_mvm_f32_held_transpose_{nb}^2"] = summary(h, one_b, hbm)
+            res[f"m8_mvm_f32_transposed_{nb}^2"].update({
+                "speedup_over_transpose_then_mvm": round(mp / md, 3), "faster_than_the_pair_by_more_than_its_spread": bool(mp - md > p[-1] - p[0]),
+                "ratio_to_mvm_on_a_held_transpose": round(md / mh, 3), "within_the_spread_of_the_held_transpose_call": bool(abs(md - mh) <= h[-1] - h[0])})
+        for name, fused_fn, plain_fn in (("m8_mvm_f32_scale_and_add", lib.clm8_mvm_f32_scale_and_add, lib.clm8_mvm_f32),
+                                         ("m8_mvm_f32_transposed_scale_and_add", lib.clm8_mvm_f32_transposed_scale_and_add, lib.clm8_mvm_f32_transposed)):
+            if not selected(f"{name}_{nb}^2"):
+                continue
+
+            def fused_call(fused_fn=fused_fn):
+                hip.check(fused_fn(fA.ptr, fsA.ptr, nb, nb, fx.ptr, fu.ptr, 0.37, ft.ptr, fr.ptr, None))
+
+            def two_calls(plain_fn=plain_fn):
+                hip.check(plain_fn(fA.ptr, fsA.ptr, nb, nb, fx.ptr, ft.ptr, None))
+                hip.check(lib.clv_f32_scale_and_add(fu.ptr, ft.ptr, 0.37, nb, fr.ptr, None))
+            f, t2 = alternated((fused_call, two_calls), reps=reps)
+            mf, m2 = f[len(f) // 2], t2[len(t2) // 2]
+            res[f"{name}_{nb}^2"] = summary(f, mat_b + 16 * nb, hbm)
+            res[f"{name}_{nb}^2"].update({"two_calls_ms": round(m2, 5), "two_calls_rounds_ms": [round(v, 5) for v in t2],
+                                          "two_calls_spread_ms": round(t2[-1] - t2[0], 5), "ratio_to_the_two_calls": round(mf / m2, 3),
+                                          "not_slower_than_the_two_calls_by_more_than_their_spread": bool(mf - m2 <= t2[-1] - t2[0])})
+        del fA, fsA, fAt, fsAt
+    if selected("m8_f32_iht_loop_N8192"):
+        im, inn, iters = 4096, 8192, 20
+        P, sP, PT, sPT = hip.alloc(im * inn), hip.alloc(4 * (im // 64) * (inn // 64)), hip.alloc(im * inn), hip.alloc(4 * (im // 64) * (inn // 64))
+        hip.check(lib.clv_fill_random_nibbles(P.ptr, P.nbytes, 95, 0, None))
+        hip.check(lib.clv_fill_random_scales(sP.ptr, sP.nbytes // 4, 96, 0, None))
+        hip.check(lib.clm8_transpose(P.ptr, sP.ptr, im, inn, PT.ptr, sPT.ptr, None))
+        vy, vx, vt1, vt2, vt3 = (hip.alloc(4 * n) for n in (im, inn, im, im, inn))
+        hip.check(lib.clv_fill_random_ints_f32(vy.ptr, im, 10, 97, 0, None))
+        K, mu = im // 4, 2.0 ** -24
+        tail = (im, inn, vx.ptr, inn, vy.ptr, vt1.ptr, vt2.ptr, vt3.ptr, iters, K, mu, 1, None)
+
+        def two_m8():
+            hip.check(lib.clm8_iht_f32(P.ptr, sP.ptr, PT.ptr, sPT.ptr, *tail))
+
+        def one_m8():
+            hip.check(lib.clm8_iht_f32_one_matrix(P.ptr, sP.ptr, *tail))
+
+        def five_calls_m8():
+            hip.check(lib.clv_memset(vx.ptr, 0, 4 * inn, None))
+            for _ in range(iters):
+                hip.check(lib.clm8_mvm_f32(P.ptr, sP.ptr, im, inn, vx.ptr, vt1.ptr, None))
+                hip.check(lib.clv_f32_scale_and_add(vy.ptr, vt1.ptr, -1.0, im, vt2.ptr, None))
+                hip.check(lib.clm8_mvm_f32(PT.ptr, sPT.ptr, inn, im, vt2.ptr, vt3.ptr, None))
+                hip.check(lib.clv_f32_scale_and_add(vx.ptr, vt3.ptr, mu, inn, vx.ptr, None))
+                hip.check(lib.clv_f32_threshold_mode(vx.ptr, inn, inn, K, 0, None, None))      # 0 = CLV_THRESHOLD_FAST, as the loops' threshold = 1
+        t2m, t1m, t5 = ([v / iters for v in t] for t in alternated((two_m8, one_m8, five_calls_m8), reps=2))
+        m2m, m1m, m5 = t2m[len(t2m) // 2], t1m[len(t1m) // 2], t5[len(t5) // 2]
+        res["m8_f32_iht_loop_N8192"] = {
+            "clm8_iht_f32_ms_per_iteration": round(m2m, 5), "clm8_iht_f32_one_matrix_ms_per_iteration": round(m1m, 5),
+            "five_calls_ms_per_iteration": round(m5, 5), "clm8_iht_f32_rounds_ms": [round(v, 5) for v in t2m],
+            "clm8_iht_f32_one_matrix_rounds_ms": [round(v, 5) for v in t1m], "five_calls_rounds_ms": [round(v, 5) for v in t5],
+            "two_matrices_over_five_calls": round(m2m / m5, 3), "one_matrix_over_two_matrices": round(m1m / m2m, 3),
+            "note": f"calls of {iters} iterations, Phi 4096 x 8192 (32 MiB of bytes: cache-resident), K = m / 4, FAST threshold on both sides; the "
+                    "five calls are issued from Python one by one on the same buffers, all on the device"}
+        del P, sP, PT, sPT
+    if ONLY and all(any(o in r for r in M8F32_ROWS) for o in ONLY.split(",")):
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
+
+
 # ---- vector ops at n = 2^30 (4 GiB fp32 source, 512 MiB + 64 MiB quantized) and n = 2^24
 for logn in (24, 30):
     n = 1 << logn
