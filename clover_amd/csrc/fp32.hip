@@ -14,6 +14,7 @@
 // fp32 subnormals are kept (hipcc's default kernel mode; no flushing instruction is used), every sum is a separately rounded v_add_f32
 // (-ffp-contract=off) and every fma one fused v_fma_f32 / half of a v_pk_fma_f32.
 #include "dot_common.h"
+#include "mvm_f32_host.h"           // f32_iht_loop: the loop body the quantized matrices share with clm_f32_iht
 #include "clover_hip_fp32.h"
 
 template <bool NT, typename T> __device__ __forceinline__ T ld_stream(const T *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
@@ -409,14 +410,9 @@ extern "C" int clm_f32_iht(const float *Phi, const float *PhiT, uint64_t m, uint
                 (unsigned long long)x_len);
     CLV_REQUIRE(threshold >= 0 && threshold <= 2, "clm_f32_iht: unknown threshold %d", threshold);
     CLV_REQUIRE(F32_ALIGNED(Phi) && F32_ALIGNED(PhiT) && F32_ALIGNED(x) && F32_ALIGNED(t2), "clm_f32_iht: the matrices, x and t2 must be 16-byte aligned");
-    int rc = clv_internal_f32_clear(x, n, as_stream(stream));                                            // x.clear()
-    for (uint64_t it = 0; !rc && it < iterations; it++) {
-        rc = clm_f32_mvm_scale_and_add(Phi, m, n, x, y, -1.0f, t1, t2, stream);                          // t1 = Phi x; t2 = y - t1
-        if (!rc) rc = clm_f32_mvm_scale_and_add(PhiT, n, m, t2, x, mu, t3, x, stream);                   // t3 = Phi' t2; x += mu t3
-        if (!rc && threshold)                                                          // keep the K largest (2: the reference's survivor order)
-            rc = clv_f32_threshold_mode(x, x_len, n, K, threshold == 2 ? CLV_THRESHOLD_REFERENCE : CLV_THRESHOLD_FAST, nullptr, stream);
-    }
-    return rc;
+    return f32_iht_loop(
+        x, x_len, n, iterations, K, threshold, stream, [&] { return clm_f32_mvm_scale_and_add(Phi, m, n, x, y, -1.0f, t1, t2, stream); },
+        [&] { return clm_f32_mvm_scale_and_add(PhiT, n, m, t2, x, mu, t3, x, stream); });
 }
 
 extern "C" int clm_f32_transpose(const float *A, uint64_t rows, uint64_t cols, float *At, void *stream)

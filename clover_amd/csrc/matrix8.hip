@@ -525,31 +525,32 @@ extern "C" int clm8_iht(const int8_t *Phi, const float *sPhi, const int8_t *PhiT
     return rc;
 }
 
+// the launch of k_m8_mvm_f32 for checked arguments: 32 rows per workgroup, nontemporal under the rule of m8f32_streaming
+template <typename... FUSE>
+static int m8f32_launch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *r, hipStream_t st, FUSE... fuse)
+{
+    const dim3 grid((unsigned)(rows / 32)), block(256);
+    if (m8f32_streaming(rows, cols))
+        hipLaunchKernelGGL((k_m8_mvm_f32<true, FUSE...>), grid, block, 0, st, (const uint32_t *)A, sA, cols, (const f32x4 *)x, r, fuse...);
+    else
+        hipLaunchKernelGGL((k_m8_mvm_f32<false, FUSE...>), grid, block, 0, st, (const uint32_t *)A, sA, cols, (const f32x4 *)x, r, fuse...);
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+
 extern "C" int clm8_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *r, void *stream)
 {
     int rc = clv_internal_m8_check_mvm("clm8_mvm_f32", A, sA, rows, cols, x, r);
     if (rc) return rc;
     if (!rows) return CLV_OK;
-    const dim3 grid((unsigned)(rows / 32)), block(256);
-    if (rows * cols > (256ull << 20))
-        hipLaunchKernelGGL(k_m8_mvm_f32<true>, grid, block, 0, as_stream(stream), (const uint32_t *)A, sA, cols, (const f32x4 *)x, r);
-    else
-        hipLaunchKernelGGL(k_m8_mvm_f32<false>, grid, block, 0, as_stream(stream), (const uint32_t *)A, sA, cols, (const f32x4 *)x, r);
-    CLV_LAUNCH_CHECK();
-    return CLV_OK;
+    return m8f32_launch(A, sA, rows, cols, x, r, as_stream(stream));
 }
 
-// clm8_mvm_f32_scale_and_add (matrix8_f32_t.hip checks the arguments): the launch of clm8_mvm_f32 with the epilogue pack
+// clm8_mvm_f32_scale_and_add (mvm_f32_host.h checks the arguments): the launch of clm8_mvm_f32 with the epilogue pack
 int clv_internal_m8_mvm_f32_fused(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *t, const M4F32Fuse &fuse,
                                   hipStream_t st)
 {
-    const dim3 grid((unsigned)(rows / 32)), block(256);
-    if (m8f32_streaming(rows, cols))
-        hipLaunchKernelGGL((k_m8_mvm_f32<true, M4F32Fuse>), grid, block, 0, st, (const uint32_t *)A, sA, cols, (const f32x4 *)x, t, fuse);
-    else
-        hipLaunchKernelGGL((k_m8_mvm_f32<false, M4F32Fuse>), grid, block, 0, st, (const uint32_t *)A, sA, cols, (const f32x4 *)x, t, fuse);
-    CLV_LAUNCH_CHECK();
-    return CLV_OK;
+    return m8f32_launch(A, sA, rows, cols, x, t, st, fuse);
 }
 
 extern "C" int clm8_transpose(const int8_t *q, const float *s, uint64_t rows, uint64_t cols, int8_t *qt, float *st, void *stream)

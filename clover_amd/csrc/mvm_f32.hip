@@ -135,37 +135,34 @@ __global__ __launch_bounds__(256, MVF_WAVES) void k_m4_mvm_f32(const u32x4 *__re
     if (a == 0) m4f32_store(r, row, dot, fuse_u, fuse...);
 }
 
+// the launch of k_m4_mvm_f32 for checked arguments: 64 rows per workgroup, nontemporal under the rule of m4f32_streaming
+template <typename... FUSE>
+static int m4f32_launch(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *r, hipStream_t st, FUSE... fuse)
+{
+    const size_t lds = (MVF_CHUNK + MVF_CHUNK / 64) * sizeof(float);                     // 65 KiB
+    const dim3 grid((unsigned)(rows / 64));
+    if (m4f32_streaming(rows, cols)) {
+        CLV_HIP(hipFuncSetAttribute((const void *)k_m4_mvm_f32<true, FUSE...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_m4_mvm_f32<true, FUSE...>), grid, dim3(256), lds, st, (const u32x4 *)A, sA, cols, x, r, fuse...);
+    } else {
+        CLV_HIP(hipFuncSetAttribute((const void *)k_m4_mvm_f32<false, FUSE...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_m4_mvm_f32<false, FUSE...>), grid, dim3(256), lds, st, (const u32x4 *)A, sA, cols, x, r, fuse...);
+    }
+    CLV_LAUNCH_CHECK();
+    return CLV_OK;
+}
+
 extern "C" int clm4_mvm_f32(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *r, void *stream)
 {
     CLV_REQUIRE(A && sA && x && r, "clm4_mvm_f32: null pointer");
     CLV_REQUIRE(rows % 64 == 0 && cols % 128 == 0 && rows / 64 <= 0x7FFFFFFFull, "clm4_mvm_f32: rows=%llu must be a multiple of 64 (a row shard) and cols=%llu of 128",
                 (unsigned long long)rows, (unsigned long long)cols);
     if (!rows) return CLV_OK;
-    const size_t lds = (MVF_CHUNK + MVF_CHUNK / 64) * sizeof(float);                     // 65 KiB
-    const dim3 grid((unsigned)(rows / 64));
-    if (rows * (cols / 2) > (256ull << 20)) {
-        CLV_HIP(hipFuncSetAttribute((const void *)k_m4_mvm_f32<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_m4_mvm_f32<true>, grid, dim3(256), lds, as_stream(stream), (const u32x4 *)A, sA, cols, x, r);
-    } else {
-        CLV_HIP(hipFuncSetAttribute((const void *)k_m4_mvm_f32<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_m4_mvm_f32<false>, grid, dim3(256), lds, as_stream(stream), (const u32x4 *)A, sA, cols, x, r);
-    }
-    CLV_LAUNCH_CHECK();
-    return CLV_OK;
+    return m4f32_launch(A, sA, rows, cols, x, r, as_stream(stream));
 }
 
 int clv_internal_m4_mvm_f32_fused(const int8_t *A, const float *sA, uint64_t rows, uint64_t cols, const float *x, float *t, const M4F32Fuse &fuse,
                                   hipStream_t st)
 {
-    const size_t lds = (MVF_CHUNK + MVF_CHUNK / 64) * sizeof(float);
-    const dim3 grid((unsigned)(rows / 64));
-    if (m4f32_streaming(rows, cols)) {
-        CLV_HIP(hipFuncSetAttribute((const void *)k_m4_mvm_f32<true, M4F32Fuse>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_m4_mvm_f32<true, M4F32Fuse>), grid, dim3(256), lds, st, (const u32x4 *)A, sA, cols, x, t, fuse);
-    } else {
-        CLV_HIP(hipFuncSetAttribute((const void *)k_m4_mvm_f32<false, M4F32Fuse>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_m4_mvm_f32<false, M4F32Fuse>), grid, dim3(256), lds, st, (const u32x4 *)A, sA, cols, x, t, fuse);
-    }
-    CLV_LAUNCH_CHECK();
-    return CLV_OK;
+    return m4f32_launch(A, sA, rows, cols, x, t, st, fuse);
 }

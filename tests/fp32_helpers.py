@@ -8,6 +8,7 @@ test_fp32_capture.py).
 - data: make_ops (the value kinds the kernels have to get right), threshold_data, iht_problem."""
 import ctypes as C
 import functools
+import re
 import subprocess
 from pathlib import Path
 
@@ -242,3 +243,14 @@ def fast_threshold_model(x, n, k):
     keep[ties[:k - int(keep.sum())]] = True
     out[:n][~keep] = 0
     return out
+
+
+def with_project_headers(src, name, seen=None):
+    """the text of a source of clover_amd/csrc together with the headers of that directory it includes, directly or not -- common.h
+    excepted, which the whole library shares (its clv_env is for the families that read the environment)"""
+    seen = {"common.h"} if seen is None else seen
+    if name in seen or not (src / name).exists():
+        return ""
+    seen.add(name)
+    text = (src / name).read_text()
+    return text + "".join(with_project_headers(src, inc, seen) for inc in re.findall(r'^#include "([^"]+)"', text, flags=re.M))

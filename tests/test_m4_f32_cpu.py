@@ -24,7 +24,7 @@ import pytest
 import clover_amd.lib_binding as lb
 from clover_amd.build import HIP_SOURCES, build_hip_library, repo_root
 from clover_amd.lib_binding import load_library
-from fp32_helpers import rf  # noqa: F401  (fixture)
+from fp32_helpers import rf, with_project_headers  # noqa: F401  (fixture)
 from m4_f32_helpers import (CHUNK, COLS, LOOP_SHAPES, R_SHAPES, T_SHAPES, U, edge_problem, loop_problem, loop_reference, m4rt, problem, same,  # noqa: F401
                             tie_K)
 from test_mvm_batch_cpu import addr, failed
@@ -88,9 +88,14 @@ def test_the_signatures_follow_their_neighbours():
 def test_the_kernel_is_a_source_of_the_library_and_the_header_a_dependency():
     assert "mvm_f32_t.hip" in HIP_SOURCES
     src = repo_root() / "clover_amd" / "csrc"
-    text = (src / "mvm_f32_t.hip").read_text()
+    own = (src / "mvm_f32_t.hip").read_text()
+    text = with_project_headers(src, "mvm_f32_t.hip")            # the walk and the host driver are headers both widths include
+    for header in ("mvm_f32_t_device.h", "mvm_f32_host.h", "mvm_f32_device.h"):
+        assert (src / header).read_text() in text, header
     for shared in ("M4F32Fuse", "m4f32_store", "m4f32_streaming", "unpack8_16th", "times16_is_finite", '#include "mvm_f32_device.h"'):
         assert shared in text, shared
+    for width in ("m4f32_streaming", "unpack8_16th", "times16_is_finite"):      # what the 4-bit width puts into the shared code: its traits
+        assert width in own, width
     assert "M4F32Fuse" in (src / "mvm_f32.hip").read_text(), "the fused instantiation sits next to k_m4_mvm_f32"
     assert not re.search(r"\bgetenv\b|clv_env", text), "no environment hooks"
     assert "clover_hip_m4_f32.h" in (repo_root() / "clover_amd" / "build.py").read_text(), "the header is a dependency of the library"

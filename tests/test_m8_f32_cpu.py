@@ -24,7 +24,7 @@ import pytest
 import clover_amd.lib_binding as lb
 from clover_amd.build import HIP_SOURCES, build_hip_library, repo_root
 from clover_amd.lib_binding import load_library
-from fp32_helpers import rf  # noqa: F401  (fixture)
+from fp32_helpers import rf, with_project_headers  # noqa: F401  (fixture)
 from m8_f32_helpers import (CHUNK, COLS, LOOP_SHAPES, M8_UNROLL, R_SHAPES, T_SHAPES, TINY, U, edge_problem, loop_problem, loop_reference, m8rt,  # noqa: F401
                             problem, same, tie_K)
 from matrix8_helpers import m8  # noqa: F401  (fixture)
@@ -93,9 +93,14 @@ def test_the_signatures_follow_their_neighbours():
 def test_the_kernel_is_a_source_of_the_library_and_the_header_a_dependency():
     assert "matrix8_f32_t.hip" in HIP_SOURCES
     src = repo_root() / "clover_amd" / "csrc"
-    text = (src / "matrix8_f32_t.hip").read_text()
+    own = (src / "matrix8_f32_t.hip").read_text()
+    text = with_project_headers(src, "matrix8_f32_t.hip")        # the walk and the host driver are headers both widths include
+    for header in ("mvm_f32_t_device.h", "mvm_f32_host.h", "mvm_f32_device.h"):
+        assert (src / header).read_text() in text, header
     for shared in ("M4F32Fuse", "m4f32_store", "m8f32_streaming", "/ 127.0f", '#include "mvm_f32_device.h"'):
         assert shared in text, shared
+    for width in ("m8f32_streaming", "/ 127.0f"):                # what the 8-bit width puts into the shared code: its traits
+        assert width in own, width
     assert "M4F32Fuse" in (src / "matrix8.hip").read_text(), "the fused instantiation sits next to k_m8_mvm_f32"
     assert not re.search(r"\bgetenv\b|clv_env", text), "no environment hooks"
     assert "clover_hip_m8_f32.h" in (repo_root() / "clover_amd" / "build.py").read_text(), "the header is a dependency of the library"
