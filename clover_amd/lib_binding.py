@@ -263,6 +263,15 @@ SIGNATURES_M4_F32 = {
 # name -> (restype, argtypes); everything include/clover_hip_m8_f32.h declares: the same column for CloverMatrix8
 SIGNATURES_M8_F32 = {"clm8" + name[4:]: sig for name, sig in SIGNATURES_M4_F32.items()}
 
+# name -> (restype, argtypes); everything include/clover_hip_batch_f32.h declares (several fp32 vectors in one pass over a CloverMatrix4 or
+# a CloverMatrix8: plain, fused, the two-matrix IHT / GD loop for several signals); pointer arrays are HOST arrays of device pointers
+SIGNATURES_BATCH_F32 = {
+    "clm4_mvm_f32_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp]),
+    "clm4_mvm_f32_scale_and_add_batch": (C.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, C.c_float, _vp, _vp, _vp]),
+    "clm4_iht_f32_batch": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, C.c_float, C.c_int, _vp]),
+}
+SIGNATURES_BATCH_F32.update({"clm8" + name[4:]: sig for name, sig in list(SIGNATURES_BATCH_F32.items())})
+
 
 class CloverHipError(RuntimeError):
     pass
@@ -279,7 +288,7 @@ def load_library(path: str | Path | None = None, allow_probe: bool = False) -> C
     lib = C.CDLL(str(p))
     for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_FP32.items(), *SIGNATURES_BATCH_T.items(), *SIGNATURES_BATCH_T8.items(), *SIGNATURES_BATCH_T_V8.items(),
                               *SIGNATURES_BATCH_F16.items(), *SIGNATURES_F16_T.items(), *SIGNATURES_BATCH_F16_T.items(), *SIGNATURES_M4_F32.items(),
-                              *SIGNATURES_M8_F32.items()):
+                              *SIGNATURES_M8_F32.items(), *SIGNATURES_BATCH_F32.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -880,6 +889,62 @@ class CloverHip:
     def m8_iht_f32_one_matrix(self, qPhi, sPhi, m, n, y, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
                               prefill: int = 0x55):
         return self.m8_iht_f32(qPhi, sPhi, None, None, m, n, y, iterations, K, mu, threshold, x_len=x_len, prefill=prefill)
+
+    # several fp32 vectors with one CloverMatrix4 / CloverMatrix8 (include/clover_hip_batch_f32.h; lists in, lists out; the matrix pair and
+    # every vector a numpy array or a DevBuf)
+    def _mq_mvm_f32_batch(self, fn, qA, sA, rows, cols, xs):
+        (dq, ds), dx = self._m4_dev(qA, sA), [self._f32_dev(x) for x in xs]
+        dr = [self.alloc(max(4 * rows, 4)) for _ in xs]
+        pa = self.ptr_array
+        self.check(fn(dq.ptr, ds.ptr, rows, cols, len(xs), pa(dx), pa(dr), None))
+        return [r.download(np.float32, rows) for r in dr]
+
+    def _mq_mvm_f32_fused_batch(self, fn, qA, sA, rows, cols, xs, us, a, in_place, want_t):
+        (dq, ds), dx, du = self._m4_dev(qA, sA), [self._f32_dev(x) for x in xs], [self._f32_dev(u) for u in us]
+        dt = [self.alloc(max(4 * rows, 4)) for _ in xs] if want_t else None
+        dr = du if in_place else [self.alloc(max(4 * rows, 4)) for _ in xs]
+        pa = self.ptr_array
+        self.check(fn(dq.ptr, ds.ptr, rows, cols, len(xs), pa(dx), pa(du), a, pa(dt), pa(dr), None))
+        return [((dt[j].download(np.float32, rows) if want_t else None), dr[j].download(np.float32, rows)) for j in range(len(xs))]
+
+    def _mq_iht_f32_batch(self, fn, qPhi, sPhi, qPhiT, sPhiT, m, n, ys, iterations, K, mu, threshold, x_len, prefill):
+        b = [*self._m4_dev(qPhi, sPhi), *self._m4_dev(qPhiT, sPhiT)]
+        dy = [self._f32_dev(y) for y in ys]
+        lens = {"x": n, "t1": m, "t2": m, "t3": n}
+        v = {name: [self.alloc(max(4 * ln, 4)) for _ in ys] for name, ln in lens.items()}
+        for bufs in v.values():
+            for d in bufs:
+                self.check(self.lib.clv_memset(d.ptr, prefill, d.nbytes, None))
+        pa = self.ptr_array
+        self.check(fn(*[d.ptr for d in b], m, n, len(ys), pa(v["x"]), n if x_len is None else x_len, pa(dy), pa(v["t1"]), pa(v["t2"]), pa(v["t3"]),
+                      iterations, K, mu, threshold, None))
+        return [{name: v[name][j].download(np.float32, ln) for name, ln in lens.items()} for j in range(len(ys))]
+
+    def m4_mvm_f32_batch(self, qA, sA, rows, cols, xs):
+        """xs: list of fp32 vectors; returns the list of r of clm4_mvm_f32_batch"""
+        return self._mq_mvm_f32_batch(self.lib.clm4_mvm_f32_batch, qA, sA, rows, cols, xs)
+
+    def m4_mvm_f32_scale_and_add_batch(self, qA, sA, rows, cols, xs, us, a: float, in_place: bool = False, want_t: bool = True):
+        """xs, us: lists of fp32 vectors; returns the list of (t, r2) of clm4_mvm_f32_scale_and_add_batch; t is None when want_t is False"""
+        return self._mq_mvm_f32_fused_batch(self.lib.clm4_mvm_f32_scale_and_add_batch, qA, sA, rows, cols, xs, us, a, in_place, want_t)
+
+    def m4_iht_f32_batch(self, qPhi, sPhi, qPhiT, sPhiT, m, n, ys, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+                         prefill: int = 0x55):
+        """clm4_iht_f32_batch on buffers prefilled with `prefill` bytes; ys: list of y; returns per signal {"x", "t1", "t2", "t3"}"""
+        return self._mq_iht_f32_batch(self.lib.clm4_iht_f32_batch, qPhi, sPhi, qPhiT, sPhiT, m, n, ys, iterations, K, mu, threshold, x_len, prefill)
+
+    def m8_mvm_f32_batch(self, qA, sA, rows, cols, xs):
+        """xs: list of fp32 vectors; returns the list of r of clm8_mvm_f32_batch"""
+        return self._mq_mvm_f32_batch(self.lib.clm8_mvm_f32_batch, qA, sA, rows, cols, xs)
+
+    def m8_mvm_f32_scale_and_add_batch(self, qA, sA, rows, cols, xs, us, a: float, in_place: bool = False, want_t: bool = True):
+        """xs, us: lists of fp32 vectors; returns the list of (t, r2) of clm8_mvm_f32_scale_and_add_batch; t is None when want_t is False"""
+        return self._mq_mvm_f32_fused_batch(self.lib.clm8_mvm_f32_scale_and_add_batch, qA, sA, rows, cols, xs, us, a, in_place, want_t)
+
+    def m8_iht_f32_batch(self, qPhi, sPhi, qPhiT, sPhiT, m, n, ys, iterations: int, K: int, mu: float, threshold: int, x_len: int | None = None,
+                         prefill: int = 0x55):
+        """clm8_iht_f32_batch on buffers prefilled with `prefill` bytes; ys: list of y; returns per signal {"x", "t1", "t2", "t3"}"""
+        return self._mq_iht_f32_batch(self.lib.clm8_iht_f32_batch, qPhi, sPhi, qPhiT, sPhiT, m, n, ys, iterations, K, mu, threshold, x_len, prefill)
 
     def m8_transpose(self, q, s, rows, cols):
         dq, ds = self.to_device(q), self.to_device(s)

@@ -575,6 +575,32 @@ inline void Q_GD_one_matrix(CloverMatrix8 &Phi, CloverVector32 &x, CloverVector3
 {
     Phi.iht_loop_one_matrix(x, y, t1, t2, t3, iterations, 0, mu, false);
 }
+/* the same for `count` signals with ONE Phi (CloverMatrix4::iht_loop_batch -> clm4_iht_f32_batch, clover_hip_batch_f32.h): bit-identical to
+ * calling Q_IHT / Q_GD above signal after signal */
+inline void Q_IHT_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector32 *const *x, CloverVector32 *const *y, CloverVector32 *const *t1,
+                        CloverVector32 *const *t2, CloverVector32 *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
+                        const float mu)
+{
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, K, mu, true);
+}
+inline void Q_GD_batch(CloverMatrix4 &Phi, CloverMatrix4 &PhiT, CloverVector32 *const *x, CloverVector32 *const *y, CloverVector32 *const *t1,
+                       CloverVector32 *const *t2, CloverVector32 *const *t3, const uint64_t count, const uint64_t iterations, const float mu)
+{
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+}
+/* the same for `count` signals with ONE Phi (CloverMatrix8::iht_loop_batch -> clm8_iht_f32_batch, clover_hip_batch_f32.h): bit-identical to
+ * calling Q_IHT / Q_GD above signal after signal */
+inline void Q_IHT_batch(CloverMatrix8 &Phi, CloverMatrix8 &PhiT, CloverVector32 *const *x, CloverVector32 *const *y, CloverVector32 *const *t1,
+                        CloverVector32 *const *t2, CloverVector32 *const *t3, const uint64_t count, const uint64_t iterations, const uint64_t K,
+                        const float mu)
+{
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, K, mu, true);
+}
+inline void Q_GD_batch(CloverMatrix8 &Phi, CloverMatrix8 &PhiT, CloverVector32 *const *x, CloverVector32 *const *y, CloverVector32 *const *t1,
+                       CloverVector32 *const *t2, CloverVector32 *const *t3, const uint64_t count, const uint64_t iterations, const float mu)
+{
+    Phi.iht_loop_batch(PhiT, x, y, t1, t2, t3, count, iterations, 0, mu, false);
+}
 #endif
 
 #endif

@@ -565,6 +565,29 @@ public:
         x.commit();
         if (iterations) { t1.commit(); t2.commit(); t3.commit(); }
     }
+    /* Not in the reference: the batch methods above for CloverVector32 vectors (clm8_mvm_f32_batch, clm8_mvm_f32_scale_and_add_batch,
+     * clm8_iht_f32_batch; clover_hip_batch_f32.h): one pass over the matrix per group of CLM4_MVM_BATCH_MAX vectors, the bits of mvm,
+     * mvm_scaleAndAdd and iht_loop called vector after vector. */
+    void mvm_batch(const CloverVector32 *const *x, CloverVector32 *const *r, uint64_t count)
+    {
+        clover_hip::BatchF32<CloverMatrix8>::mvm(batch_view(), x, r, count, "CloverMatrix8::mvm_batch");
+    }
+    void mvm_scaleAndAdd_batch(const CloverVector32 *const *x, const CloverVector32 *const *u, float a, CloverVector32 *const *t,
+                               CloverVector32 *const *r, uint64_t count)
+    {
+        clover_hip::BatchF32<CloverMatrix8>::fused(batch_view(), x, u, a, t, r, count, "CloverMatrix8::mvm_scaleAndAdd_batch");
+    }
+    void mvm_scaleAndAdd_batch(const CloverVector32 *const *x, CloverVector32 *const *u, float a, CloverVector32 *const *t, uint64_t count)
+    {
+        clover_hip::BatchF32<CloverMatrix8>::fused_in_place(batch_view(), x, u, a, t, count, "CloverMatrix8::mvm_scaleAndAdd_batch");
+    }
+    void iht_loop_batch(CloverMatrix8 &PhiT, CloverVector32 *const *x, const CloverVector32 *const *y, CloverVector32 *const *t1,
+                        CloverVector32 *const *t2, CloverVector32 *const *t3, uint64_t count, uint64_t iterations, uint64_t K, float mu,
+                        bool with_threshold)
+    {
+        clover_hip::BatchF32<CloverMatrix8>::iht_loop(batch_view(), PhiT.batch_view(), x, y, t1, t2, t3, count, iterations, K, mu, with_threshold,
+                                                      "CloverMatrix8::iht_loop_batch");
+    }
 #endif
     /* :550-556: double accumulation on the host */
     void mvm_scalar(const CloverVector32 &productVector, CloverVector32 &resultVector)

@@ -16,6 +16,9 @@
 #include "clover_hip_batch_t.h"    /* the batched transposed calls: headers of their own beside clover_hip.h */
 #include "clover_hip_batch_t8.h"
 #include "clover_hip_batch_t_v8.h"
+#ifdef CLOVER_FP32_ON_DEVICE
+#include "clover_hip_batch_f32.h"  /* several CloverVector32 with one CloverMatrix4 / CloverMatrix8 */
+#endif
 
 class CloverMatrix4;
 class CloverMatrix8;
@@ -212,6 +215,95 @@ struct Batch {
         }
     }
 };
+
+#ifdef CLOVER_FP32_ON_DEVICE
+/* The same for CloverVector32 vectors (clover_hip_batch_f32.h), only where CloverVector32's own arithmetic runs on the device: plain fp32,
+ * no scales, no generator, no positioned form.  BatchF32Abi names the three entry points of a matrix class; the bodies of BatchF32<M> are
+ * what the CloverVector32 overloads of the batch methods call.  V is CloverVector32 (a template parameter, so that this header needs no
+ * more than its name). */
+typedef decltype(&clm4_mvm_f32_batch) batch_f32_mvm_fn;
+typedef decltype(&clm4_mvm_f32_scale_and_add_batch) batch_f32_fused_fn;
+typedef decltype(&clm4_iht_f32_batch) batch_f32_loop_fn;
+
+template <class M> struct BatchF32Abi;
+template <> struct BatchF32Abi<CloverMatrix4> {
+    static batch_f32_mvm_fn mvm() { return clm4_mvm_f32_batch; }
+    static batch_f32_fused_fn fused() { return clm4_mvm_f32_scale_and_add_batch; }
+    static batch_f32_loop_fn loop() { return clm4_iht_f32_batch; }
+};
+template <> struct BatchF32Abi<CloverMatrix8> {
+    static batch_f32_mvm_fn mvm() { return clm8_mvm_f32_batch; }
+    static batch_f32_fused_fn fused() { return clm8_mvm_f32_scale_and_add_batch; }
+    static batch_f32_loop_fn loop() { return clm8_iht_f32_batch; }
+};
+
+template <class V>
+std::vector<float *> dev_f32_inputs(const V *const *v, uint64_t count)
+{
+    std::vector<float *> a;
+    for (uint64_t j = 0; j < count; j++) a.push_back(const_cast<float *>(v[j]->device_ro()));
+    return a;
+}
+template <class V>
+std::vector<float *> dev_f32_outputs(V *const *v, uint64_t count, bool read_too)
+{
+    std::vector<float *> a;
+    for (uint64_t j = 0; j < count; j++) a.push_back(read_too ? v[j]->device_rw() : v[j]->device_wo());
+    return a;
+}
+
+template <class M>
+struct BatchF32 {
+    /* r[j] = A x[j] */
+    template <class V>
+    static void mvm(const BatchMatrix &A, const V *const *x, V *const *r, uint64_t count, const char *what)
+    {
+        for (uint64_t j = 0; j < count; j++)
+            if (x[j]->size() != A.cols || r[j]->size_pad() != A.rows) batch_exit("MVM can not be performed. Exiting ...");
+        const std::vector<float *> px = dev_f32_inputs(x, count), pr = dev_f32_outputs(r, count, false);
+        check(BatchF32Abi<M>::mvm()(A.q, A.s, A.rows, A.cols, count, px.data(), pr.data(), nullptr), what);
+        for (uint64_t j = 0; j < count; j++) r[j]->commit();
+    }
+    /* t[j] = A x[j], r[j] = u[j] + a * t[j] */
+    template <class V>
+    static void fused(const BatchMatrix &A, const V *const *x, const V *const *u, float a, V *const *t, V *const *r, uint64_t count, const char *what)
+    {
+        batch_check_fused<V>(A.cols, A.rows, x, u, t, r, count);
+        const std::vector<float *> px = dev_f32_inputs(x, count), pu = dev_f32_inputs(u, count), pt = dev_f32_outputs(t, count, false),
+                                   pr = dev_f32_outputs(r, count, false);
+        check(BatchF32Abi<M>::fused()(A.q, A.s, A.rows, A.cols, count, px.data(), pu.data(), a, pt.data(), pr.data(), nullptr), what);
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); r[j]->commit(); }
+    }
+    /* in place: u[j] = u[j] + a * t[j]; u[j] is mapped read-write and is both the call's u and its r2 */
+    template <class V>
+    static void fused_in_place(const BatchMatrix &A, const V *const *x, V *const *u, float a, V *const *t, uint64_t count, const char *what)
+    {
+        batch_check_fused<V>(A.cols, A.rows, x, u, t, nullptr, count);
+        const std::vector<float *> px = dev_f32_inputs(x, count), pu = dev_f32_outputs(u, count, true), pt = dev_f32_outputs(t, count, false);
+        check(BatchF32Abi<M>::fused()(A.q, A.s, A.rows, A.cols, count, px.data(), pu.data(), a, pt.data(), pu.data(), nullptr), what);
+        for (uint64_t j = 0; j < count; j++) { t[j]->commit(); u[j]->commit(); }
+    }
+    /* the IHT / GD loop for `count` signals with A as Phi and AT as its stored transpose */
+    template <class V>
+    static void iht_loop(const BatchMatrix &A, const BatchMatrix &AT, V *const *x, const V *const *y, V *const *t1, V *const *t2, V *const *t3,
+                         uint64_t count, uint64_t iterations, uint64_t K, float mu, bool with_threshold, const char *what)
+    {
+        for (uint64_t j = 0; j < count; j++)
+            if (AT.rows != A.cols || AT.cols != A.rows || x[j]->size_pad() != A.cols || y[j]->size_pad() != A.rows || t1[j]->size_pad() != A.rows ||
+                t2[j]->size_pad() != A.rows || t3[j]->size_pad() != A.cols || x[j]->size() != x[0]->size())
+                batch_exit("MVM can not be performed. Exiting ...");
+        const std::vector<float *> py = dev_f32_inputs(y, count), px = dev_f32_outputs(x, count, false), p1 = dev_f32_outputs(t1, count, false),
+                                   p2 = dev_f32_outputs(t2, count, false), p3 = dev_f32_outputs(t3, count, false);
+        const int thr = !with_threshold ? 0 : (threshold_mode() == CLV_THRESHOLD_FAST ? 1 : 2);
+        check(BatchF32Abi<M>::loop()(A.q, A.s, AT.q, AT.s, A.rows, A.cols, count, px.data(), count ? x[0]->size() : 0, py.data(), p1.data(),
+                                     p2.data(), p3.data(), iterations, K, mu, thr, nullptr), what);
+        for (uint64_t j = 0; j < count; j++) {
+            x[j]->commit();
+            if (iterations) { t1[j]->commit(); t2[j]->commit(); t3[j]->commit(); }
+        }
+    }
+};
+#endif
 
 }      /* namespace clover_hip */
 

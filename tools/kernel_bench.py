@@ -1283,6 +1283,89 @@ if any(selected(r) for r in M8F32_ROWS):
         sys.exit(0)
 
 
+# ---- several fp32 vectors with one CloverMatrix4 / CloverMatrix8 (mvm_f32_batch.hip; clover_hip_batch_f32.h): every row pairs the batch
+# call, on the batched kernel (CLV_MVM_BATCH=1), with the same vectors issued as g single calls in the same process, rounds alternated.
+# m{4,8}_mvm_f32_batch{2,4,8}_{32768,65536}^2: the plain product (streaming); m{4,8}_mvm_f32_saa_batch{2,4,8}_8192x4096: the fused
+# x += mu Phi' t2 step of the IHT shape (cache-resident); m{4,8}_iht_f32_batch8_N8192: clm{4,8}_iht_f32_batch against 8 x clm{4,8}_iht_f32,
+# ms per iteration for 8 signals.  KB_ONLY=m4_mvm_f32_batch,m4_mvm_f32_saa_batch,m4_iht_f32_batch (or m8_...) selects them and the run
+# ends after them.
+MQF32B_GROUPS = (2, 4, 8)
+MQF32B_ROWS = tuple(f"m{w}_mvm_f32_batch{g}_{nb}^2" for w in (4, 8) for nb in (32768, 65536) for g in MQF32B_GROUPS) + \
+    tuple(f"m{w}_mvm_f32_saa_batch{g}_8192x4096" for w in (4, 8) for g in MQF32B_GROUPS) + tuple(f"m{w}_iht_f32_batch8_N8192" for w in (4, 8))
+
+
+def rec_f32_batch(name, nbytes_single, g, single, batch, reps, hbm, per=1):
+    if not selected(name):
+        return
+    one, many = ([v / per for v in t] for t in alternated((single, forced_batch(batch)), reps=reps))
+    o, m, spread = one[len(one) // 2], many[len(many) // 2], one[-1] - one[0]
+    res[name] = {"vectors": g, "batch_ms": round(m, 5), "single_calls_ms": round(o, 5), "single_calls_rounds_ms": [round(t, 5) for t in one],
+                 "batch_rounds_ms": [round(t, 5) for t in many], "single_calls_spread_ms": round(spread, 5), "speedup": round(o / m, 3),
+                 "batch_faster_by_more_than_the_spread": bool(o - m > spread),
+                 "GB/s_per_vector_batch": round(g * nbytes_single / m / 1e6, 1), "GB/s_single_calls": round(g * nbytes_single / o / 1e6, 1)}
+    if hbm:      # hbm = the bytes of one more vector (x and r): the pass reads the matrix ONCE, its own share of the HBM peak
+        res[name]["batch_pass_frac_of_8TBs"] = round((nbytes_single + (g - 1) * hbm) / m / 1e6 / 8000.0, 4)
+        res[name]["single_call_frac_of_8TBs"] = round(g * nbytes_single / o / 1e6 / 8000.0, 4)
+
+
+for w in (4, 8):
+    if not any(selected(r) for r in MQF32B_ROWS if r.startswith(f"m{w}_")):
+        continue
+    mvm1, saa1, iht1 = (getattr(lib, f"clm{w}_{k}") for k in ("mvm_f32", "mvm_f32_scale_and_add", "iht_f32"))
+    mvmb, saab, ihtb = (getattr(lib, f"clm{w}_{k}_batch") for k in ("mvm_f32", "mvm_f32_scale_and_add", "iht_f32"))
+    transpose = lib.clm4_transpose if w == 4 else lib.clm8_transpose
+    for nb in (32768, 65536):
+        if not any(selected(f"m{w}_mvm_f32_batch{g}_{nb}^2") for g in MQF32B_GROUPS):
+            continue
+        fA, fsA = hip.alloc(nb * nb * w // 8), hip.alloc(4 * (nb // 64) ** 2)
+        hip.check(lib.clv_fill_random_nibbles(fA.ptr, fA.nbytes, 101, 0, None))
+        hip.check(lib.clv_fill_random_scales(fsA.ptr, fsA.nbytes // 4, 102, 0, None))
+        bx, br = [hip.alloc(4 * nb) for _ in range(8)], [hip.alloc(4 * nb) for _ in range(8)]
+        for j, b in enumerate(bx):
+            hip.check(lib.clv_fill_random_ints_f32(b.ptr, nb, 10, 110 + j, 0, None))
+        for g in MQF32B_GROUPS:
+            def singles(g=g):
+                for j in range(g):
+                    hip.check(mvm1(fA.ptr, fsA.ptr, nb, nb, bx[j].ptr, br[j].ptr, None))
+            rec_f32_batch(f"m{w}_mvm_f32_batch{g}_{nb}^2", fA.nbytes + fsA.nbytes + 8 * nb, g, singles,
+                          lambda g=g, a=(ptrs(bx[:g]), ptrs(br[:g])): hip.check(mvmb(fA.ptr, fsA.ptr, nb, nb, g, a[0], a[1], None)),
+                          reps=10 if nb == 32768 else 4, hbm=8 * nb)
+        del fA, fsA, bx, br
+    im, inn, ig, iters = 4096, 8192, 8, 10
+    if any(selected(r) for r in MQF32B_ROWS if r.startswith(f"m{w}_") and ("N8192" in r or "8192x4096" in r)):
+        P, sP, PT, sPT = (hip.alloc(n) for n in (im * inn * w // 8, 4 * (im // 64) * (inn // 64)) * 2)
+        hip.check(lib.clv_fill_random_nibbles(P.ptr, P.nbytes, 103, 0, None))
+        hip.check(lib.clv_fill_random_scales(sP.ptr, sP.nbytes // 4, 104, 0, None))
+        hip.check(transpose(P.ptr, sP.ptr, im, inn, PT.ptr, sPT.ptr, None))
+        V = {k: [hip.alloc(4 * ln) for _ in range(ig)] for k, ln in dict(y=im, x=inn, t1=im, t2=im, t3=inn, r=inn).items()}
+        for k in ("y", "x", "t2"):
+            for j, b in enumerate(V[k]):
+                hip.check(lib.clv_fill_random_ints_f32(b.ptr, b.nbytes // 4, 10, 500 + 10 * j + len(k), 0, None))
+        for sg in MQF32B_GROUPS:
+            def saa_singles(sg=sg):
+                for j in range(sg):
+                    hip.check(saa1(PT.ptr, sPT.ptr, inn, im, V["t2"][j].ptr, V["x"][j].ptr, 2.0 ** -24, V["t3"][j].ptr, V["r"][j].ptr, None))
+            rec_f32_batch(f"m{w}_mvm_f32_saa_batch{sg}_8192x4096", P.nbytes + sP.nbytes + 4 * im + 12 * inn, sg, saa_singles,
+                          lambda sg=sg, a=tuple(ptrs(V[k][:sg]) for k in ("t2", "x", "t3", "r")): hip.check(
+                              saab(PT.ptr, sPT.ptr, inn, im, sg, a[0], a[1], 2.0 ** -24, a[2], a[3], None)), reps=20, hbm=0)
+
+        def iht_singles():
+            for j in range(ig):
+                hip.check(iht1(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, V["x"][j].ptr, inn, V["y"][j].ptr, V["t1"][j].ptr, V["t2"][j].ptr,
+                               V["t3"][j].ptr, iters, inn // 4, 2.0 ** -24, 1, None))
+        A = {k: ptrs(v) for k, v in V.items()}
+        rec_f32_batch(f"m{w}_iht_f32_batch8_N8192", 2 * (P.nbytes + sP.nbytes), ig, iht_singles,
+                      lambda: hip.check(ihtb(P.ptr, sP.ptr, PT.ptr, sPT.ptr, im, inn, ig, A["x"], inn, A["y"], A["t1"], A["t2"], A["t3"], iters,
+                                             inn // 4, 2.0 ** -24, 1, None)), reps=2, hbm=0, per=iters)
+        if f"m{w}_iht_f32_batch8_N8192" in res:
+            res[f"m{w}_iht_f32_batch8_N8192"]["note"] = (f"ms per iteration for all 8 signals, calls of {iters} iterations, K = n / 4, FAST threshold; the "
+                                                        f"single calls are 8 x clm{w}_iht_f32 (three launches per iteration and signal)")
+        del P, sP, PT, sPT, V, A
+if ONLY and all(any(o in r for r in MQF32B_ROWS) for o in ONLY.split(",")):
+    print(json.dumps(res, indent=1))
+    sys.exit(0)
+
+
 # ---- vector ops at n = 2^30 (4 GiB fp32 source, 512 MiB + 64 MiB quantized) and n = 2^24
 for logn in (24, 30):
     n = 1 << logn
